@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fake-quant fwd+bwd throughput on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload at N=1 (BASELINE.json `metric`: "fake-quant fwd+bwd Gelem/s & achieved HBM GB/s,
 4096x11008 bf16 W4A8"; it is the per-tensor hot path of configs[1], LLaMA-7B W4-A8-KV4):
@@ -20,10 +20,16 @@ the same step on its own GPU, no data-path collective; value = N * per-rank elem
 anything touches a GPU; under `python -m torch.distributed.run` it joins the ranks the launcher started.
 A request for N ranks never reports fewer: if a rank is missing the run exits non-zero.
 
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...); nothing else.
+--dump-outputs DIR writes what the timed step computed in its LAST step to DIR/*.npy (float32 / float64, a fixed row sample of the
+forward outputs and gradients + every row's bounds; see dump_outputs), for output-for-output comparison of two builds.
+--full adds everything below: the product-default step, the sustained leg and every extras family (per-kernel roofline entries,
+autograd / API paths, model shapes, GPU eager chain, CPU baselines and the parity gate).
+
 Output (round 3): stdout carries exactly ONE line, a compact headline (< 4 KB: the contract's keys + `roofline`, `roofline_step`,
 `cpu_baseline`, `value_product_default`, `self_check`) -- the driver keeps an 8 KB stdout tail, and round 2's single 27 KB line was cut.
-Every other family below is printed as its own STDERR line ({"bench_extras": <family>, "data": ...}) and the whole record is
-written to bench_extras.json next to this file.
+With --full, every other family below is printed as its own STDERR line ({"bench_extras": <family>, "data": ...}) and the whole
+record is written to bench_extras.json next to this file.
 Families (every `frac` is a byte RATE the kernel sustained / 8 TB/s, never > 1):
   roofline      dominant kernel (the step's forward launch): algorithmic bytes / live HIP-event launch time vs 8 TB/s
   kernels_step  both launches of the step;  kernels  the four single-tensor launches
@@ -839,6 +845,30 @@ def ensure_built(local_rank, dist):
         dist.barrier()
 
 
+DUMP_SAMPLE_ROWS, DUMP_SAMPLE_SEED = 256, 0
+
+
+def dump_outputs(wl, i, out_dir):
+    """What step i of the timed path handed its caller, as float32 .npy files in out_dir (bf16 -> fp32 is exact): the forward outputs of
+    the set step i quantized (y_w4, y_a8) and the STE gradients of the set it ran the backward on (gx_w4, gx_a8), each on a fixed, seeded
+    sample of DUMP_SAMPLE_ROWS rows (sample_rows.npy, float64 row indices; 4 x 11.3 MB instead of 4 x 180 MB), and every row's recorded
+    bounds (bounds_w4, bounds_a8: [rows, 2]).  The 1-bit STE masks are left out: only their clippable rows are defined."""
+    import numpy as np
+    torch = wl.torch
+    os.makedirs(out_dir, exist_ok=True)
+    sf, sb = wl.sets[i % wl.nsets], wl.sets[(i + wl.nsets - 2) % wl.nsets]   # the sets step()/step_out_of_place() pick
+    rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(wl.rows, size=min(DUMP_SAMPLE_ROWS, wl.rows), replace=False))
+    idx = torch.from_numpy(rows).to(wl.device)
+    torch.cuda.synchronize()
+    arrays = {"sample_rows": rows.astype(np.float64),
+              "y_w4": sf["yw"][idx], "y_a8": sf["ya"][idx], "bounds_w4": sf["bw"], "bounds_a8": sf["ba"],
+              "gx_w4": sb["gxw"][idx], "gx_a8": sb["gxa"][idx]}
+    for name, a in arrays.items():
+        if not isinstance(a, np.ndarray):
+            a = a.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------------------------
 # launching: N ranks, one process per GPU
 # ----------------------------------------------------------------------------------------------
@@ -847,6 +877,11 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the product-default step, the sustained leg and every extras family (per-kernel roofline, "
+                         "autograd / API paths, model shapes, GPU eager chain, CPU baselines); the options below refine a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--sustain-seconds", type=float, default=5.0,
@@ -996,6 +1031,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args, argv)   # this process stays torch-free
 
@@ -1017,15 +1054,20 @@ def main(argv=None):
     # still timed, right after, under the same K / W / barrier / max-over-ranks protocol, as `value_product_default`.)
     seconds = timed_region(wl.step_out_of_place, args.steps, args.warmup, torch.cuda.synchronize, dist)
     PROFILE_MANIFEST.append(("timed region: step (both gradients written)", 2 * (args.steps + args.warmup)))
-    PROFILE_MANIFEST.append(("timed region: product-default step (weight gradient in place)", 2 * (args.steps + args.warmup)))
-    seconds_pd = timed_region(wl.step, args.steps, args.warmup, torch.cuda.synchronize, dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.warmup + args.steps - 1, args.dump_outputs)   # before anything else touches the buffer sets
     elems_step = 2 * wl.n
     value = aggregate_value(elems_step, args.steps, world, seconds)
-    sus_steps, sus_s, sus_chunks = sustained_region(wl.step_out_of_place, 0.0 if args.no_extras else args.sustain_seconds, torch.cuda.synchronize)
-    if sus_steps:
-        PROFILE_MANIFEST.append(("sustained: step (both gradients written)", 2 * sus_steps))
     ms_step = seconds / args.steps * 1e3
-    ms_step_pd = seconds_pd / args.steps * 1e3
+    if args.full:
+        PROFILE_MANIFEST.append(("timed region: product-default step (weight gradient in place)", 2 * (args.steps + args.warmup)))
+        seconds_pd = timed_region(wl.step, args.steps, args.warmup, torch.cuda.synchronize, dist)
+        sus_steps, sus_s, sus_chunks = sustained_region(wl.step_out_of_place, 0.0 if args.no_extras else args.sustain_seconds, torch.cuda.synchronize)
+        if sus_steps:
+            PROFILE_MANIFEST.append(("sustained: step (both gradients written)", 2 * sus_steps))
+        ms_step_pd = seconds_pd / args.steps * 1e3
+    else:
+        sus_steps = 0
     clip_frac = wl.clippable_fraction()
     mask_bytes_a = int(wl.n * clip_frac) // 8          # 1 bit/element for the A8 tensor's clippable rows; the W4 tensor has none
     algo_bytes_step = elems_step * (FWD_BYTES_PER_ELEM + BWD_BYTES_PER_ELEM)
@@ -1047,16 +1089,20 @@ def main(argv=None):
                                "to fresh tensors (the reference's grad_output.clone()); value_product_default = the same step with the "
                                "weight's gradient masked in place (gx == g: rows that cannot clip -- all of a weight's -- are not touched)",
                    "launches_per_step": "2 (weight + input of a QuantizeLinear share one forward and one backward launch)"},
-        # the product's default data flow (utils_quant.py point 6): the weight's gradient handed on by reference.  NOT the headline: its
-        # backward touches half the elements, so elements/s on it is not comparable with the 10 B/elem accounting
-        "value_product_default": round(aggregate_value(elems_step, args.steps, world, seconds_pd), 2),
-        "ms_per_step_product_default": round(ms_step_pd, 4),
         # elements whose gradient the timed backward reads + writes
-        "backward_elements_touched": 2 * wl.n, "backward_elements_touched_product_default": wl.n,
+        "backward_elements_touched": 2 * wl.n,
         "hbm_gbs_moved": round(moved_bytes_step / (ms_step * 1e-3) / 1e9 * world, 1),
-        "hbm_gbs_moved_product_default": round(moved_bytes_step_pd / (ms_step_pd * 1e-3) / 1e9 * world, 1),
         "hbm_gbs_note": "bytes the step's two launches move (fwd 4 + bwd 4 B/elem + mask bits) / ms_per_step: a real byte rate",
     }
+    if args.full:
+        # the product's default data flow (utils_quant.py point 6): the weight's gradient handed on by reference.  NOT the headline: its
+        # backward touches half the elements, so elements/s on it is not comparable with the 10 B/elem accounting
+        out.update({"value_product_default": round(aggregate_value(elems_step, args.steps, world, seconds_pd), 2),
+                    "ms_per_step_product_default": round(ms_step_pd, 4),
+                    "backward_elements_touched_product_default": wl.n,
+                    "hbm_gbs_moved_product_default": round(moved_bytes_step_pd / (ms_step_pd * 1e-3) / 1e9 * world, 1)})
+    if args.dump_outputs:
+        out["dumped_outputs"] = args.dump_outputs
     out.update(info)
     if sus_steps:
         cs = sorted(sus_chunks)
@@ -1066,7 +1112,7 @@ def main(argv=None):
                             "what": "rank 0, the headline step back to back for `seconds` (1000-step chunks, one sync each), after the timed "
                                     "region: steady-state rate per GPU; not the headline"}
 
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         traffic, tsrc = load_traffic()
         it = max(MIN_KERNEL_ITERS, min(args.steps, 1000))   # >= 200 launches per kernel whatever --steps says (time_launches enforces it too)
         nb = wl.n
@@ -1243,7 +1289,7 @@ def emit(out, args):
     stdout carries exactly ONE line, the compact headline (the launch contract: "rank 0 prints ONE JSON line")."""
     head_keys = set(_HEAD_KEYS) | {"config", "roofline", "roofline_step", "cpu_baseline", "hbm_gbs_note"}
     extras_file = None
-    if not getattr(args, "no_sidecar", False):
+    if getattr(args, "full", True) and not getattr(args, "no_sidecar", False):   # a plain run has no extras to write
         for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
             try:
                 if os.path.isdir(d):

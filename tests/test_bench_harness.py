@@ -288,3 +288,38 @@ def test_kernel_timing_protocol_is_independent_of_steps():
     assert bench.PROFILE_MANIFEST[-1] == ("k", t.warmup + 2 * t.iters)
     e = bench.roofline_entry("k", 1000, t)
     assert e["launches_timed"] >= 200 and e["warmup_launches"] >= 20 and abs(e["us_per_launch"] - 95.0) < 0.01
+
+
+# ---- a plain run measures the headline only; --full adds the rest; --dump-outputs writes the last timed step's results ----
+def test_plain_run_is_the_headline_and_full_is_opt_in():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_last_steps_sets_as_float_arrays(tmp_path, monkeypatch):
+    import types
+
+    import numpy as np
+    import torch
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    rows, cols = 600, 24
+    g = torch.Generator().manual_seed(0)
+    wl = types.SimpleNamespace(torch=torch, rows=rows, cols=cols, nsets=4, device="cpu", sets=[
+        {k: torch.randn(rows, 2 if k[0] == "b" else cols, generator=g).to(torch.float32 if k[0] == "b" else torch.bfloat16)
+         for k in ("yw", "ya", "gxw", "gxa", "bw", "ba")} for _ in range(4)])
+    i = 3 + 7 - 1                                   # warmup 3, steps 7: the last timed step
+    bench.dump_outputs(wl, i, str(tmp_path))
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == sorted(f"{n}.npy" for n in ("sample_rows", "y_w4", "y_a8", "gx_w4", "gx_a8", "bounds_w4", "bounds_a8"))
+    arr = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+    r = arr["sample_rows"].astype(np.int64)
+    assert len(r) == bench.DUMP_SAMPLE_ROWS and (np.diff(r) > 0).all() and r[-1] < rows
+    sf, sb = wl.sets[i % 4], wl.sets[(i + 2) % 4]   # the forward's set and the backward's set of step i
+    assert np.array_equal(arr["y_w4"], sf["yw"][torch.from_numpy(r)].float().numpy())
+    assert np.array_equal(arr["gx_a8"], sb["gxa"][torch.from_numpy(r)].float().numpy())
+    assert np.array_equal(arr["bounds_a8"], sf["ba"].numpy())
+    bench.dump_outputs(wl, i, str(tmp_path / "again"))  # the sample is fixed: the same rows every run
+    assert np.array_equal(np.load(tmp_path / "again" / "sample_rows.npy"), arr["sample_rows"])
