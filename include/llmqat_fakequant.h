@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FQ_ABI_VERSION 5 /* 5: + the *_v entry points: rows that do not follow one another in memory (fq_rows_view);  2: + multi-tensor launches, export, row scales, fq_w12_fwd_rows; 3: the STE mask is a plain row bitmap;
+#define FQ_ABI_VERSION 6 /* 6: + fq_group_fwd (group-wise scales);  5: + the *_v entry points: rows that do not follow one another in memory (fq_rows_view);  2: + multi-tensor launches, export, row scales, fq_w12_fwd_rows; 3: the STE mask is a plain row bitmap;
                             4: fq_sym_fwd_autocast takes `sem` (and the autocast modes of pair / multi / export / row_scales honour it),
                                launch status from hipLaunchKernel's return value (the hipGetLastError slot is left alone), fq_qlinear_fwd (an experiment with test hooks in its signature) left the library, fq_w12_fwd_rows sums
                                in ATen's own order (no `sem`) */
@@ -347,6 +347,25 @@ int fq_asym_export(const void* x, void* bins_out, float* scales_out, int32_t* ov
  */
 int fq_sym_row_scales(const void* x, float* scales_out, int64_t rows, int64_t cols, int bits, int dtype, int sem, int autocast, float lo,
                       float hi, float* row_bounds_out, void* mask_out, size_t mask_bytes, void* stream);
+
+/*
+ * ---- group-wise scales (ABI 6) ----------------------------------------------------------------------------------------------------------
+ * The int4 deployment format: every run of `group` consecutive elements of a row has its own scale (g = 128 is the usual choice).
+ * Semantics:  y = Q(x.reshape(-1, group)).reshape(x.shape), with Q = SymQuantizer.forward (asym = 0, models/utils_quant.py:37-74) or
+ * AsymQuantizer.forward (asym = 1, :96-149) in the arithmetic of the row-wise entry points (`sem`; autocast = 1: fq_sym_fwd_autocast with
+ * wide_out = 0).  Every NaN / Inf / +-0 rule of the row-wise path applies per group; group == cols is the row-wise result.
+ *   x, y            [rows, cols] `dtype` (bf16 / fp16 / fp32), contiguous, 16-byte aligned; y may not alias x
+ *   group           divides cols
+ *   row_bounds_out  optional float[rows][2]: bounds of the WHOLE row ({+m, -m} / {max, min}, as fq_*_fwd_train writes them)
+ *   mask_out        optional (needs row_bounds_out): the ABI-3 row bitmap of fq_*_fwd_train, fq_ste_mask_bytes(rows, cols, dtype) bytes;
+ *                   lo / hi = the STE clip.  The STE backward does not depend on the group: fq_ste_bwd_mask (copying or in place) serves it.
+ * Served: groups of 4..64 16-byte vectors (bf16 / fp16: group 32, 64, 128, 256; fp32: 64, 128, 256) in rows of <= 8192 vectors.
+ * FQ_ERR_UNSUPPORTED for anything else (other divisors, float64, misaligned tensors): quantize the [rows * cols / group, group] view with
+ * the row-wise entry points instead -- same values.
+ */
+int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t cols, int64_t group, int bits, int dtype, int sem,
+                 int autocast /* 0 or 1 */, float lo, float hi, float* row_bounds_out, void* mask_out, size_t mask_bytes,
+                 void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # LLMQAT_AMD_LIB points the loader at another build of the library (A/B runs of kernel variants: tools/ab_bench.sh) -- the product
 # file is never overwritten; fq_build_info() / LIB_PATH say which one is loaded
 LIB_PATH = os.environ.get("LLMQAT_AMD_LIB") or os.path.join(HERE, "libllmqat_fakequant.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16, DTYPE_F64 = 0, 1, 2, 3
 SEM_CPU_EAGER, SEM_DEVICE_EAGER = 0, 1
@@ -24,6 +24,7 @@ EXPORTS = (
     "fq_w12_fwd", "fq_sym_fwd_autocast", "fq_sym_fwd_pair", "fq_ste_bwd_mask_pair", "fq_ste_bwd_mask_wide",
     "fq_export_bins_bytes", "fq_sym_export", "fq_asym_export", "fq_sym_row_scales", "fq_sym_fwd_multi", "fq_ste_bwd_mask_multi", "fq_w12_fwd_rows",
     "fq_rowwise_fwd_v", "fq_sym_fwd_multi_v", "fq_ste_bwd_mask_multi_v", "fq_ste_bwd_v",
+    "fq_group_fwd",
 )
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
@@ -124,6 +125,8 @@ def _bind(L):
     L.fq_ste_bwd_mask_multi_v.restype = i32
     L.fq_ste_bwd_v.argtypes = [vp, rv, vp, rv, vp, rv, i64, i64, f32, f32, vp, i32, vp]
     L.fq_ste_bwd_v.restype = i32
+    L.fq_group_fwd.argtypes = [i32, vp, vp, i64, i64, i64, i32, i32, i32, i32, f32, f32, vp, vp, sz, vp]
+    L.fq_group_fwd.restype = i32
     return L
 
 

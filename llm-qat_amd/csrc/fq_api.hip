@@ -433,4 +433,52 @@ FQ_API int fq_ste_bwd_v(const void* g, const fq_rows_view* gv, const void* x, co
     }
 }
 
+FQ_API int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t cols, int64_t group, int bits, int dtype, int sem, int autocast,
+                        float lo, float hi, float* row_bounds_out, void* mask_out, size_t mask_bytes, void* stream) {
+    // every check comes before any division or launch (the ABI fuzz passes group = 0, negatives and 2^62)
+    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
+    if (asym != 0 && asym != 1) return fail(FQ_ERR_ARG, "asym must be 0 or 1");
+    if (bits < 1 || bits > 31) return fail(FQ_ERR_BITS, "num_bits=%d outside [1, 31]", bits);
+    if (sem != FQ_SEM_CPU_EAGER && sem != FQ_SEM_DEVICE_EAGER) return fail(FQ_ERR_ARG, "unknown semantics code %d", sem);
+    if (autocast != 0 && autocast != 1) return fail(FQ_ERR_ARG, "autocast must be 0 or 1 (the fp32-result form is not served here)");
+    if (autocast && (asym || (dtype != FQ_DTYPE_BF16 && dtype != FQ_DTYPE_F16)))
+        return fail(FQ_ERR_DTYPE, "autocast arithmetic applies to SymQuantizer on bf16 / fp16 tensors only");
+    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
+    if (group <= 0) return fail(FQ_ERR_ARG, "group=%lld must be positive", (long long)group);
+    if (cols % group != 0) return fail(FQ_ERR_SHAPE, "group=%lld does not divide cols=%lld", (long long)group, (long long)cols);
+    if (cols > 0 && rows > INT64_MAX / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
+    if (rows == 0 || cols == 0) return ok();
+    if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
+    if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+    if (mask_out && !row_bounds_out) return fail(FQ_ERR_NULL, "a mask needs row_bounds_out too");
+    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_UNSUPPORTED, "float64: quantize the [rows * cols / group, group] view with fq_sym_fwd / fq_asym_fwd");
+    const int es = esize_of(dtype), epv = 16 / es;
+    if (cols / epv > REG_MAX_VEC) return fail(FQ_ERR_UNSUPPORTED, "rows longer than %lld vectors are not served", (long long)REG_MAX_VEC);
+    const int64_t gbytes = group * es;   // group <= cols <= 8 * REG_MAX_VEC: no overflow
+    const int64_t gv = gbytes / 16;
+    if (gbytes % 16 != 0 || !(gv == 4 || gv == 8 || gv == 16 || gv == 32 || gv == 64))
+        return fail(FQ_ERR_UNSUPPORTED, "group=%lld: the kernel serves groups of 4..64 16-byte vectors (bf16 / fp16 g = 32..256, fp32 g = 64..256)", (long long)group);
+    if (rows > 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "rows=%lld exceeds the grid limit", (long long)rows);
+    if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "x / y must be 16-byte aligned");
+    const Consts c = make_consts(bits, dtype, sem);
+    RowArgs a{x, y, nullptr, nullptr, row_bounds_out, rows, cols, c.sym, c.asym, nullptr, 0, 0.f, 0.f, 0u, rows, 0, {}};
+    if (mask_out) {
+        const int64_t mrw = mask_row_words(cols, es);
+        if (mask_bytes < (size_t)rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)rows * mrw * 8);
+        a.mask = (uint64_t*)mask_out;
+        a.mask_row_words = mrw;
+        a.lo = host_rb(lo, dtype);
+        a.hi = host_rb(hi, dtype);
+        a.clipk = ste_clip_key(a.lo, a.hi, dtype);
+    }
+    seal_slots(a);
+    hipStream_t st = (hipStream_t)stream;
+    const bool fast = asym ? bits <= 8 : true;   // as rowwise(): only bf16 honours it
+    switch (dtype) {
+        case FQ_DTYPE_F32: return launch_group<F32>(asym != 0, fast, 0, a, (int)gv, st);
+        case FQ_DTYPE_F16: return launch_group<F16>(asym != 0, fast, autocast, a, (int)gv, st);
+        default: return launch_group<BF16>(asym != 0, fast, autocast, a, (int)gv, st);
+    }
+}
+
 }  // extern "C"

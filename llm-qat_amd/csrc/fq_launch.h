@@ -175,6 +175,9 @@ FQ_HIDDEN int launch_f64_w12(const void* w, const void* scale, void* out, int64_
 template <int DT> FQ_HIDDEN int launch_rowwise(bool asym, bool fast, RowArgs a, void* ws, size_t wsb, hipStream_t st);
 // Sym under CUDA-autocast arithmetic (16-bit tensors only): wide = fp32 output, else rounded once to the tensor dtype
 template <int DT> FQ_HIDDEN int launch_sym_autocast(bool wide, RowArgs a, void* ws, size_t wsb, hipStream_t st);
+// group-wise forward (fq_group.h / fq_group.hip): a = x, y, rows, cols, constants and the optional training-mode outputs; gv = vectors
+// per group (4 .. 64); autocast = 1: Sym under autocast with the result rounded once to the tensor dtype (16-bit tensors)
+template <int DT> FQ_HIDDEN int launch_group(bool asym, bool fast, int autocast, RowArgs a, int gv, hipStream_t st);
 template <int DT> FQ_HIDDEN int launch_ste(const void* g, const void* x, void* gx, int64_t n, float lo, float hi, hipStream_t st);
 // STE backward from (bounds, mask) for the L.n tensors of one launch (g / gx / bounds / mask / rows filled in by the caller;
 // blk_begin / inplace are set here)

@@ -673,10 +673,19 @@ def multi_backward(grads, sides, rows, cols, lo, hi, inplace=None):
     return out
 
 
-def quantize_train(kind, x, num_bits, layerwise, lo, hi):
+def quantize_train(kind, x, num_bits, layerwise, lo, hi, group_size=None):
     """Training-mode forward (fq_*_fwd_train): -> (y, row_bounds, mask) or None if this shape/alignment is
     not served by the STE-mask path (the caller then uses the general forward + x-based backward).
-    Convenience form of train_forward() with the side buffer split into its two views."""
+    Convenience form of train_forward() with the side buffer split into its two views.
+    group_size: group-wise scales (fq_group_fwd); the bounds and the mask keep the full-row layout, so ste_backward_mask serves them."""
+    if group_size is not None:
+        g = check_group(tuple(x.shape), group_size, layerwise)
+        _prep(x, f"{kind}_quantize")
+        res = group_forward(kind, x, num_bits, g, lo=float(lo), hi=float(hi), train=True)
+        if res is None:
+            return None
+        y, side, rows, _ = res
+        return y, side[: rows * 8].view(torch.float32).view(rows, 2), side[rows * 8:]
     res = train_forward(kind, x, num_bits, layerwise, float(lo), float(hi))
     if res is None:
         return None
@@ -736,14 +745,110 @@ def low_bit_weight_fused(w, w_bits):
     return out, scale
 
 
-def sym_quantize(x, num_bits, layerwise=False, want_bounds=False):
-    """SymQuantizer.forward (utils_quant.py:37-74).  -> y, or (y, row_bounds) if want_bounds."""
+# ---- group-wise scales: every run of `group_size` consecutive elements of a row has its own scale ------------------------------------
+# y = Q(x.reshape(-1, g)).reshape(x.shape), in the arithmetic the row-wise path uses for that tensor.  Where fq_group_fwd serves the shape
+# (contiguous 16-byte aligned bf16 / fp16 / fp32, groups of 4..64 16-byte vectors, rows that fit the register kernels) it runs one launch
+# with the side outputs of the FULL row; everything else takes the row-wise kernels on the [rows * C / g, g] view (same values).  Which of
+# the two ran is counted here (utils_quant.stats() reports it): the route follows from the inputs alone.
+group_counts = {"group_launch": 0, "group_view_route": 0}
+
+
+def check_group(shape, group_size, layerwise=False):
+    """-> g as an int after the argument checks of the group-wise API (ValueError for what is not defined)"""
+    if isinstance(group_size, (bool, str)) or isinstance(group_size, torch.Tensor):
+        raise ValueError(f"group_size must be a positive integer, got {group_size!r}")
+    if not isinstance(group_size, int):
+        try:
+            g = int(group_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"group_size must be a positive integer, got {group_size!r}") from None
+        if g != group_size:
+            raise ValueError(f"group_size must be a positive integer, got {group_size!r}")
+    else:
+        g = group_size
+    if layerwise:
+        raise ValueError("group_size cannot be combined with layerwise=True")
+    if len(shape) > 3:
+        raise ValueError(f"group-wise fake quantization takes tensors of at most 3 dimensions, got {len(shape)}")
+    if g <= 0:
+        raise ValueError(f"group_size must be positive, got {g}")
+    cols = shape[-1] if len(shape) else 1
+    if cols % g:
+        raise ValueError(f"group_size={g} does not divide the last dimension ({cols})")
+    return g
+
+
+def group_forward(kind, x, num_bits, group_size, autocast=False, lo=-2.0, hi=2.0, train=False):
+    """fq_group_fwd -> (y, side, rows, cols) or None when the kernel does not serve this tensor (the caller takes the view route).
+    side: None, or (train=True) one uint8 buffer of float[rows][2] full-row bounds followed by the row bitmap, as train_forward's."""
+    code = _DTYPES.get(x.dtype)
+    if code is None or code == _lib.DTYPE_F64 or not x.is_cuda or not x.is_contiguous() or x.numel() == 0 or x.data_ptr() & 15:
+        return None
+    rows, cols = rows_cols(tuple(x.shape), False)
+    side = None
+    bp = mp = None
+    mbytes = 0
+    if train:
+        mbytes = _mask_bytes(rows, cols, code)
+        if not mbytes:
+            return None
+        side = torch.empty(rows * 8 + mbytes, dtype=torch.uint8, device=x.device)
+        bp = side.data_ptr()
+        mp = bp + rows * 8
+    y = torch.empty_like(x)
+    sem = _SEM_AUTOCAST if autocast else _semantics
+    L = _lib.lib()
+    rc = _on_device(x, lambda st: L.fq_group_fwd(1 if kind == "asym" else 0, x.data_ptr(), y.data_ptr(), rows, cols, int(group_size), int(num_bits), code,
+                                                 sem, 1 if autocast else 0, float(lo), float(hi), bp, mp, mbytes, st))
+    if rc == _lib.ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, f"{kind}_quantize[group]")
+    group_counts["group_launch"] += 1
+    return y, side, rows, cols
+
+
+def group_view(x, group_size):
+    """the [rows * C / g, g] view the row-wise path quantizes for the view route (a copy where x's layout has no such view)"""
+    return x.reshape(-1, group_size)
+
+
+def _grouped(kind, x, num_bits, group_size, want_bounds):
+    g = check_group(tuple(x.shape), group_size)
+    code = _prep(x, f"{kind}_quantize")
+    res = group_forward(kind, x, num_bits, g, lo=-2.0, hi=2.0, train=False) if not want_bounds else None
+    if res is None and want_bounds:
+        res = group_forward(kind, x, num_bits, g, lo=-2.0, hi=2.0, train=True)
+    if res is not None:
+        y, side, rows, _ = res
+        return (y, side[: rows * 8].view(torch.float32).view(rows, 2)) if want_bounds else y
+    group_counts["group_view_route"] += 1
+    if x.numel() == 0:
+        return (torch.empty_like(x), None) if want_bounds else torch.empty_like(x)
+    yv, bv, _, _ = _rowwise(kind, group_view(x, g), num_bits, False, want_bounds and code != _lib.DTYPE_F64, False)
+    y = yv.reshape(x.shape)
+    if not want_bounds:
+        return y
+    if bv is None:
+        return y, None
+    rows, _ = rows_cols(tuple(x.shape), False)
+    b = bv.view(rows, -1, 2)   # per-group bounds -> the row's (max / min propagate NaN, as the kernels' bounds do)
+    return y, torch.stack((b[..., 0].amax(1), b[..., 1].amin(1)), 1)
+
+
+def sym_quantize(x, num_bits, layerwise=False, want_bounds=False, group_size=None):
+    """SymQuantizer.forward (utils_quant.py:37-74).  -> y, or (y, row_bounds) if want_bounds.
+    group_size: one scale per `group_size` consecutive elements of a row (the forward of the [-1, group_size] view); row_bounds are
+    still those of the whole row."""
+    if group_size is not None:
+        return _grouped("sym", x, num_bits, group_size, want_bounds)
     y, bounds, _, _ = _rowwise("sym", x, num_bits, layerwise, want_bounds, False)
     return (y, bounds) if want_bounds else y
 
 
-def asym_quantize(x, num_bits, layerwise=False, want_bounds=False):
-    """AsymQuantizer.forward (utils_quant.py:96-149)."""
+def asym_quantize(x, num_bits, layerwise=False, want_bounds=False, group_size=None):
+    """AsymQuantizer.forward (utils_quant.py:96-149).  group_size: as sym_quantize."""
+    if group_size is not None:
+        return _grouped("asym", x, num_bits, group_size, want_bounds)
     y, bounds, _, _ = _rowwise("asym", x, num_bits, layerwise, want_bounds, False)
     return (y, bounds) if want_bounds else y
 
@@ -810,8 +915,10 @@ class QuantExport:
                 element 2k in the low nibble of byte k
       scales    float32 [rows, 2]: Sym {s, t2 = s + 1e-6};  Asym {a = alpha + 1e-8, beta}
       overflow  int32 [rows]: elements the container saturated (0 everywhere <=> dequantize() == the fake-quant forward)
+    group_size None (one scale per row), or g: scales are float32 [rows, cols / g, 2] and overflow int32 [rows, cols / g], one entry per
+                group; int4 bins of an even g are byte for byte the row-major packing of the full rows ([rows, cols / 2])
     """
-    __slots__ = ("kind", "bins", "scales", "overflow", "container", "num_bits", "shape", "rows", "cols", "dtype")
+    __slots__ = ("kind", "bins", "scales", "overflow", "container", "num_bits", "shape", "rows", "cols", "dtype", "group_size")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -823,8 +930,10 @@ class QuantExport:
         if self.container != "int4":
             v = b.reshape(self.rows, self.cols).to(torch.int32)
             return v & 0xFFFF if (self.kind == "asym" and self.container == "int16") else v   # unsigned 16-bit bins
+        g = getattr(self, "group_size", None)
+        prow, pcols = (self.rows, self.cols) if g is None else (self.rows * (self.cols // g), g)   # rows as packed: the group view's
         lo, hi = (b & 0xF).to(torch.int32), (b >> 4).to(torch.int32)
-        v = torch.stack((lo, hi), dim=-1).reshape(self.rows, -1)[:, : self.cols]
+        v = torch.stack((lo, hi), dim=-1).reshape(prow, -1)[:, :pcols].reshape(self.rows, self.cols)
         return torch.where(v >= 8, v - 16, v) if self.kind == "sym" else v
 
     def dequantize(self):
@@ -834,6 +943,10 @@ class QuantExport:
         q = self.unpacked().to(torch.float32)
         sc = self.scales
         dt = self.dtype
+        g = getattr(self, "group_size", None)
+        if g is not None:   # one scale per group: the row-wise formula on the [rows * cols / g, g] view
+            q = q.reshape(-1, g)
+            sc = sc.reshape(-1, 2)
         if self.kind == "sym":
             y = (q / sc[:, 1:2]).to(dt)
         else:
@@ -854,6 +967,21 @@ def default_container(kind, num_bits, dtype):
     if num_bits <= 7 or (num_bits == 8 and dtype != torch.bfloat16):
         return "int8"
     return "int16"
+
+
+def _export_grouped(kind, x, num_bits, group_size, container, autocast):
+    """the export kernels on the [rows * C / g, g] view (no kernel of its own), reshaped to the full tensor's rows"""
+    g = check_group(tuple(x.shape), group_size)
+    _prep(x, f"{kind}_export")
+    e = _export(kind, group_view(x, g), num_bits, False, container, autocast)
+    rows, cols = rows_cols(tuple(x.shape), False)
+    bins = e.bins
+    if e.container != "int4":
+        bins = bins.reshape(x.shape)
+    elif g % 2 == 0:
+        bins = bins.reshape(rows, cols // 2)
+    return QuantExport(kind=kind, bins=bins, scales=e.scales.view(rows, cols // g, 2), overflow=e.overflow.view(rows, cols // g),
+                       container=e.container, num_bits=e.num_bits, shape=tuple(x.shape), rows=rows, cols=cols, dtype=x.dtype, group_size=g)
 
 
 def _export(kind, x, num_bits, layerwise, container, autocast):
@@ -887,18 +1015,28 @@ def _export(kind, x, num_bits, layerwise, container, autocast):
     else:
         bins = raw.view(rows, (cols + 1) // 2)
     return QuantExport(kind=kind, bins=bins, scales=scales, overflow=overflow, container=container, num_bits=int(num_bits),
-                       shape=tuple(xc.shape), rows=rows, cols=cols, dtype=x.dtype)
+                       shape=tuple(xc.shape), rows=rows, cols=cols, dtype=x.dtype, group_size=None)
 
 
-def sym_export(x, num_bits, layerwise=False, container=None, autocast=None):
+def sym_export(x, num_bits, layerwise=False, container=None, autocast=None, group_size=None):
     """SymQuantizer's integer bins `torch.round(input * s)` (utils_quant.py:71-72) packed into int4 / int8 / int16 + per-row
-    {s, t2}.  autocast: None = follow torch.is_autocast_enabled (as the forward does), or force True / False."""
+    {s, t2}.  autocast: None = follow torch.is_autocast_enabled (as the forward does), or force True / False.
+    group_size: {s, t2} per group of `group_size` elements (see QuantExport)."""
     ac = autocast_active(x) if autocast is None else bool(autocast)
+    if group_size is not None:
+        if layerwise:
+            check_group(tuple(x.shape), group_size, layerwise)
+        return _export_grouped("sym", x, num_bits, group_size, container, ac)
     return _export("sym", x, num_bits, layerwise, container, ac)
 
 
-def asym_export(x, num_bits, layerwise=False, container=None):
-    """AsymQuantizer's bins `torch.round(input_normalized * s)` (utils_quant.py:144-146), unsigned, + per-row {alpha+1e-8, beta}"""
+def asym_export(x, num_bits, layerwise=False, container=None, group_size=None):
+    """AsymQuantizer's bins `torch.round(input_normalized * s)` (utils_quant.py:144-146), unsigned, + per-row {alpha+1e-8, beta}
+    group_size: {alpha+1e-8, beta} per group of `group_size` elements (see QuantExport)."""
+    if group_size is not None:
+        if layerwise:
+            check_group(tuple(x.shape), group_size, layerwise)
+        return _export_grouped("asym", x, num_bits, group_size, container, False)
     return _export("asym", x, num_bits, layerwise, container, False)
 
 

@@ -105,13 +105,20 @@ def stats(reset=False):
                                          leans on is missing in this build (fail closed; warned once)
       w12_fused_unverified               1-/2-bit weights that took ATen's own abs + mean because the one-launch kernel's restatement of
                                          ATen's summation order did not verify on this device / torch build
+      group_launch / group_view_route    group-wise forwards served by the group kernel (fq_group_fwd) / by the row-wise kernels on the
+                                         [-1, group_size] view (other divisors, strided or misaligned tensors, float64, fp32-result autocast)
       cpp_pair_forward / cpp_weight_forward / cpp_pair_backward / cpp_one_backward / cpp_slow_backward
                                          what the C++ autograd nodes did (_fq_node.so; `host_node()` says whether it is loaded): operand-pair and
                                          weight-only launches made from C++, pair / one-tensor (K, V) backwards, and backwards handed back to the
                                          Python nodes' code"""
     out = dict(_stats)
+    for k, v in ops.group_counts.items():   # group-wise forwards (ops.group_forward): kernel launches / row-wise kernels on the view
+        if v:
+            out[k] = out.get(k, 0) + v
     if reset:
         _stats.clear()
+        for k in ops.group_counts:
+            ops.group_counts[k] = 0
     if _cnode is not None:      # what the C++ node counted (its guard's decisions, its launches): same names
         for k, v in _cnode.counters(reset).items():
             out[k] = out.get(k, 0) + v
@@ -328,6 +335,85 @@ class AsymQuantizer(_FakeQuantFunction):
             if out is not None:
                 return out
         return super().apply(input, clip_val, num_bits, layerwise)
+
+
+def _compute_group(kind, input, clip_val, num_bits, group, narrow, need_grad):
+    """_compute for group-wise scales: y = Q(input.reshape(-1, group)).reshape(input.shape).  The group kernel records the side outputs of the
+    full rows, so its "mask" _Raw is the row-wise one and every backward below serves it; the view route saves the input (the STE backward is
+    elementwise and does not see the groups)."""
+    if input.device.type == "cpu":   # opt-in CPU tensors (cpu_tensors.py): the torch ops on the view
+        if not cpu_tensors.ENABLED:
+            cpu_tensors.refuse(input, f"{kind}_quantize")
+        return _Raw(cpu_tensors.forward(kind, ops.group_view(input, group), num_bits, False).reshape(input.shape), "cpu", (input, clip_val))
+    ops._prep(input, f"{kind}_quantize")
+    ac = kind == "sym" and ops.autocast_active(input)
+    narrow = ac and narrow and ops.autocast_narrow_ok(input)
+    lo, hi = _clip_pair(clip_val)
+    grad_dtype = input.dtype if ac else None
+    if not ac or narrow:   # (the fp32-result autocast form is not served by the kernel)
+        train = need_grad and _BACKWARD_MODE == "mask"
+        res = ops.group_forward(kind, input, num_bits, group, autocast=ac, lo=lo, hi=hi, train=train)
+        if res is not None:
+            out, side, rows, cols = res
+            if not need_grad:
+                return _Raw(out, "none")
+            if train:
+                return _Raw(out, "mask", (side,), (lo, hi), (rows, cols), grad_dtype)
+            return _Raw(out, "plain", (input, clip_val), (lo, hi), (rows, cols), grad_dtype)
+    ops.group_counts["group_view_route"] += 1
+    xv = ops.group_view(input, group)
+    if ac:
+        out = ops.sym_forward_autocast(xv, num_bits, False, wide=not narrow)[0]
+    else:
+        out = ops.sym_quantize(xv, num_bits) if kind == "sym" else ops.asym_quantize(xv, num_bits)
+    out = out.reshape(input.shape)
+    if not need_grad:
+        return _Raw(out, "none")
+    return _Raw(out, "plain", (input, clip_val), (lo, hi), ops.rows_cols(tuple(input.shape), False), grad_dtype)   # reference :45 / :104
+
+
+class _GroupQuantizer(torch.autograd.Function):
+    """SymQuantizer / AsymQuantizer with one scale per `group` consecutive elements of a row; the unchanged STE backward (:77-87)."""
+
+    @staticmethod
+    def forward(ctx, input, clip_val, num_bits, group, kind, narrow, inplace_grad):
+        if type(num_bits) is not int:
+            num_bits = ops.bits_arg(num_bits)
+        if torch.compiler.is_compiling():   # the custom ops of compiled.py on the view
+            ctx.save_for_backward(input, clip_val)
+            ctx.fq_mode = "compiled"
+            return compiled.fake_quant(kind, ops.group_view(input, group), clip_val, num_bits, False, narrow).reshape(input.shape)
+        raw = _compute_group(kind, input, clip_val, num_bits, group, narrow, ctx.needs_input_grad[0])
+        _attach(ctx, raw, inplace_grad)
+        return raw.out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return _FakeQuantFunction.backward(ctx, grad_output) + (None, None, None)
+
+
+def group_quantize(x, clip_val, num_bits, group_size, symmetric=True):
+    """Group-wise fake quantization with the reference's straight-through gradient: SymQuantizer (symmetric) or AsymQuantizer applied to
+    `x.reshape(-1, group_size)`, result in x's shape.  x has at most 3 dimensions and group_size divides its last one."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"group_quantize: expected a torch.Tensor, got {type(x).__name__}")
+    g = ops.check_group(tuple(x.shape), group_size)
+    return _GroupQuantizer.apply(x, clip_val, num_bits, g, "sym" if symmetric else "asym", False, False)
+
+
+_DEFAULT_GROUPS = (None, None)   # (weight, activation) group sizes of QuantizeLinears constructed without explicit ones
+
+
+def default_group_sizes(weight=None, act=None):
+    """Group sizes the QuantizeLinears constructed from now on take when their own weight_group_size / act_group_size are not given
+    (None: one scale per row).  Lets unchanged model code (LLM-QAT's train.py) train for a group-wise export.  -> the previous pair."""
+    global _DEFAULT_GROUPS
+    prev = _DEFAULT_GROUPS
+    for name, g in (("weight", weight), ("act", act)):
+        if g is not None:
+            ops.check_group((g,), g)
+    _DEFAULT_GROUPS = (weight, act)
+    return prev
 
 
 class _LowBitWeightCpu(torch.autograd.Function):
@@ -1090,14 +1176,30 @@ def _precomputed(x, y, side, rows, cols, clip):
 
 class QuantizeLinear(nn.Linear):
     _fq_plan = None   # (input shape, input dtype, weight dtype, ops.pair_plan): the launch plan of the last input shape (a plain attribute)
+    weight_group_size = None   # group-wise scales (plain attributes: state_dict() keys stay the reference's)
+    act_group_size = None
 
     def __init__(self, *kargs, symmetric=True, bias=False, w_bits=32, a_bits=32, act_layerwise=False,
-                 weight_layerwise=False):
+                 weight_layerwise=False, weight_group_size=None, act_group_size=None):
         super().__init__(*kargs, bias=False)  # `bias` is accepted and ignored, as in the reference (:176)
         self.w_bits = w_bits
         self.a_bits = a_bits
         self.act_layerwise = act_layerwise
         self.weight_layerwise = weight_layerwise
+        # group sizes: an explicit argument is checked and kept; the process default (default_group_sizes) applies where it means something
+        dw, da = _DEFAULT_GROUPS
+        if weight_group_size is not None:
+            if not 3 <= w_bits < 32:
+                raise ValueError(f"weight_group_size applies to SymQuantizer weights (3 <= w_bits < 32), this layer has w_bits={w_bits}")
+            self.weight_group_size = ops.check_group(tuple(self.weight.shape), weight_group_size, weight_layerwise)
+        elif dw is not None and 3 <= w_bits < 32 and not weight_layerwise:
+            self.weight_group_size = ops.check_group(tuple(self.weight.shape), dw)
+        if act_group_size is not None:
+            if not 2 < a_bits < 32:
+                raise ValueError(f"act_group_size applies to quantized activations (2 < a_bits < 32), this layer has a_bits={a_bits}")
+            self.act_group_size = ops.check_group((self.in_features,), act_group_size, act_layerwise)
+        elif da is not None and 2 < a_bits < 32 and not act_layerwise:
+            self.act_group_size = ops.check_group((self.in_features,), da)
         if 2 < self.a_bits < 32:
             self.act_quantizer = SymQuantizer if symmetric else AsymQuantizer   # (attribute absent otherwise, as in the reference :184-188)
         self._act_kind = "sym" if symmetric else "asym"  # what torch.compile's trace reads (a class identity test does not trace)
@@ -1126,6 +1228,8 @@ class QuantizeLinear(nn.Linear):
 
     def _quantized_weight(self):
         w = self.weight
+        if self.weight_group_size is not None:   # (no weight cache for grouped weights)
+            return _GroupQuantizer.apply(w, _CLIP, self.w_bits, self.weight_group_size, "sym", True, True)
         ac = ops.autocast_active(w)
         if not _WEIGHT_CACHE or not w.is_cuda or w.is_inference() or (ac and not ops.autocast_narrow_ok(w)):
             # (an fp16 weight inside autocast(bf16), or the reverse, gets the reference's fp32 result and an fp32 gradient:
@@ -1173,11 +1277,14 @@ class QuantizeLinear(nn.Linear):
         plan = self._fq_plan
         # (the module's settings are plain attributes a caller may change after construction: they are part of what a plan is valid for)
         if (plan is None or plan[0] != input_.shape or plan[1] is not input_.dtype or plan[2] is not weight.dtype
-                or plan[4] != (self.w_bits, self.a_bits, self.act_layerwise, self.weight_layerwise, getattr(self, "act_quantizer", None))):
+                or plan[4] != (self.w_bits, self.a_bits, self.act_layerwise, self.weight_layerwise, getattr(self, "act_quantizer", None),
+                               self.weight_group_size, self.act_group_size)):
+            # (grouped layers take the single-launch route: one group launch for the weight, the activation's own)
             ok = (3 <= self.w_bits < 32 and 2 < self.a_bits < 32 and getattr(self, "act_quantizer", None) is SymQuantizer and not self.act_layerwise
-                  and not self.weight_layerwise)
+                  and not self.weight_layerwise and self.weight_group_size is None and self.act_group_size is None)
             plan = self._fq_plan = (input_.shape, input_.dtype, weight.dtype, ops.pair_plan(weight, input_) if ok else None,
-                                    (self.w_bits, self.a_bits, self.act_layerwise, self.weight_layerwise, getattr(self, "act_quantizer", None)),
+                                    (self.w_bits, self.a_bits, self.act_layerwise, self.weight_layerwise, getattr(self, "act_quantizer", None),
+                                     self.weight_group_size, self.act_group_size),
                                     (ops.bits_arg(self.w_bits), ops.bits_arg(self.a_bits)) if ok else None)
         pp = plan[3]
         if pp is None or _WEIGHT_CACHE or not (weight.is_contiguous() and input_.is_contiguous()) or input_.is_inference() or weight.is_inference():
@@ -1250,6 +1357,8 @@ class QuantizeLinear(nn.Linear):
             return None   # no version counters under torch.inference_mode: nothing is paired, shared or remembered
         if self.act_quantizer is not SymQuantizer or self.act_layerwise or self.weight_layerwise:
             return None
+        if self.weight_group_size is not None or self.act_group_size is not None:
+            return None
         wkey = None
         if _WEIGHT_CACHE:
             # With the weight cache on, the FIRST use of a weight in a step still shares a launch with its input and fills the
@@ -1298,12 +1407,15 @@ class QuantizeLinear(nn.Linear):
         value the forward multiplies with, bit for bit where overflow == 0).  Serves the w_bits >= 3 path (:195-201)."""
         if not 3 <= self.w_bits < 32:
             raise ValueError(f"export_weight serves 3 <= w_bits < 32 (SymQuantizer weights), this layer has w_bits={self.w_bits}")
-        return ops.sym_export(self.weight.detach(), self.w_bits, self.weight_layerwise, container=container)
+        return ops.sym_export(self.weight.detach(), self.w_bits, self.weight_layerwise, container=container, group_size=self.weight_group_size)
 
     def _forward_compiled(self, input_):
         """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
         if self.w_bits >= 32:
             weight = self.weight
+        elif self.w_bits >= 3 and self.weight_group_size is not None:   # grouped: the same custom ops on the [-1, g] view
+            g = self.weight_group_size
+            weight = compiled.fake_quant("sym", self.weight.reshape(-1, g), _CLIP, self.w_bits, False, narrow=True).reshape(self.weight.shape)
         elif self.w_bits >= 3:
             weight = compiled.fake_quant("sym", self.weight, _CLIP, self.w_bits, self.weight_layerwise, narrow=True)
         else:
@@ -1311,7 +1423,10 @@ class QuantizeLinear(nn.Linear):
                 absmean = self.weight.abs().mean() if self.weight_layerwise else self.weight.abs().mean(dim=1, keepdim=True)
                 sc = absmean if self.w_bits == 1 else 2 * absmean
             weight = compiled.low_bit_weight_op(self.weight, sc, self.w_bits)
-        if 2 < self.a_bits < 32:
+        if 2 < self.a_bits < 32 and self.act_group_size is not None:
+            g = self.act_group_size
+            input_ = compiled.fake_quant(self._act_kind, input_.reshape(-1, g), _CLIP, self.a_bits, False, narrow=True).reshape(input_.shape)
+        elif 2 < self.a_bits < 32:
             input_ = compiled.fake_quant(self._act_kind, input_, _CLIP, self.a_bits, self.act_layerwise, narrow=True)
         out = nn.functional.linear(input_, weight)
         if self.bias is not None:
@@ -1334,7 +1449,10 @@ class QuantizeLinear(nn.Linear):
             else:
                 weight = self._low_bit_weight(self.weight)
             if 2 < self.a_bits < 32:
-                input_ = _shared_activation(self.act_quantizer, input_, self.a_bits, self.act_layerwise)
+                if self.act_group_size is not None:
+                    input_ = _GroupQuantizer.apply(input_, _CLIP, self.a_bits, self.act_group_size, self._act_kind, True, False)
+                else:
+                    input_ = _shared_activation(self.act_quantizer, input_, self.a_bits, self.act_layerwise)
         out = nn.functional.linear(input_, weight)
         if self.bias is not None:
             out += self.bias.view(1, -1).expand_as(out)
