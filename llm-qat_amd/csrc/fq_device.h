@@ -46,6 +46,23 @@ template <bool NT> __device__ __forceinline__ void st16(uint4* p, uint4 v) {
         *p = v;
     }
 }
+// Store cache policy of an output stream (the NTS template flag of the row kernels; `false` / `true` are ST_PLAIN / ST_NT).
+// The sc1 flavours are 16-byte buffer stores with the policy in the instruction's cache-policy operand:
+//   sc1 writes through the XCD's L2 (the line is not left dirty there); nt keeps it.  A/B: tools/kbench.hip `policy`.
+enum : int { ST_PLAIN = 0, ST_NT = 1, ST_SC1 = 2, ST_SC0_SC1 = 3, ST_NT_SC1 = 4 };
+template <int POL> __device__ __forceinline__ void st16_at(uint4* base /* wave-uniform */, int v, uint4 val) {
+    if constexpr (POL == ST_PLAIN || POL == ST_NT) {
+        st16<POL == ST_NT>(base + v, val);
+    } else {
+        constexpr int AUX = POL == ST_SC1 ? 16 : POL == ST_SC0_SC1 ? 17 : 18;   // gfx950 cache-policy bits: sc0 1, nt 2, sc1 16
+        const uint64_t b = (uint64_t)base;
+        const uint64_t bu = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b) |
+                            ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)bu, (short)0, 0x7FFFFFFF, 0x00020000);
+        const u32x4_t w = {val.x, val.y, val.z, val.w};
+        __builtin_amdgcn_raw_buffer_store_b128(w, rs, v * 16, 0, AUX);
+    }
+}
 
 // ------------------------------------------------------------------------------------
 // dtype traits.  A "dword" is the 32-bit register unit: 1 fp32 element or 2 16-bit ones.

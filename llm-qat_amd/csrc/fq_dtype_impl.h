@@ -12,13 +12,14 @@ namespace fq {
 //   4096 -> 512 vectors -> 256 x 2     5120 -> 640 -> 256 x 3     11008 -> 1376 -> 512 x 3     13824 -> 1728 -> 512 x 4
 //   tiny-LLaMA (fp32, 4 per vector): 256 -> 64 x 1, 688 -> 64 x 3.      Every other width is served by the nearest shape that holds it.
 // Round 4 pruned the instantiations nothing selects often enough to deserve its own code (27 MB / 100 s of build in round 3): stores
-// are always non-temporal (two cache-policy flavours instead of three), 5 / 7 vectors per thread share the 6 / 8 kernels.
+// are always non-temporal (two cache-policy flavours instead of three; round 6: `nt sc1` on the streamed Sym forward and the two-slot
+// mask backward, below), 5 / 7 vectors per thread share the 6 / 8 kernels.
 // Launch shape of the register-resident kernel, from tools/kbench on MI355X: 2-3 vectors per
 // thread is the sweet spot (round 3 re-checked with block sizes that are not powers of two -- 704 x 2 for 11008 cols wastes 2 % of
 // the vector slots instead of 10 %, 576 x 3 for 13824, 320 x 2 for 5120 -- and with 256 x 6 for mid-sized tensors: within +-2 % of
 // the shapes below everywhere, profiles/r03_kbench_block_shapes.txt, r03_ab_mid_rows_256.txt) (11008 bf16 cols: 512 thr x 3 = 30.6 us, 256 x 6 = 31.1, 1024 x 2 = 32.2;
 // 4096 cols: 256 x 2 = 6.1 us, 128 x 4 = 6.3, 64 x 8 = 6.9, 512 x 1 = 7.7).
-template <int DT, bool ASYM, bool FAST, bool NTL, bool NTS, bool DBG, bool PITCH = false>
+template <int DT, bool ASYM, bool FAST, bool NTL, int NTS, bool DBG, bool PITCH = false>
 static void launch_reg(const RowArgs& a, int64_t nvec, hipStream_t st) {
 #define R(TPR, V)                                                                                                   \
     case V:                                                                                                         \
@@ -177,7 +178,9 @@ static int rowwise_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
         // kernels carry none of that code; it runs the same arithmetic with the default cache policy
         if (a.idx || a.scale) launch_reg<DT, ASYM, FAST, false, false, true>(a, nvec, st);
         else if (pitched) launch_reg<DT, ASYM, FAST, false, true, false, true>(a, nvec, st);   // rows that do not follow one another: their own instantiations
-        else if (ntl) launch_reg<DT, ASYM, FAST, true, true, false>(a, nvec, st);
+        // streamed Sym tensors (the pair forward): y stores nt sc1, 2.5 % faster than nt on the W4 + A8 [4096, 11008] pair
+        // (59.6 -> 58.1 us, tools/fwd_variants.hip, profiles/r06_ab_store_policy.txt); Asym keeps nt (not measured)
+        else if (ntl) launch_reg<DT, ASYM, FAST, true, ASYM ? ST_NT : ST_NT_SC1, false>(a, nvec, st);
         else launch_reg<DT, ASYM, FAST, false, true, false>(a, nvec, st);
     } else if (a.mask) {
         return fail(FQ_ERR_UNSUPPORTED, "STE-mask forward needs 16-byte aligned rows that fit the register kernels");
@@ -328,10 +331,12 @@ template <int DT> int launch_ste_mask(SteLaunch L, int64_t cols, float lo, float
 #undef S1
         return launch_result();
     }
-    if (L.n <= 2 && !pitched) {   // two tensors (a QuantizeLinear's weight + input): the slot pick looks at two slots instead of four
+    // two tensors (a QuantizeLinear's weight + input): the slot pick looks at two slots instead of four.  Streamed gx stores nt sc1:
+    // the W4 + A8 [4096, 11008] forward + backward pair 2.0 % faster with both launches' stores nt sc1 (profiles/r06_ab_store_policy.txt)
+    if (L.n <= 2 && !pitched) {
 #define S2(V)                                                                                                                  \
     case V:                                                                                                                    \
-        if (ntl) FQ_LAUNCH2((ste_mask_kernel<DT, V, true, true, false, 2>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);   \
+        if (ntl) FQ_LAUNCH2((ste_mask_kernel<DT, V, true, ST_NT_SC1, false, 2>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);   \
         else FQ_LAUNCH2((ste_mask_kernel<DT, V, false, true, false, 2>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);      \
         break;
         switch (vpt) { S2(1) S2(2) S2(3) S2(4) S2(5) S2(6) S2(7) S2(8) }

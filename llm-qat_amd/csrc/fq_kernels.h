@@ -174,7 +174,7 @@ template <int DT> __device__ __forceinline__ uint4 ste_mask_apply(const uint4& g
 //   Out-of-range slots re-load the row's last vector (idempotent for max/min), so no load
 //   sits behind a branch; only stores are predicated.
 // ------------------------------------------------------------------------------------
-template <int DT, int TPR, int VPT, bool ASYM, bool FAST, bool NTL = true, bool NTS = true, bool DBG = false, int AC = 0, bool PITCH = false>
+template <int DT, int TPR, int VPT, bool ASYM, bool FAST, bool NTL = true, int NTS = ST_NT, bool DBG = false, int AC = 0, bool PITCH = false>
 __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs a) {
     using T = Ty<DT>;
     static_assert(AC == 0 || (AC == 1 && !ASYM && !DBG && T::ESIZE == 2), "autocast arithmetic: Sym on 16-bit tensors");
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs 
                 for (int k = 0; k < T::EPD; ++k) fd[k] = f[d * T::EPD + k];
                 o[d] = T::pack(fd);
             }
-            if (v < nvec) st16<NTS>(&yr[v], make_uint4(o[0], o[1], o[2], o[3]));
+            if (v < nvec) st16_at<NTS>(yr, v, make_uint4(o[0], o[1], o[2], o[3]));
             continue;
         }
         uint32_t o[4];
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs 
             } else o[d] = asym_chain<DT, FAST && DT == BF16>(fd, ar, a.asym, ip);
         }
         if (v < nvec) {
-            st16<NTS>(&yr[v], make_uint4(o[0], o[1], o[2], o[3]));
+            st16_at<NTS>(yr, v, make_uint4(o[0], o[1], o[2], o[3]));
             if constexpr (DBG) {
                 if (idxr) {
 #pragma unroll
@@ -1175,7 +1175,7 @@ template <bool PITCH = false, int NS = 4> __device__ __forceinline__ SteSlot ste
 
 // one chunk (cv vectors from vector vs) of one row.  `bounds` non-null: the row's {upper, lower} bounds are read HERE, after
 // the gradient and mask loads have been issued, so that nothing waits on them (null: the caller knows the row can clip).
-template <int DT, int VPT, bool NTL, bool NTS, bool PITCH = false>
+template <int DT, int VPT, bool NTL, int NTS, bool PITCH = false>
 __device__ __forceinline__ void ste_mask_chunk(const void* g, void* gx, const uint8_t* mrow, int mrow_dwords, int64_t row, int64_t nvec_row,
                                                int64_t vs, int cv, const float* bounds, float lo, float hi, int t, const RowPitch& gp,
                                                const RowPitch& op) {
@@ -1202,7 +1202,7 @@ __device__ __forceinline__ void ste_mask_chunk(const void* g, void* gx, const ui
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
             const int v = t + i * STE_THREADS;
-            if (v < nvec) st16<NTS>(&or_[v], rg[i]);
+            if (v < nvec) st16_at<NTS>(or_, v, rg[i]);
         }
     } else {
         uint32_t mb[VPT];
@@ -1211,7 +1211,7 @@ __device__ __forceinline__ void ste_mask_chunk(const void* g, void* gx, const ui
         for (int i = 0; i < VPT; ++i) {
             const int v = t + i * STE_THREADS;
             const uint4 o = ste_mask_apply<DT>(rg[i], mb[i]);
-            if (v < nvec) st16<NTS>(&or_[v], o);
+            if (v < nvec) st16_at<NTS>(or_, v, o);
         }
     }
 }
@@ -1229,7 +1229,7 @@ __global__ __launch_bounds__(STE_THREADS) void ste_mask_one_kernel(const void* g
                                              bounds, lo, hi, (int)threadIdx.x, RowPitch{}, RowPitch{});
 }
 
-template <int DT, int VPT, bool NTL = true, bool NTS = true, bool PITCH = false, int NS = 4>
+template <int DT, int VPT, bool NTL = true, int NTS = ST_NT, bool PITCH = false, int NS = 4>
 __global__ __launch_bounds__(STE_THREADS) void ste_mask_kernel(SteLaunch L, int64_t nvec_row, int cv, int64_t mask_row_words, float lo, float hi) {
     __shared__ uint64_t unsafe_rows[STE_THREADS / 64];
     const int t = threadIdx.x;

@@ -7,7 +7,9 @@
 // rounds.  Every variant's output is compared with variant 0's bit for bit before it is timed.
 //
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -I llm-qat_amd/csrc -o tools/fwd_variants tools/fwd_variants.hip
-//   ./tools/fwd_variants [rows cols rounds]        (default 4096 11008 5: the W4 + A8 pair launch of the metric step)
+//   ./tools/fwd_variants [rows cols rounds [old|new]]   (default 4096 11008 5: the W4 + A8 pair launch of the metric step)
+//   Round 6 added store policies on y (and on the backward's gx, timed as forward + backward steps), s_setprio around the
+//   reduce / store phase, and W / A rows interleaved in blockIdx order.  `old`: the round 3-4 variants only; `new`: round 6's only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -121,7 +123,7 @@ __device__ __forceinline__ void compute_row(const RowArgs& a, const Sel& s, cons
         out.o[i] = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
-template <int TPR, int VPT> __device__ __forceinline__ void store_row(const RowArgs& a, const Sel& s, int t, int nvec, const RowOut<VPT>& out) {
+template <int TPR, int VPT, int POL = ST_NT> __device__ __forceinline__ void store_row(const RowArgs& a, const Sel& s, int t, int nvec, const RowOut<VPT>& out) {
     uint8_t* mrow = (uint8_t*)(s.msk + s.row * a.mask_row_words);
     uint4* __restrict__ yr = (uint4*)((char*)s.yb + s.row * a.cols * 2);
 #pragma unroll
@@ -129,7 +131,7 @@ template <int TPR, int VPT> __device__ __forceinline__ void store_row(const RowA
         const int v = t + i * TPR;
         if (v < nvec) {
             if (out.want_mask) mrow[v] = (uint8_t)out.mbyte[i];
-            st16<true>(&yr[v], out.o[i]);
+            st16_at<POL>(yr, v, out.o[i]);
         }
     }
 }
@@ -252,6 +254,40 @@ __global__ __launch_bounds__(TPR) void fwd_variant_kernel(RowArgs a, int rows_pe
     }
 }
 
+// MODE 4 (round 6): one row per workgroup in registers, as the product kernel, with
+//   PRIO: s_setprio 3 once the row's loads are issued, back to 0 once its stores are issued (the reduce / store phase of a
+//         workgroup wins issue slots over the waves that are still loading, so its stores drain and the slot frees sooner);
+//   ILV:  W and A rows interleaved in blockIdx order (block b: tensor b & 1, row b >> 1; both tensors have the same rows here), so
+//         the A rows, which carry the mask work, are spread over every round of workgroups instead of making up the last half.
+template <int TPR, int VPT, int POL, bool PRIO, bool ILV>
+__global__ __launch_bounds__(TPR) void fwd_one_kernel(RowArgs a) {
+    constexpr int NW = TPR / 64;
+    __shared__ uint32_t red[NW];
+    const int t = threadIdx.x;
+    const int nvec = (int)(a.cols / 8);
+    const int64_t b = blockIdx.x;
+    const Sel s = select_tensor(a, ILV ? ((b & 1) ? a.rows0 + (b >> 1) : (b >> 1)) : b);
+    const uint4* xr = (const uint4*)((const char*)s.xb + s.row * a.cols * 2);
+    uint4 r[VPT];
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        int v = t + i * TPR;
+        v = v < nvec ? v : nvec - 1;
+        r[i] = ld16<true>(&xr[v]);
+    }
+    if constexpr (PRIO) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(3);
+    }
+    RowOut<VPT> out;
+    compute_row<TPR, VPT>(a, s, r, t, nvec, red, out);
+    store_row<TPR, VPT, POL>(a, s, t, nvec, out);
+    if constexpr (PRIO) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(0);
+    }
+}
+
 __global__ void fill_bf16(uint16_t* p, int64_t n, uint32_t seed, float scale, int outliers) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         uint32_t h = (uint32_t)i * 2654435761u + seed;
@@ -263,7 +299,7 @@ __global__ void fill_bf16(uint16_t* p, int64_t n, uint32_t seed, float scale, in
 }
 
 struct Set {
-    void *w, *a, *yw, *ya, *mw, *ma;
+    void *w, *a, *yw, *ya, *mw, *ma, *gw, *ga, *gxw, *gxa;
     float *bw, *ba;
 };
 
@@ -285,9 +321,12 @@ int main(int argc, char** argv) {
         CK(hipMalloc(&q.mw, mbytes)); CK(hipMalloc(&q.ma, mbytes)); CK(hipMalloc((void**)&q.bw, rows * 8)); CK(hipMalloc((void**)&q.ba, rows * 8));
         hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, (uint16_t*)q.w, n, 17u + s, 0.02f, 0);
         hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, (uint16_t*)q.a, n, 99u + s, 1.0f, 1);
+        CK(hipMalloc(&q.gw, bytes)); CK(hipMalloc(&q.ga, bytes)); CK(hipMalloc(&q.gxw, bytes)); CK(hipMalloc(&q.gxa, bytes));
+        hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, (uint16_t*)q.gw, n, 55u + s, 0.001f, 0);
+        hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, (uint16_t*)q.ga, n, 77u + s, 0.001f, 0);
     }
-    void *cy_w, *cy_a, *cm_a;   // variant 0's outputs of set 0, for the bit-for-bit check
-    CK(hipMalloc(&cy_w, bytes)); CK(hipMalloc(&cy_a, bytes)); CK(hipMalloc(&cm_a, mbytes));
+    void *cy_w, *cy_a, *cm_a, *cgx_a;   // variant 0's outputs of set 0, for the bit-for-bit check
+    CK(hipMalloc(&cy_w, bytes)); CK(hipMalloc(&cy_a, bytes)); CK(hipMalloc(&cm_a, mbytes)); CK(hipMalloc(&cgx_a, bytes));
     CK(hipDeviceSynchronize());
 
     auto args = [&](const Set& q) {
@@ -300,8 +339,12 @@ int main(int argc, char** argv) {
         for (int i = 1; i < MAX_MORE; ++i) { a.more[i] = TensorSlot{}; a.more[i].row_begin = INT64_MAX; }
         return a;
     };
-    struct Var { const char* name; int mode, rpw; };
-    const Var vars[] = {{"0 product row_reg_kernel<512,3> (one row / WG)", 0, 1},
+    // mode 5 (round 6): the product kernel with another store policy on y (rpw = the policy); mode 4: fwd_one_kernel (rpw = flags:
+    // 1 PRIO, 2 ILV, 4 sc1 stores); bwd = the backward's store policy on gx in the step rows (-1: forward alone)
+    struct Var { const char* name; int mode, rpw, bwd = -1; };
+    const bool old_only = argc > 4 && !strcmp(argv[4], "old");   // the round 3-4 variants (LDS-DMA, pipelined rows)
+    const bool step_only = argc > 4 && !strcmp(argv[4], "new");
+    std::vector<Var> vv = {{"0 product row_reg_kernel<512,3> (one row / WG)", 0, 1},
                         {"1 LDS-DMA row load, one row / WG", 1, 1},
                         {"2 pipelined rows, registers, 2 rows / WG", 2, 2},
                         {"2 pipelined rows, registers, 4 rows / WG", 2, 4},
@@ -309,30 +352,98 @@ int main(int argc, char** argv) {
                         {"3 LDS-DMA + pipelined, 2 rows / WG", 3, 2},
                         {"3 LDS-DMA + pipelined, 4 rows / WG", 3, 4},
                         {"3 LDS-DMA + pipelined, 8 rows / WG", 3, 8}};
-    const int NV = sizeof(vars) / sizeof(vars[0]);
+    if (step_only) vv.resize(1);
+    if (!old_only) {
+        const Var more[] = {{"5 product kernel, y stores plain", 5, ST_PLAIN},
+                            {"5 product kernel, y stores sc1", 5, ST_SC1},
+                            {"5 product kernel, y stores sc0 sc1", 5, ST_SC0_SC1},
+                            {"5 product kernel, y stores nt sc1", 5, ST_NT_SC1},
+                            {"4 one row / WG, nt (harness twin of 0)", 4, 0},
+                            {"4b s_setprio 3 after loads, 0 after stores", 4, 1},
+                            {"4c W / A rows interleaved", 4, 2},
+                            {"4bc setprio + interleaved", 4, 3},
+                            {"4c interleaved, sc1", 4, 6},
+                            {"step: fwd nt + bwd nt (product)", 0, 1, ST_NT},
+                            {"step: fwd sc1 + bwd nt", 5, ST_SC1, ST_NT},
+                            {"step: fwd nt + bwd sc1", 0, 1, ST_SC1},
+                            {"step: fwd sc1 + bwd sc1", 5, ST_SC1, ST_SC1},
+                            {"step: fwd nt sc1 + bwd nt sc1", 5, ST_NT_SC1, ST_NT_SC1},
+                            {"step: fwd plain + bwd plain", 5, ST_PLAIN, ST_PLAIN},
+                            {"step: fwd interleaved nt + bwd nt", 4, 2, ST_NT}};
+        for (const Var& m : more) vv.push_back(m);
+    }
+    const Var* vars = vv.data();
+    const int NV = (int)vv.size();
     auto launch = [&](const Var& v, const Set& q) {
         RowArgs a = args(q);
         const int64_t total = 2 * rows;
         if (v.mode == 0) hipLaunchKernelGGL((row_reg_kernel<BF16, TPR, VPT, false, true, true, true>), dim3((unsigned)total), dim3(TPR), 0, 0, a);
-        else {
+        else if (v.mode == 5) {
+            const dim3 g((unsigned)total), bl(TPR);
+            switch (v.rpw) {
+                case ST_PLAIN: hipLaunchKernelGGL((row_reg_kernel<BF16, TPR, VPT, false, true, true, ST_PLAIN>), g, bl, 0, 0, a); break;
+                case ST_SC1: hipLaunchKernelGGL((row_reg_kernel<BF16, TPR, VPT, false, true, true, ST_SC1>), g, bl, 0, 0, a); break;
+                case ST_SC0_SC1: hipLaunchKernelGGL((row_reg_kernel<BF16, TPR, VPT, false, true, true, ST_SC0_SC1>), g, bl, 0, 0, a); break;
+                default: hipLaunchKernelGGL((row_reg_kernel<BF16, TPR, VPT, false, true, true, ST_NT_SC1>), g, bl, 0, 0, a); break;
+            }
+        } else if (v.mode == 4) {
+            const dim3 g((unsigned)total), bl(TPR);
+            switch (v.rpw) {
+                case 0: hipLaunchKernelGGL((fwd_one_kernel<TPR, VPT, ST_NT, false, false>), g, bl, 0, 0, a); break;
+                case 1: hipLaunchKernelGGL((fwd_one_kernel<TPR, VPT, ST_NT, true, false>), g, bl, 0, 0, a); break;
+                case 2: hipLaunchKernelGGL((fwd_one_kernel<TPR, VPT, ST_NT, false, true>), g, bl, 0, 0, a); break;
+                case 3: hipLaunchKernelGGL((fwd_one_kernel<TPR, VPT, ST_NT, true, true>), g, bl, 0, 0, a); break;
+                default: hipLaunchKernelGGL((fwd_one_kernel<TPR, VPT, ST_SC1, false, true>), g, bl, 0, 0, a); break;
+            }
+        } else {
             const unsigned grid = (unsigned)((total + v.rpw - 1) / v.rpw);
             if (v.mode == 1) hipLaunchKernelGGL((fwd_variant_kernel<TPR, VPT, 1>), dim3((unsigned)total), dim3(TPR), 0, 0, a, 1);
             else if (v.mode == 2) hipLaunchKernelGGL((fwd_variant_kernel<TPR, VPT, 2>), dim3(grid), dim3(TPR), 0, 0, a, v.rpw);
             else hipLaunchKernelGGL((fwd_variant_kernel<TPR, VPT, 3>), dim3(grid), dim3(TPR), 0, 0, a, v.rpw);
         }
     };
+    // the pair backward as the product launches it for this shape (fq_dtype_impl.h launch_ste_mask, two copying slots: VPT 6, one chunk)
+    const int64_t bchunks = (nvec + STE_THREADS * 8 - 1) / (STE_THREADS * 8);
+    const int bcv = (int)((nvec + bchunks - 1) / bchunks + 63) / 64 * 64;
+    if ((bcv + STE_THREADS - 1) / STE_THREADS != 6) {
+        fprintf(stderr, "the step rows are built for the backward's 6 vectors per thread\n");
+        return 2;
+    }
+    auto bwd = [&](int pol, const Set& q) {
+        SteLaunch L{};
+        L.n = 2;
+        L.t[0] = SteSlot{q.gw, q.gxw, q.bw, (const uint64_t*)q.mw, rows, 0, 0, {}, {}};
+        L.t[1] = SteSlot{q.ga, q.gxa, q.ba, (const uint64_t*)q.ma, rows, rows, 0, {}, {}};
+        for (int i = 2; i < 1 + MAX_MORE; ++i) { L.t[i] = SteSlot{}; L.t[i].blk_begin = INT64_MAX; }
+        const dim3 g((unsigned)(2 * rows), (unsigned)bchunks), bl(STE_THREADS);
+        const float lo = -2.0f, hi = 2.0f;
+        switch (pol) {
+            case ST_NT: hipLaunchKernelGGL((ste_mask_kernel<BF16, 6, true, ST_NT, false, 2>), g, bl, 0, 0, L, nvec, bcv, (int64_t)mrw, lo, hi); break;
+            case ST_PLAIN: hipLaunchKernelGGL((ste_mask_kernel<BF16, 6, true, ST_PLAIN, false, 2>), g, bl, 0, 0, L, nvec, bcv, (int64_t)mrw, lo, hi); break;
+            case ST_SC1: hipLaunchKernelGGL((ste_mask_kernel<BF16, 6, true, ST_SC1, false, 2>), g, bl, 0, 0, L, nvec, bcv, (int64_t)mrw, lo, hi); break;
+            case ST_SC0_SC1: hipLaunchKernelGGL((ste_mask_kernel<BF16, 6, true, ST_SC0_SC1, false, 2>), g, bl, 0, 0, L, nvec, bcv, (int64_t)mrw, lo, hi); break;
+            default: hipLaunchKernelGGL((ste_mask_kernel<BF16, 6, true, ST_NT_SC1, false, 2>), g, bl, 0, 0, L, nvec, bcv, (int64_t)mrw, lo, hi); break;
+        }
+    };
+    auto run = [&](const Var& v, const Set& q) {
+        launch(v, q);
+        if (v.bwd >= 0) bwd(v.bwd, q);
+    };
     // ---- correctness: every variant == variant 0 on set 0 (values of both tensors, the A8 tensor's mask)
     launch(vars[0], sets[0]);
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(cy_w, sets[0].yw, bytes, hipMemcpyDeviceToDevice)); CK(hipMemcpy(cy_a, sets[0].ya, bytes, hipMemcpyDeviceToDevice));
     CK(hipMemcpy(cm_a, sets[0].ma, mbytes, hipMemcpyDeviceToDevice));
+    bwd(ST_NT, sets[0]);
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(cgx_a, sets[0].gxa, bytes, hipMemcpyDeviceToDevice));
     std::vector<char> h0(bytes), h1(bytes), m0(mbytes), m1(mbytes);
     std::vector<float> b0(rows * 2), b1(rows * 2);
     CK(hipMemcpy(b0.data(), sets[0].ba, rows * 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(m0.data(), cm_a, mbytes, hipMemcpyDeviceToHost));
     for (int vi = 1; vi < NV; ++vi) {
-        CK(hipMemset(sets[0].yw, 0, bytes)); CK(hipMemset(sets[0].ya, 0, bytes));
-        launch(vars[vi], sets[0]);
+        CK(hipMemset(sets[0].yw, 0, bytes)); CK(hipMemset(sets[0].ya, 0, bytes)); CK(hipMemset(sets[0].gxa, 0, bytes));
+        run(vars[vi], sets[0]);
         CK(hipDeviceSynchronize());
         CK(hipGetLastError());
         bool ok = true;
@@ -345,6 +456,10 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(m1.data(), sets[0].ma, mbytes, hipMemcpyDeviceToHost));
         for (int64_t r = 0; r < rows && ok; ++r)   // the mask is defined only for rows whose bounds reach the clip
             if (b0[2 * r] >= 2.0f && memcmp(m0.data() + r * mrw * 8, m1.data() + r * mrw * 8, (cols + 7) / 8)) ok = false;
+        if (ok && vars[vi].bwd >= 0) {   // the A8 tensor's input gradient (the one with masked rows)
+            CK(hipMemcpy(h0.data(), cgx_a, bytes, hipMemcpyDeviceToHost)); CK(hipMemcpy(h1.data(), sets[0].gxa, bytes, hipMemcpyDeviceToHost));
+            ok = !memcmp(h0.data(), h1.data(), bytes);
+        }
         printf("variant %-52s %s\n", vars[vi].name, ok ? "bit-identical to the product kernel" : "MISMATCH");
         if (!ok) return 1;
     }
@@ -354,10 +469,10 @@ int main(int argc, char** argv) {
     std::vector<std::vector<float>> us(NV);
     for (int r = 0; r < rounds; ++r)
         for (int vi = 0; vi < NV; ++vi) {
-            for (int i = 0; i < 20; ++i) launch(vars[vi], sets[i % NS]);
+            for (int i = 0; i < 20; ++i) run(vars[vi], sets[i % NS]);
             CK(hipDeviceSynchronize());
             CK(hipEventRecord(e0, 0));
-            for (int i = 0; i < IT; ++i) launch(vars[vi], sets[i % NS]);
+            for (int i = 0; i < IT; ++i) run(vars[vi], sets[i % NS]);
             CK(hipEventRecord(e1, 0));
             CK(hipEventSynchronize(e1));
             float ms;
@@ -366,9 +481,17 @@ int main(int argc, char** argv) {
         }
     const double alg = 2.0 * 2.0 * bytes;   // read x + write y of both tensors
     printf("pair forward W4 + A8 on [%lld, %lld] bf16 x 2 (%.1f MB algorithmic), %d rounds x %d launches, median us:\n", (long long)rows, (long long)cols, alg / 1e6, rounds, IT);
+    int step0 = -1;   // the product step row, the reference of the other step rows
+    for (int vi = 0; vi < NV; ++vi)
+        if (step0 < 0 && vars[vi].bwd == ST_NT && vars[vi].mode == 0) step0 = vi;
+    for (int vi = 0; vi < NV; ++vi) std::sort(us[vi].begin(), us[vi].end());
     for (int vi = 0; vi < NV; ++vi) {
-        std::sort(us[vi].begin(), us[vi].end());
         const float med = us[vi][us[vi].size() / 2];
+        if (vars[vi].bwd >= 0) {   // a step (forward + backward): 2x the bytes, compared with the product step
+            printf("  %-52s %7.2f us  %6.0f GB/s             (min %.2f max %.2f)  vs product step %.3f\n", vars[vi].name, med, 2 * alg / (med * 1e-6) / 1e9,
+                   us[vi].front(), us[vi].back(), med / us[step0][us[step0].size() / 2]);
+            continue;
+        }
         printf("  %-52s %7.2f us  %6.0f GB/s  frac %.3f   (min %.2f max %.2f)  vs product %.3f\n", vars[vi].name, med, alg / (med * 1e-6) / 1e9,
                alg / (med * 1e-6) / 1e9 / 8000.0, us[vi].front(), us[vi].back(), med / us[0][us[0].size() / 2]);
     }

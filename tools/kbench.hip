@@ -1,7 +1,7 @@
 // kbench.hip -- standalone tuning harness for the fake-quant kernels (not part of the product).
 //
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -I llm-qat_amd/csrc -o tools/kbench tools/kbench.hip
-//   ./tools/kbench [rows cols]
+//   ./tools/kbench [rows cols [mode]]     mode: ceilings | placement | policy | shapes | sweep
 //
 // Times kernel variants with HIP events on rotating buffer sets (defeats the 256 MiB Infinity
 // Cache) and prints achieved algorithmic GB/s.  Used to pick launch shapes; the winners are
@@ -9,7 +9,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
@@ -215,6 +217,53 @@ __global__ __launch_bounds__(256) void write8_kernel(uint2* __restrict__ out, in
     for (int i = 0; i < 4; ++i) {
         const int64_t v = v0 + (int64_t)i * 256;
         if (v < n8) out[v] = make_uint2((uint32_t)v, 7);
+    }
+}
+
+// ---------------------------------------------------------------- store cache-policy matrix (mode `policy`)
+// The same 16-byte stores under each policy of fq_device.h st16_at: ST_PLAIN, ST_NT, ST_SC1, ST_SC0_SC1, ST_NT_SC1 (loads nt).
+template <int UNR, int POL>
+__global__ __launch_bounds__(256) void copy_pol_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, int64_t nvec) {
+    const int64_t b0 = (int64_t)blockIdx.x * (256 * UNR);
+    uint4 r[UNR];
+#pragma unroll
+    for (int i = 0; i < UNR; ++i) {
+        int64_t v = b0 + threadIdx.x + (int64_t)i * 256;
+        v = v < nvec ? v : nvec - 1;
+        r[i] = ld_nt(&in[v]);
+    }
+#pragma unroll
+    for (int i = 0; i < UNR; ++i) {
+        const int j = threadIdx.x + i * 256;
+        if (b0 + j < nvec) st16_at<POL>(out + b0, j, r[i]);
+    }
+}
+// the forward's row structure 1:1 (row_reg_kernel<.., 512, 3>, rowshrink-style, no arithmetic): one row per workgroup held in
+// registers, a block max through LDS (one barrier), then the row's 16-byte stores
+template <int TPR, int VPT, int POL>
+__global__ __launch_bounds__(TPR) void rowcopy_pol_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, int nvec_row) {
+    __shared__ uint32_t red[TPR / 64];
+    const int t = threadIdx.x;
+    const uint4* xr = in + (int64_t)blockIdx.x * nvec_row;
+    uint4 r[VPT];
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        int v = t + i * TPR;
+        v = v < nvec_row ? v : nvec_row - 1;
+        r[i] = ld_nt(&xr[v]);
+    }
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const uint32_t m = (r[i].x | r[i].y | r[i].z | r[i].w) & 0x7FFF7FFFu;
+        acc = acc > m ? acc : m;
+    }
+    const uint32_t m = block_reduce<OpMaxU, TPR / 64>(acc, red);
+    uint4* yr = out + (int64_t)blockIdx.x * nvec_row;
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const int v = t + i * TPR;
+        if (v < nvec_row) st16_at<POL>(yr, v, make_uint4(r[i].x ^ m, r[i].y, r[i].z, r[i].w));
     }
 }
 
@@ -433,6 +482,77 @@ int main(int argc, char** argv) {
         report("copy<UNR=1,NT=true> separate allocations, set 0 only", 2.0 * bytes, time_it([&](int i) {
                    hipLaunchKernelGGL((copy_kernel<1, true>), dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, 0, (const uint4*)b.x[0], (uint4*)b.y[0], nvec);
                }, IT));
+        return 0;
+    }
+    if (argc > 3 && std::string(argv[3]) == "policy") {
+        // each producer (cold-buffer copy; the forward's row structure) alone, and followed on the same stream by a consumer that
+        // reads what it wrote (copy<UNR=1,NT> y -> gx): the consumer's extra time over its own cold run is the boundary's price of
+        // the producer's store policy.  Rounds interleave the policies; median of rounds.
+        const char* pn[5] = {"plain", "nt", "sc1", "sc0 sc1", "nt sc1"};
+        const int64_t nvr = cols / 8;
+        const bool rowshape = cols % 8 == 0 && nvr <= 512 * 3 && nvr > 512 * 2;
+        auto consumer = [&](int s) {
+            hipLaunchKernelGGL((copy_kernel<1, true>), dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, 0, (const uint4*)b.y[s], (uint4*)b.gx[s], nvec);
+        };
+        auto copy_p = [&](int pol, int s) {
+            const dim3 g((unsigned)((nvec + 255) / 256));
+            const uint4* in = (const uint4*)b.x[s];
+            uint4* out = (uint4*)b.y[s];
+            switch (pol) {
+                case 0: hipLaunchKernelGGL((copy_pol_kernel<1, ST_PLAIN>), g, dim3(256), 0, 0, in, out, nvec); break;
+                case 1: hipLaunchKernelGGL((copy_pol_kernel<1, ST_NT>), g, dim3(256), 0, 0, in, out, nvec); break;
+                case 2: hipLaunchKernelGGL((copy_pol_kernel<1, ST_SC1>), g, dim3(256), 0, 0, in, out, nvec); break;
+                case 3: hipLaunchKernelGGL((copy_pol_kernel<1, ST_SC0_SC1>), g, dim3(256), 0, 0, in, out, nvec); break;
+                default: hipLaunchKernelGGL((copy_pol_kernel<1, ST_NT_SC1>), g, dim3(256), 0, 0, in, out, nvec); break;
+            }
+        };
+        auto row_p = [&](int pol, int s) {
+            const dim3 g((unsigned)rows);
+            const uint4* in = (const uint4*)b.x[s];
+            uint4* out = (uint4*)b.y[s];
+            switch (pol) {
+                case 0: hipLaunchKernelGGL((rowcopy_pol_kernel<512, 3, ST_PLAIN>), g, dim3(512), 0, 0, in, out, (int)nvr); break;
+                case 1: hipLaunchKernelGGL((rowcopy_pol_kernel<512, 3, ST_NT>), g, dim3(512), 0, 0, in, out, (int)nvr); break;
+                case 2: hipLaunchKernelGGL((rowcopy_pol_kernel<512, 3, ST_SC1>), g, dim3(512), 0, 0, in, out, (int)nvr); break;
+                case 3: hipLaunchKernelGGL((rowcopy_pol_kernel<512, 3, ST_SC0_SC1>), g, dim3(512), 0, 0, in, out, (int)nvr); break;
+                default: hipLaunchKernelGGL((rowcopy_pol_kernel<512, 3, ST_NT_SC1>), g, dim3(512), 0, 0, in, out, (int)nvr); break;
+            }
+        };
+        // correctness: every policy writes the same bytes as plain
+        {
+            std::vector<char> h0(bytes), h1(bytes);
+            for (int kind = 0; kind < (rowshape ? 2 : 1); ++kind)
+                for (int pol = 0; pol < 5; ++pol) {
+                    CK(hipMemset(b.y[0], 0, bytes));
+                    if (kind) row_p(pol, 0); else copy_p(pol, 0);
+                    CK(hipDeviceSynchronize());
+                    CK(hipMemcpy(pol ? h1.data() : h0.data(), b.y[0], bytes, hipMemcpyDeviceToHost));
+                    if (pol && memcmp(h0.data(), h1.data(), bytes)) { printf("policy %s (%s): MISMATCH\n", pn[pol], kind ? "row" : "copy"); return 1; }
+                }
+            printf("all store policies write identical bytes\n");
+        }
+        const int R = 7;
+        std::vector<float> t_cons, t_alone[2][5], t_pair[2][5];
+        for (int r = 0; r < R; ++r) {
+            t_cons.push_back(time_it([&](int i) { consumer(i % NS); }, IT));
+            for (int kind = 0; kind < (rowshape ? 2 : 1); ++kind)
+                for (int pol = 0; pol < 5; ++pol) {
+                    auto prod = [&](int s) { if (kind) row_p(pol, s); else copy_p(pol, s); };
+                    t_alone[kind][pol].push_back(time_it([&](int i) { prod(i % NS); }, IT));
+                    t_pair[kind][pol].push_back(time_it([&](int i) { prod(i % NS); consumer(i % NS); }, IT));
+                }
+        }
+        auto med = [](std::vector<float> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
+        const float c = med(t_cons);
+        printf("store-policy matrix, %lld x %lld bf16, %d rounds x %d launches, median; consumer copy<UNR=1,NT> alone %.2f us\n", (long long)rows,
+               (long long)cols, R, IT, c * 1e3);
+        printf("%-34s %-8s %9s %9s %9s %11s\n", "producer", "policy", "alone us", "GB/s", "pair us", "pair-alone-cons");
+        for (int kind = 0; kind < (rowshape ? 2 : 1); ++kind)
+            for (int pol = 0; pol < 5; ++pol) {
+                const float a = med(t_alone[kind][pol]), p = med(t_pair[kind][pol]);
+                printf("%-34s %-8s %9.2f %9.1f %9.2f %11.2f\n", kind ? "row 512 x 3 (forward structure)" : "copy<UNR=1> (cold buffers)", pn[pol], a * 1e3,
+                       2.0 * bytes / (a * 1e-3) / 1e9, p * 1e3, (p - a - c) * 1e3);
+            }
         return 0;
     }
     if (argc > 3 && std::string(argv[3]) == "ceilings") {
