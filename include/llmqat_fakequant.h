@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FQ_ABI_VERSION 6 /* 6: + fq_group_fwd (group-wise scales);  5: + the *_v entry points: rows that do not follow one another in memory (fq_rows_view);  2: + multi-tensor launches, export, row scales, fq_w12_fwd_rows; 3: the STE mask is a plain row bitmap;
+#define FQ_ABI_VERSION 7 /* 7: + fq_mx_fwd / fq_mx_export (OCP MX block scales);  6: + fq_group_fwd (group-wise scales);  5: + the *_v entry points: rows that do not follow one another in memory (fq_rows_view);  2: + multi-tensor launches, export, row scales, fq_w12_fwd_rows; 3: the STE mask is a plain row bitmap;
                             4: fq_sym_fwd_autocast takes `sem` (and the autocast modes of pair / multi / export / row_scales honour it),
                                launch status from hipLaunchKernel's return value (the hipGetLastError slot is left alone), fq_qlinear_fwd (an experiment with test hooks in its signature) left the library, fq_w12_fwd_rows sums
                                in ATen's own order (no `sem`) */
@@ -366,6 +366,38 @@ int fq_sym_row_scales(const void* x, float* scales_out, int64_t rows, int64_t co
 int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t cols, int64_t group, int bits, int dtype, int sem,
                  int autocast /* 0 or 1 */, float lo, float hi, float* row_bounds_out, void* mask_out, size_t mask_bytes,
                  void* stream);
+
+/*
+ * ---- OCP Microscaling (MX) block scales (ABI 7) ---------------------------------------------------------------------------------------
+ * The operand format of gfx950's block-scaled MFMA (v_mfma_scale_f32_*_f8f6f4): every 32 consecutive elements of the last dimension
+ * share one E8M0 power-of-two scale X = 2^E, and each element is a narrow float.  Per block, in fp32:
+ *   amax = max|v|.  A NaN or +-Inf in the block makes all 32 outputs NaN (export: scale byte 0xFF, codes 0).
+ *   E = floor(log2 amax) - emax_elem, from the bits of amax (subnormal amax included), clamped to [-127, 127]; amax == 0: E = -127.
+ *   q = v / X rounded to nearest-even onto the element grid (normals and subnormals), saturated to +-max-normal, sign kept (-0.2 -> -0);
+ *   y = q * X (exact in fp32), rounded once to the tensor dtype.
+ *       fmt                  element   emax_elem  mantissa bits  max normal  smallest subnormal
+ *       FQ_MX_FP4_E2M1       E2M1      2          1              6           0.5
+ *       FQ_MX_FP6_E2M3       E2M3      2          3              7.5         0.125
+ *       FQ_MX_FP6_E3M2       E3M2      4          2              28          0.0625
+ *       FQ_MX_FP8_E4M3       E4M3 (fn) 8          3              448         2^-9
+ *       FQ_MX_FP8_E5M2       E5M2      15         2              57344       2^-16
+ *   x, y     [rows, cols] `dtype` (bf16 / fp16 / fp32), contiguous, 16-byte aligned; cols a multiple of 32; y may not alias x
+ * fq_mx_export writes the integer form instead of y (FP4 and FP8 formats; FP6 has no packing here: FQ_ERR_ARG):
+ *   elems_out   FP4: rows*cols/2 bytes, two codes per byte, element 2k in the low nibble of byte k (the int4 container's order);
+ *               FP8: rows*cols bytes, one OCP code per element (float8_e4m3fn / float8_e5m2 bit patterns)
+ *   scales_out  rows*cols/32 bytes, one E8M0 byte (E + 127) per block
+ *   both 16-byte aligned.
+ * Status: FQ_ERR_DTYPE (float64, unknown codes), FQ_ERR_ARG (unknown fmt, FP6 export, y == x), FQ_ERR_SHAPE (cols % 32, negative or
+ * overflowing shapes), FQ_ERR_NULL, FQ_ERR_UNSUPPORTED (pointers not 16-byte aligned, more blocks than one launch holds), all before any
+ * HIP call; 0 without a launch for an empty shape.
+ */
+#define FQ_MX_FP4_E2M1 0
+#define FQ_MX_FP6_E2M3 1
+#define FQ_MX_FP6_E3M2 2
+#define FQ_MX_FP8_E4M3 3
+#define FQ_MX_FP8_E5M2 4
+int fq_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, void* stream);
+int fq_mx_export(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # LLMQAT_AMD_LIB points the loader at another build of the library (A/B runs of kernel variants: tools/ab_bench.sh) -- the product
 # file is never overwritten; fq_build_info() / LIB_PATH say which one is loaded
 LIB_PATH = os.environ.get("LLMQAT_AMD_LIB") or os.path.join(HERE, "libllmqat_fakequant.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16, DTYPE_F64 = 0, 1, 2, 3
 SEM_CPU_EAGER, SEM_DEVICE_EAGER = 0, 1
@@ -25,6 +25,7 @@ EXPORTS = (
     "fq_export_bins_bytes", "fq_sym_export", "fq_asym_export", "fq_sym_row_scales", "fq_sym_fwd_multi", "fq_ste_bwd_mask_multi", "fq_w12_fwd_rows",
     "fq_rowwise_fwd_v", "fq_sym_fwd_multi_v", "fq_ste_bwd_mask_multi_v", "fq_ste_bwd_v",
     "fq_group_fwd",
+    "fq_mx_fwd", "fq_mx_export",
 )
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
@@ -51,6 +52,7 @@ class BwdTensorV(ctypes.Structure):  # fq_bwd_tensor_v
     _fields_ = BwdTensor._fields_ + [("gv", RowsView), ("gxv", RowsView)]
 
 
+MX_FP4_E2M1, MX_FP6_E2M3, MX_FP6_E3M2, MX_FP8_E4M3, MX_FP8_E5M2 = 0, 1, 2, 3, 4
 BINS_NONE, BINS_INT4, BINS_INT8, BINS_INT16 = 0, 1, 2, 3
 ERR_UNSUPPORTED = -8
 
@@ -127,6 +129,10 @@ def _bind(L):
     L.fq_ste_bwd_v.restype = i32
     L.fq_group_fwd.argtypes = [i32, vp, vp, i64, i64, i64, i32, i32, i32, i32, f32, f32, vp, vp, sz, vp]
     L.fq_group_fwd.restype = i32
+    L.fq_mx_fwd.argtypes = [vp, vp, i64, i64, i32, i32, vp]
+    L.fq_mx_fwd.restype = i32
+    L.fq_mx_export.argtypes = [vp, vp, vp, i64, i64, i32, i32, vp]
+    L.fq_mx_export.restype = i32
     return L
 
 

@@ -74,3 +74,18 @@ def fake_quant(kind, x, clip_val, num_bits, layerwise, narrow=False):
     if kind == "sym" and ops.autocast_active(x):
         mode = 1 if (narrow and ops.autocast_narrow_ok(x)) else 2
     return fake_quant_op(x, clip_val, _KINDS[kind], int(num_bits), bool(layerwise), mode)
+
+
+# MX block-scaled fake quantization (ops.mx_quantize): the straight-through identity gradient, nothing saved
+@torch.library.custom_op("llmqat_amd::mx_fake_quant", mutates_args=(), device_types="cuda")
+def mx_fake_quant_op(x: torch.Tensor, fmt: str) -> torch.Tensor:
+    return ops.mx_quantize(x, fmt)
+
+
+@mx_fake_quant_op.register_fake
+def _(x, fmt):
+    ops.check_mx(tuple(x.shape), fmt)
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+mx_fake_quant_op.register_autograd(lambda ctx, g: (g, None))

@@ -481,4 +481,50 @@ FQ_API int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t 
     }
 }
 
+namespace {
+// element formats of the MX entry points, indexed by FQ_MX_*: {emax, mbits, emin, max-normal, code of max-normal, sign bit of a code}
+const MxFmt kMxFmts[5] = {
+    {2, 1, 0, 6.0f, 0x7u, 0x8u},            // E2M1
+    {2, 3, 0, 7.5f, 0x1Fu, 0x20u},          // E2M3
+    {4, 2, -2, 28.0f, 0x1Fu, 0x20u},        // E3M2
+    {8, 3, -6, 448.0f, 0x7Eu, 0x80u},       // E4M3 (0x7F is its NaN)
+    {15, 2, -14, 57344.0f, 0x7Bu, 0x80u},   // E5M2
+};
+
+// exp = false: fq_mx_fwd (x -> y); true: fq_mx_export (x -> elems + scales).  Every check comes before any HIP call.
+int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
+    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
+    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
+    if (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
+    if (exp && (fmt == FQ_MX_FP6_E2M3 || fmt == FQ_MX_FP6_E3M2)) return fail(FQ_ERR_ARG, "FP6 formats have no export packing");
+    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
+    if (cols % 32 != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the 32-element MX block", (long long)cols);
+    if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
+    if (rows == 0 || cols == 0) return ok();
+    if (!x || (!exp && !y) || (exp && (!elems || !scales))) return fail(FQ_ERR_NULL, exp ? "x / elems / scales must not be NULL" : "x / y must not be NULL");
+    if (!exp && x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+    if (!aligned16(x) || (!exp && !aligned16(y)) || (exp && (!aligned16(elems) || !aligned16(scales))))
+        return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+    const int es = esize_of(dtype);
+    const int64_t nvec = rows * cols * es / 16;    // cols % 32 == 0: whole 16-byte vectors, whole blocks
+    if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
+    MxArgs a{x, y, (uint8_t*)elems, (uint8_t*)scales, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    const int kind = !exp ? MX_FWD : (fmt == FQ_MX_FP4_E2M1 ? MX_EXP4 : MX_EXP8);
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case FQ_DTYPE_F32: return launch_mx<F32>(kind, a, kMxFmts[fmt], st);
+        case FQ_DTYPE_F16: return launch_mx<F16>(kind, a, kMxFmts[fmt], st);
+        default: return launch_mx<BF16>(kind, a, kMxFmts[fmt], st);
+    }
+}
+}  // namespace
+
+FQ_API int fq_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
+    return mx_entry(false, x, y, nullptr, nullptr, rows, cols, fmt, dtype, stream);
+}
+
+FQ_API int fq_mx_export(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
+    return mx_entry(true, x, nullptr, elems_out, scales_out, rows, cols, fmt, dtype, stream);
+}
+
 }  // extern "C"

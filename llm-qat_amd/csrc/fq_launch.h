@@ -178,6 +178,27 @@ template <int DT> FQ_HIDDEN int launch_sym_autocast(bool wide, RowArgs a, void* 
 // group-wise forward (fq_group.h / fq_group.hip): a = x, y, rows, cols, constants and the optional training-mode outputs; gv = vectors
 // per group (4 .. 64); autocast = 1: Sym under autocast with the result rounded once to the tensor dtype (16-bit tensors)
 template <int DT> FQ_HIDDEN int launch_group(bool asym, bool fast, int autocast, RowArgs a, int gv, hipStream_t st);
+// MX block-scaled forward / export (fq_mx.h / fq_mx.hip): blocks of 32 consecutive elements, the element format in MxFmt
+enum : int { MX_FWD = 0, MX_EXP4 = 1, MX_EXP8 = 2 };
+constexpr int MX_TPB = 256, MX_VPT = 4;   // threads per workgroup, 16-byte vectors in flight per lane
+struct MxFmt {
+    int emax;          // exponent of the element format's largest binade (floor(log2 max-normal))
+    int mbits;         // mantissa bits
+    int emin;          // exponent of its smallest normal binade
+    float maxnorm;     // largest normal
+    uint32_t maxcode;  // code of the largest normal (export)
+    uint32_t signbit;  // sign bit of a code (export)
+};
+
+struct MxArgs {
+    const void* x;
+    void* y;             // MX_FWD
+    uint8_t* elems;      // MX_EXP4 / MX_EXP8
+    uint8_t* scales;     // MX_EXP4 / MX_EXP8
+    int64_t nvec;        // 16-byte vectors of the tensor: a multiple of the block's vector count
+    int ntl;             // non-temporal loads (the tensor is larger than NT_LOAD_MIN_BYTES): uniform over the launch
+};
+template <int DT> FQ_HIDDEN int launch_mx(int kind, MxArgs a, MxFmt f, hipStream_t st);
 template <int DT> FQ_HIDDEN int launch_ste(const void* g, const void* x, void* gx, int64_t n, float lo, float hi, hipStream_t st);
 // STE backward from (bounds, mask) for the L.n tensors of one launch (g / gx / bounds / mask / rows filled in by the caller;
 // blk_begin / inplace are set here)

@@ -1054,3 +1054,106 @@ def sym_row_scales(x, num_bits, layerwise=False, autocast=None):
                                           -2.0, 2.0, None, None, 0, _stream(x))
     _lib.check(rc, "sym_row_scales")
     return scales
+
+
+# ---- OCP Microscaling (MX) block scales: 32 consecutive elements of the last dimension share one E8M0 power-of-two scale ----------------
+# (include/llmqat_fakequant.h "MX block scales").  One launch per tensor; a non-contiguous or misaligned input takes one
+# .contiguous() copy first (a correctness path, counted as mx_copy_route).  No CPU implementation: CPU tensors raise.
+MX_FORMATS = {"mxfp4": _lib.MX_FP4_E2M1, "mxfp6_e2m3": _lib.MX_FP6_E2M3, "mxfp6_e3m2": _lib.MX_FP6_E3M2,
+              "mxfp8_e4m3": _lib.MX_FP8_E4M3, "mxfp8_e5m2": _lib.MX_FP8_E5M2}
+MX_BLOCK = 32
+mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0}
+
+
+def check_mx(shape, fmt):
+    """-> the format's C code after the argument checks of the MX API (ValueError for an unknown format or a last dimension that is not a
+    multiple of 32)"""
+    code = MX_FORMATS.get(fmt) if isinstance(fmt, str) else None
+    if code is None:
+        raise ValueError(f"unknown MX format {fmt!r}: one of {', '.join(MX_FORMATS)}")
+    if len(shape) == 0:
+        raise ValueError("MX formats take tensors with at least one dimension")
+    if shape[-1] % MX_BLOCK:
+        raise ValueError(f"MX formats need a last dimension that is a multiple of {MX_BLOCK}, got {shape[-1]}")
+    return code
+
+
+def _mx_input(x, fmt, what):
+    code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) else None
+    dt = _prep(x, what)
+    if dt == _lib.DTYPE_F64:
+        raise NotImplementedError(f"{what}: float64 is not served by the MX formats (float32, bfloat16, float16 are)")
+    if not x.is_contiguous() or x.data_ptr() & 15:
+        mx_counts["mx_copy_route"] += 1
+        x = x.contiguous() if not x.is_contiguous() else x.clone()   # (a fresh allocation is 16-byte aligned)
+    return x, code, dt
+
+
+def mx_quantize(x, fmt):
+    """MX fake quantization of x (same shape and dtype): each block of 32 elements along the last dimension scaled by its shared power
+    of two, rounded onto the element grid of `fmt` and saturated, then scaled back and rounded once to x's dtype."""
+    x, code, dt = _mx_input(x, fmt, "mx_quantize")
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    if x.numel():
+        cols = x.shape[-1]
+        rows = x.numel() // cols
+        L = _lib.lib()
+        _lib.check(_on_device(x, lambda st: L.fq_mx_fwd(x.data_ptr(), y.data_ptr(), rows, cols, code, dt, st)), "mx_quantize")
+        mx_counts["mx_launch"] += 1
+    return y
+
+
+# E2M1 values of the 16 FP4 codes (sign in bit 3)
+_FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)
+
+
+class MXExport:
+    """The integer form of an MX-fake-quantized tensor.
+      elements  uint8 [..., cols / 2] (mxfp4: element 2k in the low nibble of byte k) or [..., cols] (mxfp8_*: float8_e4m3fn / float8_e5m2
+                bit patterns)
+      scales    uint8 [..., cols / 32]: one E8M0 byte (E + 127) per block; 0xFF marks a block that held a NaN or Inf (its codes are 0)
+    dequantize() gives back mx_quantize(x, fmt) bit for bit (signed zeros included; NaN blocks as NaN), in plain torch ops."""
+    __slots__ = ("elements", "scales", "fmt", "shape", "dtype")
+
+    def __init__(self, elements, scales, fmt, shape, dtype):
+        self.elements, self.scales, self.fmt, self.shape, self.dtype = elements, scales, fmt, tuple(shape), dtype
+
+    def __repr__(self):
+        return f"MXExport(fmt={self.fmt!r}, shape={self.shape}, dtype={self.dtype})"
+
+    def dequantize(self):
+        e = self.elements
+        if self.fmt == "mxfp4":
+            lut = torch.tensor(_FP4_VALUES, dtype=torch.float32, device=e.device)
+            codes = torch.stack((e & 0xF, e >> 4), -1).reshape(*e.shape[:-1], e.shape[-1] * 2)
+            q = lut[codes.long()]
+        elif self.fmt in ("mxfp8_e4m3", "mxfp8_e5m2"):
+            q = e.view(torch.float8_e4m3fn if self.fmt == "mxfp8_e4m3" else torch.float8_e5m2).float()
+        else:
+            raise ValueError(f"{self.fmt!r} has no export packing")
+        # 2^(scale - 127), built from its float32 bits (exact: 0 -> 2^-127, a subnormal); the E8M0 NaN byte 0xFF -> NaN for the whole block
+        s = self.scales.int()
+        x = torch.where(s == 0, 0x00400000, s << 23).view(torch.float32)
+        x = torch.where(s == 0xFF, float("nan"), x)
+        y = q.view(*q.shape[:-1], -1, MX_BLOCK) * x.unsqueeze(-1)
+        return y.reshape(self.shape).to(self.dtype)
+
+
+def mx_export(x, fmt):
+    """-> MXExport(elements, scales, fmt, shape, dtype): the codes and E8M0 scales of mx_quantize(x, fmt).  mxfp4 and mxfp8_* only (FP6 has
+    no packing here: ValueError)."""
+    code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) else None
+    if code in (_lib.MX_FP6_E2M3, _lib.MX_FP6_E3M2):
+        raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
+    x, code, dt = _mx_input(x, fmt, "mx_export")
+    cols = x.shape[-1]
+    lead = tuple(x.shape[:-1])
+    elems = torch.empty(lead + (cols // 2 if code == _lib.MX_FP4_E2M1 else cols,), dtype=torch.uint8, device=x.device)
+    scales = torch.empty(lead + (cols // MX_BLOCK,), dtype=torch.uint8, device=x.device)
+    if x.numel():
+        rows = x.numel() // cols
+        L = _lib.lib()
+        _lib.check(_on_device(x, lambda st: L.fq_mx_export(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, st)),
+                   "mx_export")
+        mx_counts["mx_export_launch"] += 1
+    return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype)

@@ -107,18 +107,23 @@ def stats(reset=False):
                                          ATen's summation order did not verify on this device / torch build
       group_launch / group_view_route    group-wise forwards served by the group kernel (fq_group_fwd) / by the row-wise kernels on the
                                          [-1, group_size] view (other divisors, strided or misaligned tensors, float64, fp32-result autocast)
+      mx_launch / mx_export_launch / mx_copy_route
+                                         MX block-scaled forwards (ops.mx_quantize) and exports (ops.mx_export) launched, and the inputs of
+                                         either that took one .contiguous() copy first (non-contiguous or misaligned)
       cpp_pair_forward / cpp_weight_forward / cpp_pair_backward / cpp_one_backward / cpp_slow_backward
                                          what the C++ autograd nodes did (_fq_node.so; `host_node()` says whether it is loaded): operand-pair and
                                          weight-only launches made from C++, pair / one-tensor (K, V) backwards, and backwards handed back to the
                                          Python nodes' code"""
     out = dict(_stats)
-    for k, v in ops.group_counts.items():   # group-wise forwards (ops.group_forward): kernel launches / row-wise kernels on the view
-        if v:
-            out[k] = out.get(k, 0) + v
+    for counts in (ops.group_counts, ops.mx_counts):   # group-wise forwards (ops.group_forward); MX forwards / exports (ops.mx_*)
+        for k, v in counts.items():
+            if v:
+                out[k] = out.get(k, 0) + v
     if reset:
         _stats.clear()
-        for k in ops.group_counts:
-            ops.group_counts[k] = 0
+        for counts in (ops.group_counts, ops.mx_counts):
+            for k in counts:
+                counts[k] = 0
     if _cnode is not None:      # what the C++ node counted (its guard's decisions, its launches): same names
         for k, v in _cnode.counters(reset).items():
             out[k] = out.get(k, 0) + v
@@ -413,6 +418,47 @@ def default_group_sizes(weight=None, act=None):
         if g is not None:
             ops.check_group((g,), g)
     _DEFAULT_GROUPS = (weight, act)
+    return prev
+
+
+class _MXQuantizer(torch.autograd.Function):
+    """MX block-scaled fake quantization (ops.mx_quantize) with the straight-through identity gradient: nothing is saved and no backward
+    kernel runs (as the 1-/2-bit weight branches, _LowBitWeight).  The saturated elements are not masked."""
+
+    @staticmethod
+    def forward(ctx, x, fmt):
+        ctx.set_materialize_grads(False)
+        return ops.mx_quantize(x, fmt)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return grad_output, None
+
+
+def mx_quantize(x, fmt):
+    """OCP MX fake quantization ("mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8_e4m3", "mxfp8_e5m2"): every 32 consecutive elements of the
+    last dimension share one power-of-two scale.  Same shape and dtype as x; the gradient is the identity (straight-through)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
+    ops.check_mx(tuple(x.shape), fmt)
+    if torch.compiler.is_compiling():
+        return compiled.mx_fake_quant_op(x, fmt)
+    return _MXQuantizer.apply(x, fmt)
+
+
+_DEFAULT_MX = (None, None)   # (weight, activation) MX formats of QuantizeLinears constructed without explicit ones
+
+
+def default_mx_formats(weight=None, act=None):
+    """MX formats the QuantizeLinears constructed from now on take for the operands they quantize (w_bits < 32 / a_bits < 32, not
+    layerwise, no explicit group size) when their own weight_format / act_format are not given (None: the integer quantizers).  Lets
+    unchanged model code (LLM-QAT's train.py) train for MXFP4.  -> the previous pair."""
+    global _DEFAULT_MX
+    for f in (weight, act):
+        if f is not None and f not in ops.MX_FORMATS:
+            raise ValueError(f"unknown MX format {f!r}: one of {', '.join(ops.MX_FORMATS)}")
+    prev = _DEFAULT_MX
+    _DEFAULT_MX = (weight, act)
     return prev
 
 
@@ -1178,16 +1224,41 @@ class QuantizeLinear(nn.Linear):
     _fq_plan = None   # (input shape, input dtype, weight dtype, ops.pair_plan): the launch plan of the last input shape (a plain attribute)
     weight_group_size = None   # group-wise scales (plain attributes: state_dict() keys stay the reference's)
     act_group_size = None
+    weight_format = None       # MX formats (ops.MX_FORMATS): replace that operand's integer quantizer
+    act_format = None
 
     def __init__(self, *kargs, symmetric=True, bias=False, w_bits=32, a_bits=32, act_layerwise=False,
-                 weight_layerwise=False, weight_group_size=None, act_group_size=None):
+                 weight_layerwise=False, weight_group_size=None, act_group_size=None, weight_format=None, act_format=None):
         super().__init__(*kargs, bias=False)  # `bias` is accepted and ignored, as in the reference (:176)
         self.w_bits = w_bits
         self.a_bits = a_bits
         self.act_layerwise = act_layerwise
         self.weight_layerwise = weight_layerwise
+        # MX formats: an explicit argument always applies (and excludes that operand's group size and layerwise flag); the process default
+        # (default_mx_formats) applies to the operands this layer quantizes, and then no default group size does
+        mw, ma = _DEFAULT_MX
+        if weight_format is not None:
+            if weight_group_size is not None or weight_layerwise:
+                raise ValueError("weight_format cannot be combined with weight_group_size or weight_layerwise")
+            ops.check_mx(tuple(self.weight.shape), weight_format)
+            self.weight_format = weight_format
+        elif mw is not None and w_bits < 32 and weight_group_size is None and not weight_layerwise:
+            self.weight_format = mw
+            ops.check_mx(tuple(self.weight.shape), mw)
+        if act_format is not None:
+            if act_group_size is not None or act_layerwise:
+                raise ValueError("act_format cannot be combined with act_group_size or act_layerwise")
+            ops.check_mx((self.in_features,), act_format)
+            self.act_format = act_format
+        elif ma is not None and a_bits < 32 and act_group_size is None and not act_layerwise:
+            self.act_format = ma
+            ops.check_mx((self.in_features,), ma)
         # group sizes: an explicit argument is checked and kept; the process default (default_group_sizes) applies where it means something
         dw, da = _DEFAULT_GROUPS
+        if self.weight_format is not None:
+            dw = None
+        if self.act_format is not None:
+            da = None
         if weight_group_size is not None:
             if not 3 <= w_bits < 32:
                 raise ValueError(f"weight_group_size applies to SymQuantizer weights (3 <= w_bits < 32), this layer has w_bits={w_bits}")
@@ -1405,13 +1476,17 @@ class QuantizeLinear(nn.Linear):
         """The integer form of this layer's fake-quantized weight for an inference export: packed bins (int4 for
         w_bits <= 4, int8 / int16 above) + per-output-channel {s, t2} (ops.QuantExport; `dequantize()` gives back the
         value the forward multiplies with, bit for bit where overflow == 0).  Serves the w_bits >= 3 path (:195-201)."""
+        if self.weight_format is not None:   # MX weights: codes + E8M0 scales (ops.MXExport); FP6 has no packing (ValueError)
+            return ops.mx_export(self.weight.detach(), self.weight_format)
         if not 3 <= self.w_bits < 32:
             raise ValueError(f"export_weight serves 3 <= w_bits < 32 (SymQuantizer weights), this layer has w_bits={self.w_bits}")
         return ops.sym_export(self.weight.detach(), self.w_bits, self.weight_layerwise, container=container, group_size=self.weight_group_size)
 
     def _forward_compiled(self, input_):
         """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
-        if self.w_bits >= 32:
+        if self.weight_format is not None:   # MX: llmqat_amd::mx_fake_quant, identity gradient
+            weight = compiled.mx_fake_quant_op(self.weight, self.weight_format)
+        elif self.w_bits >= 32:
             weight = self.weight
         elif self.w_bits >= 3 and self.weight_group_size is not None:   # grouped: the same custom ops on the [-1, g] view
             g = self.weight_group_size
@@ -1423,7 +1498,9 @@ class QuantizeLinear(nn.Linear):
                 absmean = self.weight.abs().mean() if self.weight_layerwise else self.weight.abs().mean(dim=1, keepdim=True)
                 sc = absmean if self.w_bits == 1 else 2 * absmean
             weight = compiled.low_bit_weight_op(self.weight, sc, self.w_bits)
-        if 2 < self.a_bits < 32 and self.act_group_size is not None:
+        if self.act_format is not None:
+            input_ = compiled.mx_fake_quant_op(input_, self.act_format)
+        elif 2 < self.a_bits < 32 and self.act_group_size is not None:
             g = self.act_group_size
             input_ = compiled.fake_quant(self._act_kind, input_.reshape(-1, g), _CLIP, self.a_bits, False, narrow=True).reshape(input_.shape)
         elif 2 < self.a_bits < 32:
@@ -1433,10 +1510,39 @@ class QuantizeLinear(nn.Linear):
             out += self.bias.view(1, -1).expand_as(out)
         return out
 
+    def _forward_mx(self, input_):
+        """an MX layer (eager): one launch per quantized operand forward, none backward (identity gradient).  No operand pair, C++ pair
+        node, weight cache or activation sharing; an operand without a format keeps its integer quantizer (uncached, unshared)."""
+        if self.weight_format is not None:
+            weight = _MXQuantizer.apply(self.weight, self.weight_format)
+        elif self.w_bits >= 32:
+            weight = self.weight
+        elif self.weight_group_size is not None:
+            weight = _GroupQuantizer.apply(self.weight, _CLIP, self.w_bits, self.weight_group_size, "sym", True, True)
+        elif self.w_bits >= 3:
+            weight = _SymQuantizerWeight.apply(self.weight, _CLIP, self.w_bits, self.weight_layerwise)
+        else:
+            weight = self._low_bit_weight(self.weight)
+        if self.act_format is not None:
+            input_ = _MXQuantizer.apply(input_, self.act_format)
+        elif 2 < self.a_bits < 32:
+            if self.act_group_size is not None:
+                input_ = _GroupQuantizer.apply(input_, _CLIP, self.a_bits, self.act_group_size, self._act_kind, True, False)
+            else:
+                quantizer = _SymQuantizerOperand if self.act_quantizer is SymQuantizer else self.act_quantizer
+                input_ = quantizer.apply(input_, _CLIP, self.a_bits, self.act_layerwise)
+        out = nn.functional.linear(input_, weight)
+        if self.bias is not None:
+            out += self.bias.view(1, -1).expand_as(out)
+        return out
+
     def forward(self, input_):
         assert len(self.weight.size()) == 2
         if torch.compiler.is_compiling():
             return self._forward_compiled(input_)
+        if self.weight_format is not None or self.act_format is not None:
+            _count("single_launch")
+            return self._forward_mx(input_)
         pair = self._pair_forward(input_)
         if pair is not None:
             weight, input_ = pair
