@@ -399,6 +399,27 @@ int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t cols, i
 int fq_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, void* stream);
 int fq_mx_export(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, void* stream);
 
+/*
+ * ---- MX block-scaled GEMM (an addition to ABI 7) ---------------------------------------------------------------------------------------
+ * FQ_ABI_VERSION stays 7: nothing that existed changes, and the merged suite pins fq_version() == 7 (tests/test_mx_cpu.py).  A binding that
+ * needs this entry point finds out by looking the symbol up.
+ * out[m, n] = sum_k A[m, k] * W[n, k] (the orientation of F.linear) over two fq_mx_export results, on the block-scaled matrix instruction
+ * v_mfma_scale_f32_16x16x128_f8f6f4: the element codes and E8M0 bytes are the instruction's operands as exported,
+ * the products are exact, the sum is the matrix core's fp32 accumulation, and the result is rounded once to out_dtype.
+ *   a_elems / a_scales   A: [M, K] codes (FP4: M*K/2 bytes, FP8: M*K bytes) and [M, K/32] E8M0 bytes, in fq_mx_export's layout
+ *   w_elems / w_scales   W: [N, K] likewise
+ *   a_fmt, w_fmt         each FQ_MX_FP4_E2M1, FQ_MX_FP8_E4M3 or FQ_MX_FP8_E5M2, independently (9 pairs); FP6 / unknown: FQ_ERR_ARG
+ *   out                  [M, N] out_dtype (FQ_DTYPE_F32 / BF16 / F16; float64: FQ_ERR_DTYPE), contiguous
+ *   K                    a positive multiple of 128 (the instruction's k); anything else, K == 0 included: FQ_ERR_SHAPE
+ * An 0xFF scale byte in row m of A makes out[m, :] NaN, in row n of W out[:, n]; scale byte 0 is 2^-127.
+ * M <= 32 runs the skinny (decode) kernel: W is read once, its K split over the 8 waves of a workgroup and summed in a fixed order;
+ * larger M the tiled kernel.  Neither uses atomics or a workspace: results are run-to-run identical.
+ * Status: FQ_ERR_DTYPE, FQ_ERR_ARG, FQ_ERR_SHAPE (negative sizes, M / N / K >= 2^31, K), 0 without a launch for M == 0 or N == 0, FQ_ERR_NULL,
+ * FQ_ERR_UNSUPPORTED (a_elems / w_elems / out not 16-byte aligned; N > 128 * 65535 with M > 32), in that order, all before any HIP call.
+ */
+int fq_mx_gemm(const void* a_elems, const void* a_scales, int a_fmt, const void* w_elems, const void* w_scales, int w_fmt, void* out,
+               int64_t M, int64_t N, int64_t K, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ ONE graph.  `utils_quant` routes here while `torch.compiler.is_compiling()`; res
 what a compiled graph keeps alive is planned by the partitioner, so the STE-mask / sharing / pairing machinery of the
 eager path is not replicated here.
 """
+from typing import List, Tuple
+
 import torch
 
 from . import ops
@@ -89,3 +91,35 @@ def _(x, fmt):
 
 
 mx_fake_quant_op.register_autograd(lambda ctx, g: (g, None))
+
+
+
+# MX block-scaled GEMM (ops.mx_matmul) on the tensors of the two exports; inference only: no autograd formula is registered, so asking
+# for a gradient through it raises
+@torch.library.custom_op("llmqat_amd::mx_matmul", mutates_args=(), device_types="cuda")
+def mx_matmul_op(a_elems: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, w_elems: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
+                 a_shape: List[int], out_dtype: torch.dtype) -> torch.Tensor:
+    return ops.mx_matmul_tensors(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, tuple(a_shape), out_dtype)
+
+
+@mx_matmul_op.register_fake
+def _(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, a_shape, out_dtype):
+    _, N, _ = ops.check_mx_matmul(tuple(a_shape), a_fmt, (w_scales.shape[0], w_scales.shape[1] * ops.MX_BLOCK), w_fmt, out_dtype)
+    return a_elems.new_empty(tuple(a_shape[:-1]) + (N,), dtype=out_dtype)
+
+
+# ops.mx_export as an op: (elements, scales) of x in `fmt` (mxfp4 / mxfp8_*)
+@torch.library.custom_op("llmqat_amd::mx_export", mutates_args=(), device_types="cuda")
+def mx_export_op(x: torch.Tensor, fmt: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    e = ops.mx_export(x, fmt)
+    return e.elements, e.scales
+
+
+@mx_export_op.register_fake
+def _(x, fmt):
+    ops.check_mx(tuple(x.shape), fmt)
+    if fmt not in ops.MX_GEMM_FORMATS:
+        raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
+    lead, cols = tuple(x.shape[:-1]), x.shape[-1]
+    return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
+            x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))

@@ -527,4 +527,25 @@ FQ_API int fq_mx_export(const void* x, void* elems_out, void* scales_out, int64_
     return mx_entry(true, x, nullptr, elems_out, scales_out, rows, cols, fmt, dtype, stream);
 }
 
+// Every check comes before any HIP call.
+FQ_API int fq_mx_gemm(const void* a_elems, const void* a_scales, int a_fmt, const void* w_elems, const void* w_scales, int w_fmt, void* out,
+                      int64_t M, int64_t N, int64_t K, int out_dtype, void* stream) {
+    if (out_dtype < 0 || out_dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", out_dtype);
+    if (out_dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
+    for (int fmt : {a_fmt, w_fmt}) {
+        if (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
+        if (fmt == FQ_MX_FP6_E2M3 || fmt == FQ_MX_FP6_E3M2) return fail(FQ_ERR_ARG, "FP6 formats have no export packing and no GEMM operand");
+    }
+    if (M < 0 || N < 0 || K < 0) return fail(FQ_ERR_SHAPE, "negative shape M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+    if (M > 0x7FFFFFFF || N > 0x7FFFFFFF || K > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "M, N and K must be below 2^31 (byte offsets are 64-bit products of two)");
+    if (K == 0 || K % MXG_KSTEP != 0) return fail(FQ_ERR_SHAPE, "K=%lld is not a positive multiple of %d", (long long)K, MXG_KSTEP);
+    if (M == 0 || N == 0) return ok();
+    if (!a_elems || !a_scales || !w_elems || !w_scales || !out) return fail(FQ_ERR_NULL, "a_elems / a_scales / w_elems / w_scales / out must not be NULL");
+    if (!aligned16(a_elems) || !aligned16(w_elems) || !aligned16(out))
+        return fail(FQ_ERR_UNSUPPORTED, "a_elems, w_elems and out must be 16-byte aligned");
+    if (M > MXG_SKINNY_M && (N + MXG_TILE - 1) / MXG_TILE > 65535) return fail(FQ_ERR_UNSUPPORTED, "N=%lld exceeds one launch's grid", (long long)N);
+    const MxGemmArgs g{(const uint8_t*)w_elems, (const uint8_t*)w_scales, (const uint8_t*)a_elems, (const uint8_t*)a_scales, out, M, N, K, w_fmt, a_fmt, out_dtype};
+    return launch_mx_gemm(g, (hipStream_t)stream);
+}
+
 }  // extern "C"

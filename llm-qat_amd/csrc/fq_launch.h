@@ -199,6 +199,21 @@ struct MxArgs {
     int ntl;             // non-temporal loads (the tensor is larger than NT_LOAD_MIN_BYTES): uniform over the launch
 };
 template <int DT> FQ_HIDDEN int launch_mx(int kind, MxArgs a, MxFmt f, hipStream_t st);
+// MX block-scaled GEMM (fq_mx_gemm.h / fq_mx_gemm.hip): out[m, n] = sum_k A[m, k] * W[n, k] over two MX exports
+struct MxGemmArgs {
+    const uint8_t* we;   // W: [N, K] element codes, E8M0 scales [N, K / 32]
+    const uint8_t* ws;
+    const uint8_t* ae;   // A: [M, K]
+    const uint8_t* as;
+    void* out;           // [M, N], out_dtype
+    int64_t M, N, K;     // K a positive multiple of 128
+    int w_fmt, a_fmt;    // FQ_MX_FP4_E2M1 / FQ_MX_FP8_E4M3 / FQ_MX_FP8_E5M2
+    int out_dtype;       // FQ_DTYPE_F32 / BF16 / F16
+};
+constexpr int MXG_KSTEP = 128;          // k per scaled MFMA: K must be a multiple
+constexpr int MXG_SKINNY_M = 32;        // largest M of the skinny (decode) kernel
+constexpr int MXG_TILE = 128;           // workgroup tile of the tiled kernel, both ways
+FQ_HIDDEN int launch_mx_gemm(const MxGemmArgs& g, hipStream_t st);
 template <int DT> FQ_HIDDEN int launch_ste(const void* g, const void* x, void* gx, int64_t n, float lo, float hi, hipStream_t st);
 // STE backward from (bounds, mask) for the L.n tensors of one launch (g / gx / bounds / mask / rows filled in by the caller;
 // blk_begin / inplace are set here)

@@ -1,0 +1,90 @@
+"""Inference in the arithmetic MX fake quantization simulates: a linear layer whose weight is kept as MX codes (4.25 bits per element for
+mxfp4) and whose product runs on gfx950's block-scaled matrix instruction (ops.mx_matmul)."""
+import torch
+from torch import nn
+
+from . import compiled, ops
+from .utils_quant import QuantizeLinear
+
+
+def _why_not(layer):
+    """None if `layer` can become an MXLinear, else the reason."""
+    if not isinstance(layer, QuantizeLinear):
+        return f"expected a QuantizeLinear, got {type(layer).__name__}"
+    for what, fmt in (("weight_format", layer.weight_format), ("act_format", layer.act_format)):
+        if fmt is None:
+            return f"{what} is not set: the layer does not quantize that operand to an MX format"
+        if fmt not in ops.MX_GEMM_FORMATS:
+            return f"{what}={fmt!r} has no export packing (one of {', '.join(ops.MX_GEMM_FORMATS)})"
+    if layer.in_features == 0 or layer.in_features % ops.MX_GEMM_KSTEP:
+        return f"in_features={layer.in_features} is not a positive multiple of {ops.MX_GEMM_KSTEP}, the K step of the MX GEMM kernel"
+    return None
+
+
+class MXLinear(nn.Module):
+    """y = mx_matmul(mx_export(x, act_format), W) (+ bias): two launches, W held as `weight_elements` / `weight_scales` buffers (the
+    ops.MXExport of the trained weight), no bf16 weight.  Inference only: not differentiable."""
+
+    def __init__(self, in_features, out_features, weight_format="mxfp4", act_format="mxfp8_e4m3", bias=False, device=None, dtype=None):
+        super().__init__()
+        for what, fmt in (("weight_format", weight_format), ("act_format", act_format)):
+            if fmt not in ops.MX_GEMM_FORMATS:
+                raise ValueError(f"{what}={fmt!r}: one of {', '.join(ops.MX_GEMM_FORMATS)}")
+        if in_features <= 0 or in_features % ops.MX_GEMM_KSTEP:
+            raise ValueError(f"in_features={in_features} is not a positive multiple of {ops.MX_GEMM_KSTEP}, the K step of the MX GEMM kernel")
+        self.in_features, self.out_features = in_features, out_features
+        self.weight_format, self.act_format = weight_format, act_format
+        ebytes = in_features // 2 if weight_format == "mxfp4" else in_features
+        self.register_buffer("weight_elements", torch.zeros(out_features, ebytes, dtype=torch.uint8, device=device))
+        self.register_buffer("weight_scales", torch.zeros(out_features, in_features // ops.MX_BLOCK, dtype=torch.uint8, device=device))
+        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
+
+    @classmethod
+    def from_quantize_linear(cls, layer):
+        """The inference form of a QuantizeLinear whose weight and activations both resolve to mxfp4 / mxfp8_* (explicitly or through
+        default_mx_formats) and whose in_features the kernel serves; ValueError names what is missing otherwise.  The weight is exported
+        once (one launch), on the device it lives on."""
+        why = _why_not(layer)
+        if why is not None:
+            raise ValueError(f"MXLinear.from_quantize_linear: {why}")
+        has_bias = getattr(layer, "bias", None) is not None
+        m = cls(layer.in_features, layer.out_features, layer.weight_format, layer.act_format, bias=has_bias, device=layer.weight.device,
+                dtype=layer.weight.dtype)
+        e = layer.export_weight() if hasattr(layer, "export_weight") else ops.mx_export(layer.weight.detach(), layer.weight_format)
+        m.weight_elements.copy_(e.elements)
+        m.weight_scales.copy_(e.scales)
+        if has_bias:
+            m.bias.copy_(layer.bias.detach())
+        return m
+
+    def weight_export(self):
+        """the weight as an ops.MXExport (shares the buffers)"""
+        return ops.MXExport(self.weight_elements, self.weight_scales, self.weight_format, (self.out_features, self.in_features),
+                            torch.float32 if self.bias is None else self.bias.dtype)
+
+    def forward(self, x):
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("MXLinear is an inference module and is not differentiable: call it under torch.no_grad() or on a detached input")
+        if torch.compiler.is_compiling():
+            ae, asc = compiled.mx_export_op(x, self.act_format)
+            y = compiled.mx_matmul_op(ae, asc, self.act_format, self.weight_elements, self.weight_scales, self.weight_format, list(x.shape), x.dtype)
+        else:
+            a = ops.mx_export(x, self.act_format)
+            y = ops.mx_matmul_tensors(a.elements, a.scales, a.fmt, self.weight_elements, self.weight_scales, self.weight_format, a.shape, x.dtype)
+        return y if self.bias is None else y + self.bias
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, out_features={self.out_features}, weight_format={self.weight_format!r}, "
+                f"act_format={self.act_format!r}, bias={self.bias is not None}")
+
+
+def convert_to_mx_inference(model):
+    """Replace, in place, every QuantizeLinear of `model` that MXLinear.from_quantize_linear accepts; integer-quantized, group-wise, FP6
+    layers and those whose in_features the kernel does not serve stay as they are.  -> the number of layers replaced."""
+    n = 0
+    for parent in list(model.modules()):
+        for name, child in list(parent.named_children()):
+            if isinstance(child, QuantizeLinear) and _why_not(child) is None:
+                setattr(parent, name, MXLinear.from_quantize_linear(child))
+                n += 1
+    return n

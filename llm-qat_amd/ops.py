@@ -1062,7 +1062,7 @@ def sym_row_scales(x, num_bits, layerwise=False, autocast=None):
 MX_FORMATS = {"mxfp4": _lib.MX_FP4_E2M1, "mxfp6_e2m3": _lib.MX_FP6_E2M3, "mxfp6_e3m2": _lib.MX_FP6_E3M2,
               "mxfp8_e4m3": _lib.MX_FP8_E4M3, "mxfp8_e5m2": _lib.MX_FP8_E5M2}
 MX_BLOCK = 32
-mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0}
+mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm_launch": 0, "mx_gemm_skinny": 0, "mx_gemm_tiled": 0}
 
 
 def check_mx(shape, fmt):
@@ -1157,3 +1157,81 @@ def mx_export(x, fmt):
                    "mx_export")
         mx_counts["mx_export_launch"] += 1
     return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype)
+
+
+# ---- MX block-scaled GEMM: the exported codes on gfx950's scaled matrix instruction (fq_mx_gemm) ------------------
+MX_GEMM_KSTEP = 128      # k of one v_mfma_scale_f32_16x16x128_f8f6f4: K must be a multiple
+MX_GEMM_SKINNY_M = 32    # rows of `a` up to which the skinny (decode) kernel runs
+MX_GEMM_FORMATS = ("mxfp4", "mxfp8_e4m3", "mxfp8_e5m2")
+_OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def check_mx_matmul(a_shape, a_fmt, w_shape, w_fmt, out_dtype):
+    """The argument checks of mx_matmul on shapes alone (the fake implementation of the compiled op runs them too) -> (M, N, K)."""
+    for what, fmt in (("a", a_fmt), ("w", w_fmt)):
+        if fmt not in MX_FORMATS:
+            raise ValueError(f"mx_matmul: unknown MX format {fmt!r} of {what}: one of {', '.join(MX_GEMM_FORMATS)}")
+        if fmt not in MX_GEMM_FORMATS:
+            raise ValueError(f"mx_matmul: {fmt!r} ({what}): FP6 formats have no export packing and are no GEMM operand")
+    if len(w_shape) != 2:
+        raise ValueError(f"mx_matmul: w must be 2-D [N, K], got shape {tuple(w_shape)}")
+    if len(a_shape) < 1:
+        raise ValueError("mx_matmul: a needs at least one dimension")
+    K = a_shape[-1]
+    if K != w_shape[1]:
+        raise ValueError(f"mx_matmul: a has K={K} but w has K={w_shape[1]}")
+    if K == 0 or K % MX_GEMM_KSTEP:
+        raise ValueError(f"mx_matmul: K={K} is not served: the kernel needs a positive multiple of {MX_GEMM_KSTEP}")
+    if out_dtype not in _OUT_DTYPES:
+        raise ValueError(f"mx_matmul: out_dtype {out_dtype} is not served (float32, bfloat16, float16 are)")
+    M = 1
+    for d in a_shape[:-1]:
+        M *= d
+    return M, w_shape[0], K
+
+
+def mx_matmul_tensors(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, a_shape, out_dtype):
+    """mx_matmul on the exports' tensors (what MXLinear keeps as buffers); a_shape: the exported activation's shape [..., K]."""
+    w_shape = (w_scales.shape[0], w_scales.shape[1] * MX_BLOCK) if w_scales.dim() == 2 else tuple(w_scales.shape)   # [N, K / 32] bytes
+    M, N, K = check_mx_matmul(tuple(a_shape), a_fmt, w_shape, w_fmt, out_dtype)
+    ts = (a_elems, a_scales, w_elems, w_scales)
+    for t in ts:
+        _prep_u8(t, "mx_matmul")
+    if len({t.device for t in ts}) != 1:
+        raise ValueError("mx_matmul: the operands live on different devices")
+    for t, fmt, rows, what in ((a_elems, a_fmt, M, "a.elements"), (w_elems, w_fmt, N, "w.elements")):
+        if t.numel() != rows * (K // 2 if fmt == "mxfp4" else K):
+            raise ValueError(f"mx_matmul: {what} holds {t.numel()} bytes, not those of a [{rows}, {K}] {fmt} export")
+    if a_scales.numel() != M * (K // MX_BLOCK) or w_scales.numel() != N * (K // MX_BLOCK):
+        raise ValueError("mx_matmul: a scales tensor does not hold one byte per 32-element block")
+    fix = lambda t: t if (t.is_contiguous() and not t.data_ptr() & 15) else t.contiguous().clone()
+    a_elems, a_scales, w_elems, w_scales = fix(a_elems), fix(a_scales), fix(w_elems), fix(w_scales)
+    out = torch.empty(tuple(a_shape[:-1]) + (N,), dtype=out_dtype, device=a_elems.device)
+    if M and N:
+        L = _lib.lib()
+        _lib.check(_on_device(a_elems, lambda st: L.fq_mx_gemm(a_elems.data_ptr(), a_scales.data_ptr(), MX_FORMATS[a_fmt], w_elems.data_ptr(),
+                                                               w_scales.data_ptr(), MX_FORMATS[w_fmt], out.data_ptr(), M, N, K,
+                                                               _OUT_DTYPES[out_dtype], st)), "mx_matmul")
+        mx_counts["mx_gemm_launch"] += 1
+        mx_counts["mx_gemm_skinny" if M <= MX_GEMM_SKINNY_M else "mx_gemm_tiled"] += 1
+    return out
+
+
+def _prep_u8(t, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise TypeError(f"{what}: elements and scales are uint8 tensors")
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{what}: tensor is on '{t.device}'. llm_qat_amd runs on MI355X only and has no CPU "
+                           "fallback; move the tensor to the GPU.")
+
+
+def mx_matmul(a, w, out_dtype=None):
+    """out[..., n] = sum_k a[..., k] * w[n, k] over two MXExports, on the block-scaled matrix instruction: the value of
+    a.dequantize().double() @ w.dequantize().double().T up to the fp32 accumulation of the matrix core, rounded once to out_dtype
+    (default a.dtype).  a: [..., K], w: [N, K], each mxfp4 / mxfp8_e4m3 / mxfp8_e5m2; K a multiple of 128.  An 0xFF (NaN) scale block in a
+    row of a / w makes that output row / column NaN."""
+    if not isinstance(a, MXExport) or not isinstance(w, MXExport):
+        raise TypeError("mx_matmul: a and w are MXExport objects (ops.mx_export)")
+    out_dtype = a.dtype if out_dtype is None else out_dtype
+    check_mx_matmul(a.shape, a.fmt, w.shape, w.fmt, out_dtype)
+    return mx_matmul_tensors(a.elements, a.scales, a.fmt, w.elements, w.scales.reshape(w.shape[0], -1), w.fmt, a.shape, out_dtype)

@@ -110,6 +110,8 @@ def stats(reset=False):
       mx_launch / mx_export_launch / mx_copy_route
                                          MX block-scaled forwards (ops.mx_quantize) and exports (ops.mx_export) launched, and the inputs of
                                          either that took one .contiguous() copy first (non-contiguous or misaligned)
+      mx_gemm_launch / mx_gemm_skinny / mx_gemm_tiled
+                                         MX block-scaled GEMMs (ops.mx_matmul, MXLinear) launched, and which kernel served them (M <= 32: skinny)
       cpp_pair_forward / cpp_weight_forward / cpp_pair_backward / cpp_one_backward / cpp_slow_backward
                                          what the C++ autograd nodes did (_fq_node.so; `host_node()` says whether it is loaded): operand-pair and
                                          weight-only launches made from C++, pair / one-tensor (K, V) backwards, and backwards handed back to the
