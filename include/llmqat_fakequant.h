@@ -400,6 +400,27 @@ int fq_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int d
 int fq_mx_export(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, void* stream);
 
 /*
+ * ---- Block-Hadamard rotation fused into the MX kernels (an addition to ABI 7) ------------------------------------------------------------
+ * FQ_ABI_VERSION stays 7: nothing that existed changes.  A binding that needs these entry points finds out by looking the symbols up.
+ * R is block-diagonal along the last dimension with blocks H64 / 8, H64 the 64 x 64 Sylvester Hadamard matrix (entry (i, j) =
+ * (-1)^popcount(i & j)): exactly orthonormal, symmetric and its own inverse, entries +-0.125.  Rotating both operands of a product along K
+ * leaves it unchanged, (x R)(W R)^T = x W^T, and spreads an outlier over the 64 elements of its run before the block scale is taken
+ * (DESIGN.md section 15).  The arithmetic, per run of 64 consecutive elements, so that it can be checked bit for bit:
+ *   widen to fp32; for s = 1, 2, 4, 8, 16, 32 in that order, for every element index j of the run with bit s clear,
+ *   (v[j], v[j+s]) <- (v[j] + v[j+s], v[j] - v[j+s]), each one IEEE fp32 operation; then v[j] <- v[j] * 0.125f.
+ * fq_block_rotate   y = x R, the fp32 values rounded once to `dtype`.
+ * fq_mx_fwd_rot     fq_mx_fwd of the fp32 values of x R (amax, shared exponent, rounding, saturation as above; the sign is the rotated
+ *                   value's; a block whose rotated values hold a NaN or Inf -- a finite sum that overflowed included -- is a NaN block),
+ *                   rounded once to `dtype`.  One launch, no intermediate tensor.
+ * fq_mx_export_rot  fq_mx_export of the same values (FP4 and FP8 formats).
+ * Arguments and layouts as fq_mx_fwd / fq_mx_export, except cols: a multiple of 64 (FQ_ERR_SHAPE).  Status codes as there; fq_block_rotate
+ * takes no fmt.  y may not alias x.
+ */
+int fq_mx_fwd_rot(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, void* stream);
+int fq_mx_export_rot(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, void* stream);
+int fq_block_rotate(const void* x, void* y, int64_t rows, int64_t cols, int dtype, void* stream);
+
+/*
  * ---- MX block-scaled GEMM (an addition to ABI 7) ---------------------------------------------------------------------------------------
  * FQ_ABI_VERSION stays 7: nothing that existed changes, and the merged suite pins fq_version() == 7 (tests/test_mx_cpu.py).  A binding that
  * needs this entry point finds out by looking the symbol up.

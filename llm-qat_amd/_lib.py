@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # LLMQAT_AMD_LIB points the loader at another build of the library (A/B runs of kernel variants: tools/ab_bench.sh) -- the product
 # file is never overwritten; fq_build_info() / LIB_PATH say which one is loaded
 LIB_PATH = os.environ.get("LLMQAT_AMD_LIB") or os.path.join(HERE, "libllmqat_fakequant.so")
-ABI_VERSION = 7   # fq_mx_gemm is an addition within 7 (the header says why)
+ABI_VERSION = 7   # fq_mx_gemm and the rotated MX entry points are additions within 7 (the header says why)
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16, DTYPE_F64 = 0, 1, 2, 3
 SEM_CPU_EAGER, SEM_DEVICE_EAGER = 0, 1
@@ -27,6 +27,7 @@ EXPORTS = (
     "fq_group_fwd",
     "fq_mx_fwd", "fq_mx_export",
     "fq_mx_gemm",
+    "fq_mx_fwd_rot", "fq_mx_export_rot", "fq_block_rotate",
 )
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
@@ -134,6 +135,12 @@ def _bind(L):
     L.fq_mx_fwd.restype = i32
     L.fq_mx_export.argtypes = [vp, vp, vp, i64, i64, i32, i32, vp]
     L.fq_mx_export.restype = i32
+    L.fq_mx_fwd_rot.argtypes = [vp, vp, i64, i64, i32, i32, vp]
+    L.fq_mx_fwd_rot.restype = i32
+    L.fq_mx_export_rot.argtypes = [vp, vp, vp, i64, i64, i32, i32, vp]
+    L.fq_mx_export_rot.restype = i32
+    L.fq_block_rotate.argtypes = [vp, vp, i64, i64, i32, vp]
+    L.fq_block_rotate.restype = i32
     L.fq_mx_gemm.argtypes = [vp, vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp]
     L.fq_mx_gemm.restype = i32
     return L

@@ -123,3 +123,52 @@ def _(x, fmt):
     lead, cols = tuple(x.shape[:-1]), x.shape[-1]
     return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
             x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))
+
+
+# The block-Hadamard rotation (ops.mx_rotate): R is symmetric and its own inverse, so the gradient is the same op on the gradient
+@torch.library.custom_op("llmqat_amd::mx_block_rotate", mutates_args=(), device_types="cuda")
+def mx_block_rotate_op(x: torch.Tensor) -> torch.Tensor:
+    return ops.mx_rotate(x)
+
+
+@mx_block_rotate_op.register_fake
+def _(x):
+    ops.check_mx_rotate(tuple(x.shape))
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+mx_block_rotate_op.register_autograd(lambda ctx, g: mx_block_rotate_op(g))
+
+
+# MX fake quantization of x R in one launch (ops.mx_quantize(rotate=True)); straight-through: grad_x = grad_y R, nothing saved
+@torch.library.custom_op("llmqat_amd::mx_fake_quant_rot", mutates_args=(), device_types="cuda")
+def mx_fake_quant_rot_op(x: torch.Tensor, fmt: str) -> torch.Tensor:
+    return ops.mx_quantize(x, fmt, rotate=True)
+
+
+@mx_fake_quant_rot_op.register_fake
+def _(x, fmt):
+    ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+mx_fake_quant_rot_op.register_autograd(lambda ctx, g: (mx_block_rotate_op(g), None))
+
+
+# ops.mx_export(rotate=True) as an op: (elements, scales) of x R
+@torch.library.custom_op("llmqat_amd::mx_export_rot", mutates_args=(), device_types="cuda")
+def mx_export_rot_op(x: torch.Tensor, fmt: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    e = ops.mx_export(x, fmt, rotate=True)
+    return e.elements, e.scales
+
+
+@mx_export_rot_op.register_fake
+def _(x, fmt):
+    ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_rotate(tuple(x.shape), "mx_export")
+    if fmt not in ops.MX_GEMM_FORMATS:
+        raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
+    lead, cols = tuple(x.shape[:-1]), x.shape[-1]
+    return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
+            x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))

@@ -491,13 +491,16 @@ const MxFmt kMxFmts[5] = {
     {15, 2, -14, 57344.0f, 0x7Bu, 0x80u},   // E5M2
 };
 
-// exp = false: fq_mx_fwd (x -> y); true: fq_mx_export (x -> elems + scales).  Every check comes before any HIP call.
-int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
+// exp = false: fq_mx_fwd (x -> y); true: fq_mx_export (x -> elems + scales).  rot: the *_rot forms (x R is quantized); only_rot:
+// fq_block_rotate (x -> y = x R, no format).  Every check comes before any HIP call.
+int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_t rows, int64_t cols, int fmt, int dtype, void* stream,
+             bool rot = false, bool only_rot = false) {
     if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
     if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
-    if (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
+    if (!only_rot && (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2)) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
     if (exp && (fmt == FQ_MX_FP6_E2M3 || fmt == FQ_MX_FP6_E3M2)) return fail(FQ_ERR_ARG, "FP6 formats have no export packing");
     if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
+    if (rot && cols % MX_ROT_RUN != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the %d-element rotation run", (long long)cols, MX_ROT_RUN);
     if (cols % 32 != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the 32-element MX block", (long long)cols);
     if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
     if (rows == 0 || cols == 0) return ok();
@@ -509,8 +512,16 @@ int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_
     const int64_t nvec = rows * cols * es / 16;    // cols % 32 == 0: whole 16-byte vectors, whole blocks
     if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
     MxArgs a{x, y, (uint8_t*)elems, (uint8_t*)scales, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
-    const int kind = !exp ? MX_FWD : (fmt == FQ_MX_FP4_E2M1 ? MX_EXP4 : MX_EXP8);
+    const int kind = only_rot ? MX_ROT : !exp ? MX_FWD : (fmt == FQ_MX_FP4_E2M1 ? MX_EXP4 : MX_EXP8);
     hipStream_t st = (hipStream_t)stream;
+    if (rot) {   // cols % 64 == 0: whole rotation runs
+        const MxFmt& f = kMxFmts[only_rot ? 0 : fmt];
+        switch (dtype) {
+            case FQ_DTYPE_F32: return launch_mx_rot<F32>(kind, a, f, st);
+            case FQ_DTYPE_F16: return launch_mx_rot<F16>(kind, a, f, st);
+            default: return launch_mx_rot<BF16>(kind, a, f, st);
+        }
+    }
     switch (dtype) {
         case FQ_DTYPE_F32: return launch_mx<F32>(kind, a, kMxFmts[fmt], st);
         case FQ_DTYPE_F16: return launch_mx<F16>(kind, a, kMxFmts[fmt], st);
@@ -525,6 +536,18 @@ FQ_API int fq_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fmt
 
 FQ_API int fq_mx_export(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
     return mx_entry(true, x, nullptr, elems_out, scales_out, rows, cols, fmt, dtype, stream);
+}
+
+FQ_API int fq_mx_fwd_rot(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
+    return mx_entry(false, x, y, nullptr, nullptr, rows, cols, fmt, dtype, stream, true);
+}
+
+FQ_API int fq_mx_export_rot(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
+    return mx_entry(true, x, nullptr, elems_out, scales_out, rows, cols, fmt, dtype, stream, true);
+}
+
+FQ_API int fq_block_rotate(const void* x, void* y, int64_t rows, int64_t cols, int dtype, void* stream) {
+    return mx_entry(false, x, y, nullptr, nullptr, rows, cols, 0, dtype, stream, true, true);
 }
 
 // Every check comes before any HIP call.

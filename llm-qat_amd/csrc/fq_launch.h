@@ -179,8 +179,9 @@ template <int DT> FQ_HIDDEN int launch_sym_autocast(bool wide, RowArgs a, void* 
 // per group (4 .. 64); autocast = 1: Sym under autocast with the result rounded once to the tensor dtype (16-bit tensors)
 template <int DT> FQ_HIDDEN int launch_group(bool asym, bool fast, int autocast, RowArgs a, int gv, hipStream_t st);
 // MX block-scaled forward / export (fq_mx.h / fq_mx.hip): blocks of 32 consecutive elements, the element format in MxFmt
-enum : int { MX_FWD = 0, MX_EXP4 = 1, MX_EXP8 = 2 };
+enum : int { MX_FWD = 0, MX_EXP4 = 1, MX_EXP8 = 2, MX_ROT = 3 };   // MX_ROT: the 64-wide block-Hadamard rotation alone (rotated launches only)
 constexpr int MX_TPB = 256, MX_VPT = 4;   // threads per workgroup, 16-byte vectors in flight per lane
+constexpr int MX_ROT_RUN = 64;            // elements of one rotation run (H64 / 8): two MX blocks
 struct MxFmt {
     int emax;          // exponent of the element format's largest binade (floor(log2 max-normal))
     int mbits;         // mantissa bits
@@ -192,13 +193,16 @@ struct MxFmt {
 
 struct MxArgs {
     const void* x;
-    void* y;             // MX_FWD
+    void* y;             // MX_FWD / MX_ROT
     uint8_t* elems;      // MX_EXP4 / MX_EXP8
     uint8_t* scales;     // MX_EXP4 / MX_EXP8
     int64_t nvec;        // 16-byte vectors of the tensor: a multiple of the block's vector count
     int ntl;             // non-temporal loads (the tensor is larger than NT_LOAD_MIN_BYTES): uniform over the launch
 };
 template <int DT> FQ_HIDDEN int launch_mx(int kind, MxArgs a, MxFmt f, hipStream_t st);
+// the same kinds on x R (R block-diagonal along the last dimension, blocks H64 / 8), and MX_ROT: y = x R alone (f unused); nvec is a
+// multiple of the run's vector count
+template <int DT> FQ_HIDDEN int launch_mx_rot(int kind, MxArgs a, MxFmt f, hipStream_t st);
 // MX block-scaled GEMM (fq_mx_gemm.h / fq_mx_gemm.hip): out[m, n] = sum_k A[m, k] * W[n, k] over two MX exports
 struct MxGemmArgs {
     const uint8_t* we;   // W: [N, K] element codes, E8M0 scales [N, K / 32]

@@ -12,8 +12,18 @@
 //   amax = max|v|; a NaN / Inf in the block makes every output NaN (export: scale 0xFF, codes 0).
 //   E = clamp(floor(log2 amax) - emax, -127, 127) (amax == 0: E = -127); t = v * 2^-E (exact); q = t rounded to nearest-even onto the
 //   element grid (normals and subnormals), saturated to +-max-normal, sign kept; y = q * 2^E (exact in fp32), rounded once to the dtype.
-// The format is a kernel argument (MxFmt): the rounding chain is the same for all five, so only the dtype and the output kind are
-// template parameters.
+// The format is a kernel argument (MxFmt): the rounding chain is the same for all five, so only the dtype, the output kind and the
+// rotation are template parameters.
+//
+// ROT: the kernel quantizes x R instead of x.  R is block-diagonal along the last dimension with blocks H64 / 8
+// (H64 the 64 x 64 Sylvester Hadamard matrix): orthonormal, symmetric, its own inverse, entries +-0.125.  A run of 64 elements is 8
+// consecutive vectors of a 16-bit tensor (16 of an fp32 one), held by 8 (16) lanes of one DPP row.  The run is widened to fp32, the
+// butterfly stages 1, 2, 4, .. 32 on the element index run in that order -- the strides below a vector in the lane's registers, the others
+// as lane exchanges -- and the result is multiplied by 0.125f; the MX chain then runs on these fp32 values (amax from fp32 bits, sign from
+// the rotated value, a sum that overflows makes a NaN block).  No LDS, no barrier.  KIND = MX_ROT rounds x R once to the dtype.
+// The exchanges need the lane that holds vector w ^ 1, w ^ 2, w ^ 4 (w ^ 8), and DPP has lane ^ 1, lane ^ 2 (quad_perm), lane ^ 7
+// (row_half_mirror) and lane ^ 15 (row_mirror) but no lane ^ 4 or lane ^ 8.  So lane l of a run holds vector w = mx_rot_slot(l), chosen so
+// that the mirrors flip exactly one bit of w; the run's lanes still cover the same aligned 128 (256) bytes.
 #pragma once
 #include "fq_group.h"
 
@@ -53,16 +63,55 @@ __device__ __forceinline__ uint32_t mx_code(float v, float r, int sb_rel, const 
     return (as_u(v) >> 31) ? c | f.signbit : c;
 }
 
-template <int DT, int KIND, int VPT>
+// vector (within the workgroup's slot) of lane t under ROT: bit 2 of w is t's, bits 0 and 1 are t's xor bit 2 -> t ^ 7 is w ^ 4 and
+// t ^ 1, t ^ 2 are w ^ 1, w ^ 2; fp32 (16 lanes per run): bit 3 is t's and bit 2 is xored with it -> t ^ 15 is w ^ 8, t ^ 7 still w ^ 4
+template <int EPV> __device__ __forceinline__ uint32_t mx_rot_slot(uint32_t t) {
+    uint32_t w = t ^ (((t >> 2) & 1u) * 3u);
+    if constexpr (EPV == 4) w ^= ((t >> 3) & 1u) * 4u;
+    return w;
+}
+
+// one exchange stage: the lane whose vector has the stage's bit clear takes v + partner, the other partner - v = partner + (-v), so both
+// are one IEEE add of the partner's value (DPP) and the lane's own value with its sign flipped by sgn (0 or 0x80000000)
+template <int CTRL, int EPV> __device__ __forceinline__ void mx_rot_exchange(float (&v)[EPV], uint32_t sgn) {
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) v[e] = as_f(dpp<CTRL>(as_u(v[e]))) + as_f(as_u(v[e]) ^ sgn);
+}
+
+// v: the lane's EPV consecutive elements of a run, w: the lane's vector index (only its low bits matter) -> the lane's elements of
+// (run) H64 * 0.125, every add / subtract one fp32 operation, stages in the order of the definition
+template <int EPV> __device__ __forceinline__ void mx_rotate(float (&v)[EPV], uint32_t w) {
+#pragma unroll
+    for (int s = 1; s < EPV; s *= 2) {
+#pragma unroll
+        for (int j = 0; j < EPV; ++j) {
+            if (!(j & s)) {
+                const float p = v[j], q = v[j + s];
+                v[j] = p + q;
+                v[j + s] = p - q;
+            }
+        }
+    }
+    mx_rot_exchange<0xB1, EPV>(v, (w & 1u) << 31);            // quad_perm:[1,0,3,2]: w ^ 1
+    mx_rot_exchange<0x4E, EPV>(v, (w & 2u) << 30);            // quad_perm:[2,3,0,1]: w ^ 2
+    mx_rot_exchange<0x141, EPV>(v, (w & 4u) << 29);           // row_half_mirror:     w ^ 4
+    if constexpr (EPV == 4) mx_rot_exchange<0x140, EPV>(v, (w & 8u) << 28);   // row_mirror: w ^ 8
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) v[e] = v[e] * 0.125f;
+}
+
+template <int DT, int KIND, int VPT, bool ROT>
 __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE;     // elements per vector
     constexpr int BV = 32 / EPV;           // vectors per block
-    const int64_t base = (int64_t)blockIdx.x * (MX_TPB * VPT) + threadIdx.x;
+    static_assert(ROT || KIND != MX_ROT, "the rotation alone is a rotated launch");
+    const uint32_t slot = ROT ? mx_rot_slot<EPV>(threadIdx.x) : threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * (MX_TPB * VPT) + slot;
     const uint4* __restrict__ xv = (const uint4*)a.x;
 
     // Out-of-range slots re-load the last vector: nvec is a multiple of BV and segments are BV-aligned, so such a slot's whole block
-    // is out of range and is never stored.
+    // is out of range and is never stored.  (ROT: nvec is a multiple of the run's vector count and runs are aligned, likewise.)
     uint4 r[VPT];
     if (a.ntl) {
 #pragma unroll
@@ -82,23 +131,55 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
         const int64_t v = base + i * MX_TPB;
+        const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
+        float xr[ROT ? EPV : 1];   // ROT: the lane's elements of x R
         uint32_t acc = 0;
-        acc = T::absmax_acc(acc, r[i].x);
-        acc = T::absmax_acc(acc, r[i].y);
-        acc = T::absmax_acc(acc, r[i].z);
-        acc = T::absmax_acc(acc, r[i].w);
-        const uint32_t ab = group_reduce<OpMaxU>(T::absmax_finish(acc), BV);   // fp32 bits of the block's amax (NaN sorts above Inf)
-        const bool bad = ab >= 0x7F800000u;                                     // a NaN or Inf in the block
+        if constexpr (ROT) {
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                float fd[T::EPD];
+                T::unpack(w[d], fd);
+#pragma unroll
+                for (int k = 0; k < T::EPD; ++k) xr[d * T::EPD + k] = fd[k];
+            }
+            mx_rotate<EPV>(xr, slot);
+            if constexpr (KIND == MX_ROT) {
+                uint32_t o[4];
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    float fd[T::EPD];
+#pragma unroll
+                    for (int k = 0; k < T::EPD; ++k) fd[k] = xr[d * T::EPD + k];
+                    o[d] = T::pack(fd);
+                }
+                if (v < a.nvec) st16<true>(&((uint4*)a.y)[v], make_uint4(o[0], o[1], o[2], o[3]));
+                continue;
+            }
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) acc = Ty<F32>::absmax_acc(acc, as_u(xr[e]));
+        } else {
+            acc = T::absmax_acc(acc, r[i].x);
+            acc = T::absmax_acc(acc, r[i].y);
+            acc = T::absmax_acc(acc, r[i].z);
+            acc = T::absmax_acc(acc, r[i].w);
+            acc = T::absmax_finish(acc);
+        }
+        const uint32_t ab = group_reduce<OpMaxU>(acc, BV);   // fp32 bits of the block's amax (NaN sorts above Inf)
+        const bool bad = ab >= 0x7F800000u;                   // a NaN or Inf in the block
         const int E = mx_shared_exp(ab, f.emax);
         const int nE = -E, yk = E - 127 - f.mbits;
         const float maxx = __builtin_amdgcn_ldexpf(f.maxnorm, E);
-        const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
         if constexpr (KIND == MX_FWD) {
             uint32_t o[4];
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 float fd[T::EPD];
-                T::unpack(w[d], fd);
+                if constexpr (ROT) {
+#pragma unroll
+                    for (int k = 0; k < T::EPD; ++k) fd[k] = xr[d * T::EPD + k];
+                } else {
+                    T::unpack(w[d], fd);
+                }
 #pragma unroll
                 for (int k = 0; k < T::EPD; ++k) {
                     int sb;
@@ -113,7 +194,12 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 float fd[T::EPD];
-                T::unpack(w[d], fd);
+                if constexpr (ROT) {
+#pragma unroll
+                    for (int k = 0; k < T::EPD; ++k) fd[k] = xr[d * T::EPD + k];
+                } else {
+                    T::unpack(w[d], fd);
+                }
 #pragma unroll
                 for (int k = 0; k < T::EPD; ++k) {
                     int sb;
@@ -146,9 +232,9 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
     }
 }
 
-template <int DT, int KIND> static void launch_mx_kind(const MxArgs& a, const MxFmt& f, hipStream_t st) {
+template <int DT, int KIND, bool ROT = false> static void launch_mx_kind(const MxArgs& a, const MxFmt& f, hipStream_t st) {
     const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
-    FQ_LAUNCHK((mx_kernel<DT, KIND, MX_VPT>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a, f);
+    FQ_LAUNCHK((mx_kernel<DT, KIND, MX_VPT, ROT>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a, f);
 }
 
 // kind: MX_FWD / MX_EXP4 / MX_EXP8; a and f validated by fq_mx_fwd / fq_mx_export (nvec > 0, grid within limits)
@@ -160,6 +246,18 @@ template <int DT> int launch_mx(int kind, MxArgs a, MxFmt f, hipStream_t st) {
     return launch_result();
 }
 
-#define FQ_INSTANTIATE_MX(DT) template int launch_mx<DT>(int, MxArgs, MxFmt, hipStream_t);
+// kind: MX_FWD / MX_EXP4 / MX_EXP8 on x R, or MX_ROT; validated by fq_mx_fwd_rot / fq_mx_export_rot / fq_block_rotate
+template <int DT> int launch_mx_rot(int kind, MxArgs a, MxFmt f, hipStream_t st) {
+    begin_launches();
+    if (kind == MX_FWD) launch_mx_kind<DT, MX_FWD, true>(a, f, st);
+    else if (kind == MX_EXP4) launch_mx_kind<DT, MX_EXP4, true>(a, f, st);
+    else if (kind == MX_EXP8) launch_mx_kind<DT, MX_EXP8, true>(a, f, st);
+    else launch_mx_kind<DT, MX_ROT, true>(a, f, st);
+    return launch_result();
+}
+
+#define FQ_INSTANTIATE_MX(DT)                                              \
+    template int launch_mx<DT>(int, MxArgs, MxFmt, hipStream_t); \
+    template int launch_mx_rot<DT>(int, MxArgs, MxFmt, hipStream_t);
 
 }  // namespace fq

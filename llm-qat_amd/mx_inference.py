@@ -23,9 +23,12 @@ def _why_not(layer):
 
 class MXLinear(nn.Module):
     """y = mx_matmul(mx_export(x, act_format), W) (+ bias): two launches, W held as `weight_elements` / `weight_scales` buffers (the
-    ops.MXExport of the trained weight), no bf16 weight.  Inference only: not differentiable."""
+    ops.MXExport of the trained weight), no bf16 weight.  Inference only: not differentiable.
+    rotate=True: the buffers hold the export of W R and the activation's export launch rotates x, so the product
+    is (x R)(W R)^T -- still two launches, the same GEMM.  A constructor attribute like the formats: it is not in the state_dict."""
 
-    def __init__(self, in_features, out_features, weight_format="mxfp4", act_format="mxfp8_e4m3", bias=False, device=None, dtype=None):
+    def __init__(self, in_features, out_features, weight_format="mxfp4", act_format="mxfp8_e4m3", bias=False, device=None, dtype=None,
+                 rotate=False):
         super().__init__()
         for what, fmt in (("weight_format", weight_format), ("act_format", act_format)):
             if fmt not in ops.MX_GEMM_FORMATS:
@@ -34,6 +37,7 @@ class MXLinear(nn.Module):
             raise ValueError(f"in_features={in_features} is not a positive multiple of {ops.MX_GEMM_KSTEP}, the K step of the MX GEMM kernel")
         self.in_features, self.out_features = in_features, out_features
         self.weight_format, self.act_format = weight_format, act_format
+        self.rotate = bool(rotate)   # (in_features % 128 == 0 holds whole 64-element rotation runs)
         ebytes = in_features // 2 if weight_format == "mxfp4" else in_features
         self.register_buffer("weight_elements", torch.zeros(out_features, ebytes, dtype=torch.uint8, device=device))
         self.register_buffer("weight_scales", torch.zeros(out_features, in_features // ops.MX_BLOCK, dtype=torch.uint8, device=device))
@@ -48,9 +52,10 @@ class MXLinear(nn.Module):
         if why is not None:
             raise ValueError(f"MXLinear.from_quantize_linear: {why}")
         has_bias = getattr(layer, "bias", None) is not None
+        rotate = bool(getattr(layer, "mx_rotate", False))
         m = cls(layer.in_features, layer.out_features, layer.weight_format, layer.act_format, bias=has_bias, device=layer.weight.device,
-                dtype=layer.weight.dtype)
-        e = layer.export_weight() if hasattr(layer, "export_weight") else ops.mx_export(layer.weight.detach(), layer.weight_format)
+                dtype=layer.weight.dtype, rotate=rotate)
+        e = layer.export_weight() if hasattr(layer, "export_weight") else ops.mx_export(layer.weight.detach(), layer.weight_format, rotate=rotate)
         m.weight_elements.copy_(e.elements)
         m.weight_scales.copy_(e.scales)
         if has_bias:
@@ -60,22 +65,22 @@ class MXLinear(nn.Module):
     def weight_export(self):
         """the weight as an ops.MXExport (shares the buffers)"""
         return ops.MXExport(self.weight_elements, self.weight_scales, self.weight_format, (self.out_features, self.in_features),
-                            torch.float32 if self.bias is None else self.bias.dtype)
+                            torch.float32 if self.bias is None else self.bias.dtype, self.rotate)
 
     def forward(self, x):
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("MXLinear is an inference module and is not differentiable: call it under torch.no_grad() or on a detached input")
         if torch.compiler.is_compiling():
-            ae, asc = compiled.mx_export_op(x, self.act_format)
+            ae, asc = (compiled.mx_export_rot_op if self.rotate else compiled.mx_export_op)(x, self.act_format)
             y = compiled.mx_matmul_op(ae, asc, self.act_format, self.weight_elements, self.weight_scales, self.weight_format, list(x.shape), x.dtype)
         else:
-            a = ops.mx_export(x, self.act_format)
+            a = ops.mx_export(x, self.act_format, rotate=self.rotate)
             y = ops.mx_matmul_tensors(a.elements, a.scales, a.fmt, self.weight_elements, self.weight_scales, self.weight_format, a.shape, x.dtype)
         return y if self.bias is None else y + self.bias
 
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, weight_format={self.weight_format!r}, "
-                f"act_format={self.act_format!r}, bias={self.bias is not None}")
+                f"act_format={self.act_format!r}, bias={self.bias is not None}" + (", rotate=True" if self.rotate else ""))
 
 
 def convert_to_mx_inference(model):

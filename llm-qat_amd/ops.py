@@ -1062,7 +1062,12 @@ def sym_row_scales(x, num_bits, layerwise=False, autocast=None):
 MX_FORMATS = {"mxfp4": _lib.MX_FP4_E2M1, "mxfp6_e2m3": _lib.MX_FP6_E2M3, "mxfp6_e3m2": _lib.MX_FP6_E3M2,
               "mxfp8_e4m3": _lib.MX_FP8_E4M3, "mxfp8_e5m2": _lib.MX_FP8_E5M2}
 MX_BLOCK = 32
-mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm_launch": 0, "mx_gemm_skinny": 0, "mx_gemm_tiled": 0}
+# rotate=True: the same launches quantize x R, R block-diagonal along the last dimension with blocks H64 / 8 (the
+# 64 x 64 Sylvester Hadamard matrix, normalised: orthonormal, symmetric, its own inverse).  Rotating both operands of a product along K
+# leaves the product unchanged and spreads an outlier over its 64-element run before the block scales are taken.
+MX_ROTATE = 64
+mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm_launch": 0, "mx_gemm_skinny": 0, "mx_gemm_tiled": 0,
+             "mx_rotate_launch": 0}
 
 
 def check_mx(shape, fmt):
@@ -1078,8 +1083,18 @@ def check_mx(shape, fmt):
     return code
 
 
-def _mx_input(x, fmt, what):
-    code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) else None
+def check_mx_rotate(shape, what="mx_rotate"):
+    """The shape check of every rotated MX call: ValueError unless the last dimension is a multiple of 64."""
+    if len(shape) == 0:
+        raise ValueError(f"{what}: the rotation takes tensors with at least one dimension")
+    if shape[-1] % MX_ROTATE:
+        raise ValueError(f"{what}: the block-Hadamard rotation needs a last dimension that is a multiple of {MX_ROTATE}, got {shape[-1]}")
+
+
+def _mx_input(x, fmt, what, rotate=False):
+    code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) and fmt is not None else None
+    if rotate and isinstance(x, torch.Tensor):
+        check_mx_rotate(tuple(x.shape), what)
     dt = _prep(x, what)
     if dt == _lib.DTYPE_F64:
         raise NotImplementedError(f"{what}: float64 is not served by the MX formats (float32, bfloat16, float16 are)")
@@ -1089,16 +1104,32 @@ def _mx_input(x, fmt, what):
     return x, code, dt
 
 
-def mx_quantize(x, fmt):
-    """MX fake quantization of x (same shape and dtype): each block of 32 elements along the last dimension scaled by its shared power
-    of two, rounded onto the element grid of `fmt` and saturated, then scaled back and rounded once to x's dtype."""
-    x, code, dt = _mx_input(x, fmt, "mx_quantize")
+def mx_rotate(x):
+    """x R (same shape and dtype): every run of 64 elements along the last dimension times H64 / 8, in fp32, rounded once to x's dtype.
+    R is its own inverse and its own transpose, so this is also the backward of itself.  One launch (fq_block_rotate)."""
+    x, _, dt = _mx_input(x, None, "mx_rotate", True)
     y = torch.empty_like(x, memory_format=torch.contiguous_format)
     if x.numel():
         cols = x.shape[-1]
         rows = x.numel() // cols
         L = _lib.lib()
-        _lib.check(_on_device(x, lambda st: L.fq_mx_fwd(x.data_ptr(), y.data_ptr(), rows, cols, code, dt, st)), "mx_quantize")
+        _lib.check(_on_device(x, lambda st: L.fq_block_rotate(x.data_ptr(), y.data_ptr(), rows, cols, dt, st)), "mx_rotate")
+        mx_counts["mx_rotate_launch"] += 1
+    return y
+
+
+def mx_quantize(x, fmt, rotate=False):
+    """MX fake quantization of x (same shape and dtype): each block of 32 elements along the last dimension scaled by its shared power
+    of two, rounded onto the element grid of `fmt` and saturated, then scaled back and rounded once to x's dtype.  rotate=True: of the
+    fp32 values of x R (mx_rotate) instead, in the same single launch; the result is in the rotated basis."""
+    x, code, dt = _mx_input(x, fmt, "mx_quantize", rotate)
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    if x.numel():
+        cols = x.shape[-1]
+        rows = x.numel() // cols
+        L = _lib.lib()
+        fwd = L.fq_mx_fwd_rot if rotate else L.fq_mx_fwd
+        _lib.check(_on_device(x, lambda st: fwd(x.data_ptr(), y.data_ptr(), rows, cols, code, dt, st)), "mx_quantize")
         mx_counts["mx_launch"] += 1
     return y
 
@@ -1112,14 +1143,16 @@ class MXExport:
       elements  uint8 [..., cols / 2] (mxfp4: element 2k in the low nibble of byte k) or [..., cols] (mxfp8_*: float8_e4m3fn / float8_e5m2
                 bit patterns)
       scales    uint8 [..., cols / 32]: one E8M0 byte (E + 127) per block; 0xFF marks a block that held a NaN or Inf (its codes are 0)
-    dequantize() gives back mx_quantize(x, fmt) bit for bit (signed zeros included; NaN blocks as NaN), in plain torch ops."""
-    __slots__ = ("elements", "scales", "fmt", "shape", "dtype")
+      rotated   the export is of x R (mx_export(..., rotate=True)): its values live in the rotated basis
+    dequantize() gives back mx_quantize(x, fmt, rotate=rotated) bit for bit (signed zeros included; NaN blocks as NaN), in plain torch ops."""
+    __slots__ = ("elements", "scales", "fmt", "shape", "dtype", "rotated")
 
-    def __init__(self, elements, scales, fmt, shape, dtype):
+    def __init__(self, elements, scales, fmt, shape, dtype, rotated=False):
         self.elements, self.scales, self.fmt, self.shape, self.dtype = elements, scales, fmt, tuple(shape), dtype
+        self.rotated = bool(rotated)
 
     def __repr__(self):
-        return f"MXExport(fmt={self.fmt!r}, shape={self.shape}, dtype={self.dtype})"
+        return f"MXExport(fmt={self.fmt!r}, shape={self.shape}, dtype={self.dtype}{', rotated=True' if self.rotated else ''})"
 
     def dequantize(self):
         e = self.elements
@@ -1139,13 +1172,13 @@ class MXExport:
         return y.reshape(self.shape).to(self.dtype)
 
 
-def mx_export(x, fmt):
-    """-> MXExport(elements, scales, fmt, shape, dtype): the codes and E8M0 scales of mx_quantize(x, fmt).  mxfp4 and mxfp8_* only (FP6 has
-    no packing here: ValueError)."""
+def mx_export(x, fmt, rotate=False):
+    """-> MXExport(elements, scales, fmt, shape, dtype, rotated): the codes and E8M0 scales of mx_quantize(x, fmt, rotate).  mxfp4 and
+    mxfp8_* only (FP6 has no packing here: ValueError)."""
     code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) else None
     if code in (_lib.MX_FP6_E2M3, _lib.MX_FP6_E3M2):
         raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
-    x, code, dt = _mx_input(x, fmt, "mx_export")
+    x, code, dt = _mx_input(x, fmt, "mx_export", rotate)
     cols = x.shape[-1]
     lead = tuple(x.shape[:-1])
     elems = torch.empty(lead + (cols // 2 if code == _lib.MX_FP4_E2M1 else cols,), dtype=torch.uint8, device=x.device)
@@ -1153,10 +1186,10 @@ def mx_export(x, fmt):
     if x.numel():
         rows = x.numel() // cols
         L = _lib.lib()
-        _lib.check(_on_device(x, lambda st: L.fq_mx_export(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, st)),
-                   "mx_export")
+        exp = L.fq_mx_export_rot if rotate else L.fq_mx_export
+        _lib.check(_on_device(x, lambda st: exp(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, st)), "mx_export")
         mx_counts["mx_export_launch"] += 1
-    return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype)
+    return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype, rotate)
 
 
 # ---- MX block-scaled GEMM: the exported codes on gfx950's scaled matrix instruction (fq_mx_gemm) ------------------
@@ -1229,9 +1262,12 @@ def mx_matmul(a, w, out_dtype=None):
     """out[..., n] = sum_k a[..., k] * w[n, k] over two MXExports, on the block-scaled matrix instruction: the value of
     a.dequantize().double() @ w.dequantize().double().T up to the fp32 accumulation of the matrix core, rounded once to out_dtype
     (default a.dtype).  a: [..., K], w: [N, K], each mxfp4 / mxfp8_e4m3 / mxfp8_e5m2; K a multiple of 128.  An 0xFF (NaN) scale block in a
-    row of a / w makes that output row / column NaN."""
+    row of a / w makes that output row / column NaN.  Both operands rotated or neither (ValueError): (a R)(w R)^T = a w^T, a R w^T is not."""
     if not isinstance(a, MXExport) or not isinstance(w, MXExport):
         raise TypeError("mx_matmul: a and w are MXExport objects (ops.mx_export)")
+    if a.rotated != w.rotated:
+        raise ValueError(f"mx_matmul: a is {'rotated' if a.rotated else 'not rotated'} and w is {'rotated' if w.rotated else 'not rotated'}: "
+                         "the product only equals the unrotated one when both operands carry the same rotation")
     out_dtype = a.dtype if out_dtype is None else out_dtype
     check_mx_matmul(a.shape, a.fmt, w.shape, w.fmt, out_dtype)
     return mx_matmul_tensors(a.elements, a.scales, a.fmt, w.elements, w.scales.reshape(w.shape[0], -1), w.fmt, a.shape, out_dtype)

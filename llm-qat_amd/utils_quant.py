@@ -110,6 +110,8 @@ def stats(reset=False):
       mx_launch / mx_export_launch / mx_copy_route
                                          MX block-scaled forwards (ops.mx_quantize) and exports (ops.mx_export) launched, and the inputs of
                                          either that took one .contiguous() copy first (non-contiguous or misaligned)
+      mx_rotate_launch                   block-Hadamard rotations launched on their own (ops.mx_rotate, block_rotate, the backward of the rotated
+                                         MX quantizer); the fused rotated forms count as mx_launch / mx_export_launch
       mx_gemm_launch / mx_gemm_skinny / mx_gemm_tiled
                                          MX block-scaled GEMMs (ops.mx_matmul, MXLinear) launched, and which kernel served them (M <= 32: skinny)
       cpp_pair_forward / cpp_weight_forward / cpp_pair_backward / cpp_one_backward / cpp_slow_backward
@@ -437,12 +439,56 @@ class _MXQuantizer(torch.autograd.Function):
         return grad_output, None
 
 
-def mx_quantize(x, fmt):
+class _BlockRotate(torch.autograd.Function):
+    """x R (ops.mx_rotate): R is symmetric and its own inverse, so the backward is the forward on the gradient.  Nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.set_materialize_grads(False)
+        return ops.mx_rotate(x)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return None if grad_output is None else _BlockRotate.apply(grad_output)
+
+
+class _MXRotQuantizer(torch.autograd.Function):
+    """MX fake quantization of x R in one launch (ops.mx_quantize(rotate=True)).  Straight-through over the quantizer only: the rotation
+    is a linear map with its own gradient, so grad_x = grad_y R -- one rotate launch, nothing saved."""
+
+    @staticmethod
+    def forward(ctx, x, fmt):
+        ctx.set_materialize_grads(False)
+        return ops.mx_quantize(x, fmt, rotate=True)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return (None if grad_output is None else _BlockRotate.apply(grad_output)), None
+
+
+def block_rotate(x):
+    """x R: every run of 64 consecutive elements of the last dimension (a multiple of 64) times H64 / 8, the normalised 64 x 64 Sylvester
+    Hadamard matrix; fp32 arithmetic, rounded once to x's dtype.  Differentiable; its backward is itself."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"block_rotate: expected a torch.Tensor, got {type(x).__name__}")
+    ops.check_mx_rotate(tuple(x.shape), "block_rotate")
+    if torch.compiler.is_compiling():
+        return compiled.mx_block_rotate_op(x)
+    return _BlockRotate.apply(x)
+
+
+def mx_quantize(x, fmt, rotate=False):
     """OCP MX fake quantization ("mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8_e4m3", "mxfp8_e5m2"): every 32 consecutive elements of the
-    last dimension share one power-of-two scale.  Same shape and dtype as x; the gradient is the identity (straight-through)."""
+    last dimension share one power-of-two scale.  Same shape and dtype as x; the gradient is the identity (straight-through).
+    rotate=True quantizes x R (block_rotate) in the same launch; the result is in the rotated basis and the gradient is grad R."""
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
     ops.check_mx(tuple(x.shape), fmt)
+    if rotate:
+        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
+        if torch.compiler.is_compiling():
+            return compiled.mx_fake_quant_rot_op(x, fmt)
+        return _MXRotQuantizer.apply(x, fmt)
     if torch.compiler.is_compiling():
         return compiled.mx_fake_quant_op(x, fmt)
     return _MXQuantizer.apply(x, fmt)
@@ -461,6 +507,19 @@ def default_mx_formats(weight=None, act=None):
             raise ValueError(f"unknown MX format {f!r}: one of {', '.join(ops.MX_FORMATS)}")
     prev = _DEFAULT_MX
     _DEFAULT_MX = (weight, act)
+    return prev
+
+
+_DEFAULT_MX_ROTATE = False   # mx_rotate of QuantizeLinears constructed without an explicit one
+
+
+def default_mx_rotate(flag):
+    """Whether the QuantizeLinears constructed from now on whose two operands both resolve to an MX format, and whose in_features is a
+    multiple of 64, rotate their operands (mx_rotate=True) when their own mx_rotate is not given.  Layers the rotation does not apply to
+    stay unrotated.  Lets unchanged model code train with the rotation.  -> the previous flag."""
+    global _DEFAULT_MX_ROTATE
+    prev = _DEFAULT_MX_ROTATE
+    _DEFAULT_MX_ROTATE = bool(flag)
     return prev
 
 
@@ -1228,9 +1287,10 @@ class QuantizeLinear(nn.Linear):
     act_group_size = None
     weight_format = None       # MX formats (ops.MX_FORMATS): replace that operand's integer quantizer
     act_format = None
+    mx_rotate = False          # both operands are rotated along K before they are quantized: F.linear(Q(x R), Q(W R)) (a plain attribute)
 
     def __init__(self, *kargs, symmetric=True, bias=False, w_bits=32, a_bits=32, act_layerwise=False,
-                 weight_layerwise=False, weight_group_size=None, act_group_size=None, weight_format=None, act_format=None):
+                 weight_layerwise=False, weight_group_size=None, act_group_size=None, weight_format=None, act_format=None, mx_rotate=None):
         super().__init__(*kargs, bias=False)  # `bias` is accepted and ignored, as in the reference (:176)
         self.w_bits = w_bits
         self.a_bits = a_bits
@@ -1255,6 +1315,17 @@ class QuantizeLinear(nn.Linear):
         elif ma is not None and a_bits < 32 and act_group_size is None and not act_layerwise:
             self.act_format = ma
             ops.check_mx((self.in_features,), ma)
+        # the rotation: an explicit True needs both operands in an MX format (rotating one alone changes the product) and whole 64-runs;
+        # the process default (default_mx_rotate) applies to the layers that meet both
+        both_mx = self.weight_format is not None and self.act_format is not None
+        if mx_rotate:
+            if not both_mx:
+                raise ValueError("mx_rotate needs both operands in an MX format (weight_format and act_format): (x R)(W R)^T = x W^T only "
+                                 "when both are rotated")
+            ops.check_mx_rotate((self.in_features,), "mx_rotate")
+            self.mx_rotate = True
+        elif mx_rotate is None and _DEFAULT_MX_ROTATE and both_mx and self.in_features % ops.MX_ROTATE == 0:
+            self.mx_rotate = True
         # group sizes: an explicit argument is checked and kept; the process default (default_group_sizes) applies where it means something
         dw, da = _DEFAULT_GROUPS
         if self.weight_format is not None:
@@ -1479,14 +1550,16 @@ class QuantizeLinear(nn.Linear):
         w_bits <= 4, int8 / int16 above) + per-output-channel {s, t2} (ops.QuantExport; `dequantize()` gives back the
         value the forward multiplies with, bit for bit where overflow == 0).  Serves the w_bits >= 3 path (:195-201)."""
         if self.weight_format is not None:   # MX weights: codes + E8M0 scales (ops.MXExport); FP6 has no packing (ValueError)
-            return ops.mx_export(self.weight.detach(), self.weight_format)
+            return ops.mx_export(self.weight.detach(), self.weight_format, rotate=self.mx_rotate)   # rotated: the export of W R
         if not 3 <= self.w_bits < 32:
             raise ValueError(f"export_weight serves 3 <= w_bits < 32 (SymQuantizer weights), this layer has w_bits={self.w_bits}")
         return ops.sym_export(self.weight.detach(), self.w_bits, self.weight_layerwise, container=container, group_size=self.weight_group_size)
 
     def _forward_compiled(self, input_):
         """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
-        if self.weight_format is not None:   # MX: llmqat_amd::mx_fake_quant, identity gradient
+        if self.weight_format is not None and self.mx_rotate:   # llmqat_amd::mx_fake_quant_rot: Q(W R), gradient g R
+            weight = compiled.mx_fake_quant_rot_op(self.weight, self.weight_format)
+        elif self.weight_format is not None:   # MX: llmqat_amd::mx_fake_quant, identity gradient
             weight = compiled.mx_fake_quant_op(self.weight, self.weight_format)
         elif self.w_bits >= 32:
             weight = self.weight
@@ -1500,7 +1573,9 @@ class QuantizeLinear(nn.Linear):
                 absmean = self.weight.abs().mean() if self.weight_layerwise else self.weight.abs().mean(dim=1, keepdim=True)
                 sc = absmean if self.w_bits == 1 else 2 * absmean
             weight = compiled.low_bit_weight_op(self.weight, sc, self.w_bits)
-        if self.act_format is not None:
+        if self.act_format is not None and self.mx_rotate:
+            input_ = compiled.mx_fake_quant_rot_op(input_, self.act_format)
+        elif self.act_format is not None:
             input_ = compiled.mx_fake_quant_op(input_, self.act_format)
         elif 2 < self.a_bits < 32 and self.act_group_size is not None:
             g = self.act_group_size
@@ -1514,7 +1589,13 @@ class QuantizeLinear(nn.Linear):
 
     def _forward_mx(self, input_):
         """an MX layer (eager): one launch per quantized operand forward, none backward (identity gradient).  No operand pair, C++ pair
-        node, weight cache or activation sharing; an operand without a format keeps its integer quantizer (uncached, unshared)."""
+        node, weight cache or activation sharing; an operand without a format keeps its integer quantizer (uncached, unshared).
+        mx_rotate: F.linear(Q(x R), Q(W R)), still one launch per operand forward, and one rotate launch per operand gradient."""
+        if self.mx_rotate:   # both operands have a format (the constructor's check)
+            out = nn.functional.linear(_MXRotQuantizer.apply(input_, self.act_format), _MXRotQuantizer.apply(self.weight, self.weight_format))
+            if self.bias is not None:
+                out += self.bias.view(1, -1).expand_as(out)
+            return out
         if self.weight_format is not None:
             weight = _MXQuantizer.apply(self.weight, self.weight_format)
         elif self.w_bits >= 32:
