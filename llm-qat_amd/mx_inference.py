@@ -23,7 +23,8 @@ def _why_not(layer):
 
 class MXLinear(nn.Module):
     """y = mx_matmul(mx_export(x, act_format), W) (+ bias): two launches, W held as `weight_elements` / `weight_scales` buffers (the
-    ops.MXExport of the trained weight), no bf16 weight.  Inference only: not differentiable.
+    ops.MXExport of the trained weight), no bf16 weight.  Inference only: not differentiable.  The output has x's dtype; the bias is added
+    in that dtype (cast to it when the module's dtype differs).
     rotate=True: the buffers hold the export of W R and the activation's export launch rotates x, so the product
     is (x R)(W R)^T -- still two launches, the same GEMM.  A constructor attribute like the formats: it is not in the state_dict."""
 
@@ -76,7 +77,8 @@ class MXLinear(nn.Module):
         else:
             a = ops.mx_export(x, self.act_format, rotate=self.rotate)
             y = ops.mx_matmul_tensors(a.elements, a.scales, a.fmt, self.weight_elements, self.weight_scales, self.weight_format, a.shape, x.dtype)
-        return y if self.bias is None else y + self.bias
+        # the bias in x's dtype: the output dtype follows x (fp16 + bf16 would promote the sum to fp32)
+        return y if self.bias is None else y + self.bias.to(y.dtype)
 
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, weight_format={self.weight_format!r}, "

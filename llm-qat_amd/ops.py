@@ -1262,7 +1262,10 @@ def mx_matmul(a, w, out_dtype=None):
     """out[..., n] = sum_k a[..., k] * w[n, k] over two MXExports, on the block-scaled matrix instruction: the value of
     a.dequantize().double() @ w.dequantize().double().T up to the fp32 accumulation of the matrix core, rounded once to out_dtype
     (default a.dtype).  a: [..., K], w: [N, K], each mxfp4 / mxfp8_e4m3 / mxfp8_e5m2; K a multiple of 128.  An 0xFF (NaN) scale block in a
-    row of a / w makes that output row / column NaN.  Both operands rotated or neither (ValueError): (a R)(w R)^T = a w^T, a R w^T is not."""
+    row of a / w makes that output row / column NaN.  Both operands rotated or neither (ValueError): (a R)(w R)^T = a w^T, a R w^T is not.
+    The contract covers what mx_export emits: finite element codes and scale bytes 0 .. 254 (byte 0 is 2^-127) or 0xFF.  Measured over
+    every code and byte: a single product outside fp32's normal range comes out rounded once (gradual underflow,
+    +-Inf above the maximum); the FP8 NaN / Inf codes, which mx_export never writes, act as IEEE NaN / +-Inf (Inf x 0 = NaN)."""
     if not isinstance(a, MXExport) or not isinstance(w, MXExport):
         raise TypeError("mx_matmul: a and w are MXExport objects (ops.mx_export)")
     if a.rotated != w.rotated:
