@@ -421,6 +421,33 @@ int fq_mx_export_rot(const void* x, void* elems_out, void* scales_out, int64_t r
 int fq_block_rotate(const void* x, void* y, int64_t rows, int64_t cols, int dtype, void* stream);
 
 /*
+ * ---- Scale rule and saturation-masked straight-through gradient of the MX quantizer (an addition to ABI 7) -------------------------------
+ * FQ_ABI_VERSION stays 7: nothing that existed changes; the entry points above keep their signatures and results.  DESIGN.md section 16.
+ * flags   FQ_MX_FLAG_ROTATE  quantize x R (as the *_rot entry points; cols a multiple of 64)
+ *         FQ_MX_FLAG_CEIL    the no-clip scale rule: with Ef = floor(log2 amax) - emax_elem (unclamped, from the bits of amax), E = Ef + 1 if
+ *                            amax * 2^-Ef > max-normal (an exact comparison of two fp32 values), else Ef; then the clamp to [-127, 127].
+ *                            Everything after E is unchanged, so no element of a finite block saturates.  Without the flag: the rule above.
+ *         any other bit: FQ_ERR_ARG.
+ * fq_mx_fwd_ex     fq_mx_fwd / fq_mx_fwd_rot under the flags (flags = 0 and FQ_MX_FLAG_ROTATE reproduce them byte for byte).  mask_out, if not
+ *                  NULL, receives the saturation bitmap: rows*cols/8 bytes, 16-byte aligned, bit (i & 7) of byte (i >> 3) for flat element i
+ *                  (one block = one little-endian 32-bit word).  The bit is 0 iff saturation changed the element: its value rounded to
+ *                  nearest-even on the unbounded element grid exceeds max-normal in magnitude (FP4: |t| >= 7 is, 6 < |t| < 7 is not, it rounds
+ *                  to 6 either way).  All 32 bits are 1 in NaN / Inf blocks and amax == 0 blocks.  With the rotation the bits are those of x R.
+ * fq_mx_export_ex  fq_mx_export / fq_mx_export_rot under the flags.
+ * fq_mx_ste_bwd    gx[i] = g[i] where the bit is 1, else +0.0: a select on bit patterns (a NaN / Inf g at a masked position gives +0.0).
+ *                  FQ_MX_FLAG_ROTATE: gx = (g masked) R, bit-identical to fq_block_rotate of the masked gradient, in the same launch.  No other
+ *                  flag (FQ_ERR_ARG).  gx == g is served without the rotation and refused with it (FQ_ERR_ARG).  g, mask, gx 16-byte aligned.
+ * mask_out may not be x or y, and mask may not be g or gx (FQ_ERR_ARG).
+ * Status codes and their order as fq_mx_fwd / fq_mx_export, all before any HIP call; 0 without a launch for an empty shape.
+ */
+#define FQ_MX_FLAG_ROTATE 1
+#define FQ_MX_FLAG_CEIL 2
+int fq_mx_fwd_ex(const void* x, void* y, void* mask_out /* NULL: no mask */, int64_t rows, int64_t cols, int fmt, int dtype, int flags,
+                 void* stream);
+int fq_mx_export_ex(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, int flags, void* stream);
+int fq_mx_ste_bwd(const void* g, const void* mask, void* gx, int64_t rows, int64_t cols, int dtype, int flags, void* stream);
+
+/*
  * ---- MX block-scaled GEMM (an addition to ABI 7) ---------------------------------------------------------------------------------------
  * FQ_ABI_VERSION stays 7: nothing that existed changes, and the merged suite pins fq_version() == 7 (tests/test_mx_cpu.py).  A binding that
  * needs this entry point finds out by looking the symbol up.

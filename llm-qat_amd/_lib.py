@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # LLMQAT_AMD_LIB points the loader at another build of the library (A/B runs of kernel variants: tools/ab_bench.sh) -- the product
 # file is never overwritten; fq_build_info() / LIB_PATH say which one is loaded
 LIB_PATH = os.environ.get("LLMQAT_AMD_LIB") or os.path.join(HERE, "libllmqat_fakequant.so")
-ABI_VERSION = 7   # fq_mx_gemm and the rotated MX entry points are additions within 7 (the header says why)
+ABI_VERSION = 7   # fq_mx_gemm, the rotated MX entry points and the *_ex / fq_mx_ste_bwd ones are additions within 7 (the header says why)
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16, DTYPE_F64 = 0, 1, 2, 3
 SEM_CPU_EAGER, SEM_DEVICE_EAGER = 0, 1
@@ -28,6 +28,7 @@ EXPORTS = (
     "fq_mx_fwd", "fq_mx_export",
     "fq_mx_gemm",
     "fq_mx_fwd_rot", "fq_mx_export_rot", "fq_block_rotate",
+    "fq_mx_fwd_ex", "fq_mx_export_ex", "fq_mx_ste_bwd",
 )
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
@@ -55,6 +56,7 @@ class BwdTensorV(ctypes.Structure):  # fq_bwd_tensor_v
 
 
 MX_FP4_E2M1, MX_FP6_E2M3, MX_FP6_E3M2, MX_FP8_E4M3, MX_FP8_E5M2 = 0, 1, 2, 3, 4
+MX_FLAG_ROTATE, MX_FLAG_CEIL = 1, 2   # flags of fq_mx_fwd_ex / fq_mx_export_ex (fq_mx_ste_bwd: the first only)
 BINS_NONE, BINS_INT4, BINS_INT8, BINS_INT16 = 0, 1, 2, 3
 ERR_UNSUPPORTED = -8
 
@@ -141,6 +143,12 @@ def _bind(L):
     L.fq_mx_export_rot.restype = i32
     L.fq_block_rotate.argtypes = [vp, vp, i64, i64, i32, vp]
     L.fq_block_rotate.restype = i32
+    L.fq_mx_fwd_ex.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, vp]
+    L.fq_mx_fwd_ex.restype = i32
+    L.fq_mx_export_ex.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, vp]
+    L.fq_mx_export_ex.restype = i32
+    L.fq_mx_ste_bwd.argtypes = [vp, vp, vp, i64, i64, i32, i32, vp]
+    L.fq_mx_ste_bwd.restype = i32
     L.fq_mx_gemm.argtypes = [vp, vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp]
     L.fq_mx_gemm.restype = i32
     return L

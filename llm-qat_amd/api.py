@@ -4,7 +4,7 @@ from .cpu_tensors import allow_cpu_tensors
 from ._lib import FakeQuantLibraryError
 from .ops import get_semantics, set_semantics
 from .mx_inference import MXLinear, convert_to_mx_inference
-from .utils_quant import (AsymQuantizer, QuantizeLinear, SymQuantizer, conservative, cpp_node, default_group_sizes, default_mx_formats, default_mx_rotate, enable_weight_quant_cache, fuse_low_bit_mean,
+from .utils_quant import (AsymQuantizer, QuantizeLinear, SymQuantizer, conservative, cpp_node, default_group_sizes, default_mx_formats, default_mx_rotate, default_mx_scale_rule, default_mx_ste, enable_weight_quant_cache, fuse_low_bit_mean,
                           get_backward_mode, block_rotate, group_quantize, host_node, mx_quantize,
                           inplace_weight_grad, pair_kv_hooks, pair_operands, quantize_kv, reset_learned_state, set_backward_mode, share_activation_quant, stats)
 
@@ -12,5 +12,5 @@ __version__ = "0.5.0"
 __all__ = ["SymQuantizer", "AsymQuantizer", "QuantizeLinear", "ops", "set_semantics", "get_semantics", "set_backward_mode", "get_backward_mode",
            "share_activation_quant", "enable_weight_quant_cache", "pair_operands", "quantize_kv", "fuse_low_bit_mean", "inplace_weight_grad", "pair_kv_hooks",
            "conservative", "cpp_node", "host_node", "stats", "reset_learned_state", "allow_cpu_tensors", "FakeQuantLibraryError",
-           "group_quantize", "default_group_sizes", "mx_quantize", "default_mx_formats", "block_rotate", "default_mx_rotate",
+           "group_quantize", "default_group_sizes", "mx_quantize", "default_mx_formats", "block_rotate", "default_mx_rotate", "default_mx_scale_rule", "default_mx_ste",
            "MXLinear", "convert_to_mx_inference"]

@@ -172,3 +172,94 @@ def _(x, fmt):
     lead, cols = tuple(x.shape[:-1]), x.shape[-1]
     return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
             x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))
+
+
+# ---- scale rule and saturation-masked gradient of the MX quantizer: the combinations the ops above do not cover ----
+# ops.mx_quantize under a non-default scale rule with the identity gradient (rotate: grad_x = grad_y R); nothing saved
+@torch.library.custom_op("llmqat_amd::mx_fake_quant_rule", mutates_args=(), device_types="cuda")
+def mx_fake_quant_rule_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> torch.Tensor:
+    return ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule)
+
+
+@mx_fake_quant_rule_op.register_fake
+def _(x, fmt, rotate, scale_rule):
+    ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule)
+    if rotate:
+        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+def _mx_rule_setup(ctx, inputs, output):
+    ctx.rotate = inputs[2]
+
+
+mx_fake_quant_rule_op.register_autograd(lambda ctx, g: (mx_block_rotate_op(g) if ctx.rotate else g, None, None, None), setup_context=_mx_rule_setup)
+
+
+# ops.mx_ste_backward: the gradient under the saturation bitmap (rotate: times R, same launch)
+@torch.library.custom_op("llmqat_amd::mx_ste_backward", mutates_args=(), device_types="cuda")
+def mx_ste_backward_op(g: torch.Tensor, mask: torch.Tensor, rotate: bool) -> torch.Tensor:
+    return ops.mx_ste_backward(g, mask, rotate)
+
+
+@mx_ste_backward_op.register_fake
+def _(g, mask, rotate):
+    ops.check_mx_ste(tuple(g.shape), tuple(mask.shape), mask.dtype, rotate)
+    return torch.empty_like(g, memory_format=torch.contiguous_format)
+
+
+# ops.mx_quantize(return_mask=True): (y, bitmap); the bitmap is all the backward keeps, and the backward is one launch
+@torch.library.custom_op("llmqat_amd::mx_fake_quant_clip", mutates_args=(), device_types="cuda")
+def mx_fake_quant_clip_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, return_mask=True)
+
+
+@mx_fake_quant_clip_op.register_fake
+def _(x, fmt, rotate, scale_rule):
+    ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule)
+    if rotate:
+        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
+    return torch.empty_like(x, memory_format=torch.contiguous_format), x.new_empty((x.numel() // 8,), dtype=torch.uint8)
+
+
+def _mx_clip_setup(ctx, inputs, output):
+    ctx.rotate = inputs[2]
+    ctx.save_for_backward(output[1])
+
+
+def _mx_clip_backward(ctx, grad_y, grad_mask):
+    return mx_ste_backward_op(grad_y, ctx.saved_tensors[0], ctx.rotate), None, None, None
+
+
+mx_fake_quant_clip_op.register_autograd(_mx_clip_backward, setup_context=_mx_clip_setup)
+
+
+def mx_fake_quant(x, fmt, rotate, scale_rule, clip):
+    """utils_quant's MX quantizer while compiling: the op that serves (rotate, scale_rule, clip)."""
+    if clip:
+        return mx_fake_quant_clip_op(x, fmt, rotate, scale_rule)[0]
+    if scale_rule != "floor":
+        return mx_fake_quant_rule_op(x, fmt, rotate, scale_rule)
+    return mx_fake_quant_rot_op(x, fmt) if rotate else mx_fake_quant_op(x, fmt)
+
+
+# ops.mx_export under a scale rule as an op: (elements, scales) of x (rotate: of x R)
+@torch.library.custom_op("llmqat_amd::mx_export_rule", mutates_args=(), device_types="cuda")
+def mx_export_rule_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    e = ops.mx_export(x, fmt, rotate=rotate, scale_rule=scale_rule)
+    return e.elements, e.scales
+
+
+@mx_export_rule_op.register_fake
+def _(x, fmt, rotate, scale_rule):
+    ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule, "mx_export")
+    if rotate:
+        ops.check_mx_rotate(tuple(x.shape), "mx_export")
+    if fmt not in ops.MX_GEMM_FORMATS:
+        raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
+    lead, cols = tuple(x.shape[:-1]), x.shape[-1]
+    return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
+            x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))

@@ -492,9 +492,10 @@ const MxFmt kMxFmts[5] = {
 };
 
 // exp = false: fq_mx_fwd (x -> y); true: fq_mx_export (x -> elems + scales).  rot: the *_rot forms (x R is quantized); only_rot:
-// fq_block_rotate (x -> y = x R, no format).  Every check comes before any HIP call.
+// fq_block_rotate (x -> y = x R, no format).  ceil: the scale rule of the *_ex forms; mask (forward only, optional): the saturation
+// bitmap, rows * cols / 8 bytes.  Every check comes before any HIP call.
 int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_t rows, int64_t cols, int fmt, int dtype, void* stream,
-             bool rot = false, bool only_rot = false) {
+             bool rot = false, bool only_rot = false, bool ceil = false, void* mask = nullptr) {
     if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
     if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
     if (!only_rot && (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2)) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
@@ -506,16 +507,24 @@ int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_
     if (rows == 0 || cols == 0) return ok();
     if (!x || (!exp && !y) || (exp && (!elems || !scales))) return fail(FQ_ERR_NULL, exp ? "x / elems / scales must not be NULL" : "x / y must not be NULL");
     if (!exp && x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
-    if (!aligned16(x) || (!exp && !aligned16(y)) || (exp && (!aligned16(elems) || !aligned16(scales))))
+    if (mask && (mask == x || mask == y)) return fail(FQ_ERR_ARG, "mask_out must not alias x or y");
+    if (!aligned16(x) || (!exp && !aligned16(y)) || (exp && (!aligned16(elems) || !aligned16(scales))) || !aligned16(mask))
         return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
     const int es = esize_of(dtype);
     const int64_t nvec = rows * cols * es / 16;    // cols % 32 == 0: whole 16-byte vectors, whole blocks
     if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
-    MxArgs a{x, y, (uint8_t*)elems, (uint8_t*)scales, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    MxArgs a{x, y, (uint8_t*)(mask ? mask : elems), (uint8_t*)scales, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
     const int kind = only_rot ? MX_ROT : !exp ? MX_FWD : (fmt == FQ_MX_FP4_E2M1 ? MX_EXP4 : MX_EXP8);
     hipStream_t st = (hipStream_t)stream;
+    const MxFmt& f = kMxFmts[only_rot ? 0 : fmt];
+    if (ceil || mask) {   // the forms of section 16; without either, the kernels of the seven-argument entry points
+        switch (dtype) {
+            case FQ_DTYPE_F32: return launch_mx_ex<F32>(kind, rot, ceil, mask != nullptr, a, f, st);
+            case FQ_DTYPE_F16: return launch_mx_ex<F16>(kind, rot, ceil, mask != nullptr, a, f, st);
+            default: return launch_mx_ex<BF16>(kind, rot, ceil, mask != nullptr, a, f, st);
+        }
+    }
     if (rot) {   // cols % 64 == 0: whole rotation runs
-        const MxFmt& f = kMxFmts[only_rot ? 0 : fmt];
         switch (dtype) {
             case FQ_DTYPE_F32: return launch_mx_rot<F32>(kind, a, f, st);
             case FQ_DTYPE_F16: return launch_mx_rot<F16>(kind, a, f, st);
@@ -523,11 +532,12 @@ int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_
         }
     }
     switch (dtype) {
-        case FQ_DTYPE_F32: return launch_mx<F32>(kind, a, kMxFmts[fmt], st);
-        case FQ_DTYPE_F16: return launch_mx<F16>(kind, a, kMxFmts[fmt], st);
-        default: return launch_mx<BF16>(kind, a, kMxFmts[fmt], st);
+        case FQ_DTYPE_F32: return launch_mx<F32>(kind, a, f, st);
+        case FQ_DTYPE_F16: return launch_mx<F16>(kind, a, f, st);
+        default: return launch_mx<BF16>(kind, a, f, st);
     }
 }
+const int kMxFlags = FQ_MX_FLAG_ROTATE | FQ_MX_FLAG_CEIL;
 }  // namespace
 
 FQ_API int fq_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
@@ -548,6 +558,46 @@ FQ_API int fq_mx_export_rot(const void* x, void* elems_out, void* scales_out, in
 
 FQ_API int fq_block_rotate(const void* x, void* y, int64_t rows, int64_t cols, int dtype, void* stream) {
     return mx_entry(false, x, y, nullptr, nullptr, rows, cols, 0, dtype, stream, true, true);
+}
+
+FQ_API int fq_mx_fwd_ex(const void* x, void* y, void* mask_out, int64_t rows, int64_t cols, int fmt, int dtype, int flags, void* stream) {
+    if (flags & ~kMxFlags) return fail(FQ_ERR_ARG, "unknown flag bits 0x%x", (unsigned)(flags & ~kMxFlags));
+    return mx_entry(false, x, y, nullptr, nullptr, rows, cols, fmt, dtype, stream, (flags & FQ_MX_FLAG_ROTATE) != 0, false,
+                    (flags & FQ_MX_FLAG_CEIL) != 0, mask_out);
+}
+
+FQ_API int fq_mx_export_ex(const void* x, void* elems_out, void* scales_out, int64_t rows, int64_t cols, int fmt, int dtype, int flags,
+                           void* stream) {
+    if (flags & ~kMxFlags) return fail(FQ_ERR_ARG, "unknown flag bits 0x%x", (unsigned)(flags & ~kMxFlags));
+    return mx_entry(true, x, nullptr, elems_out, scales_out, rows, cols, fmt, dtype, stream, (flags & FQ_MX_FLAG_ROTATE) != 0, false,
+                    (flags & FQ_MX_FLAG_CEIL) != 0);
+}
+
+// Every check comes before any HIP call.  gx == g is served without the rotation (every lane stores the vector it loaded).
+FQ_API int fq_mx_ste_bwd(const void* g, const void* mask, void* gx, int64_t rows, int64_t cols, int dtype, int flags, void* stream) {
+    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
+    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
+    if (flags & ~FQ_MX_FLAG_ROTATE) return fail(FQ_ERR_ARG, "flag bits 0x%x: the backward takes FQ_MX_FLAG_ROTATE only", (unsigned)(flags & ~FQ_MX_FLAG_ROTATE));
+    const bool rot = (flags & FQ_MX_FLAG_ROTATE) != 0;
+    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
+    if (rot && cols % MX_ROT_RUN != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the %d-element rotation run", (long long)cols, MX_ROT_RUN);
+    if (cols % 32 != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the 32-element MX block", (long long)cols);
+    if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
+    if (rows == 0 || cols == 0) return ok();
+    if (!g || !mask || !gx) return fail(FQ_ERR_NULL, "g / mask / gx must not be NULL");
+    if (mask == g || mask == gx) return fail(FQ_ERR_ARG, "mask must not alias g or gx");
+    if (rot && g == gx) return fail(FQ_ERR_ARG, "in-place (gx == g) is not supported with the rotation");
+    if (!aligned16(g) || !aligned16(mask) || !aligned16(gx)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+    const int es = esize_of(dtype);
+    const int64_t nvec = rows * cols * es / 16;
+    if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
+    const MxSteArgs a{g, (const uint32_t*)mask, gx, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case FQ_DTYPE_F32: return launch_mx_ste<F32>(rot, a, st);
+        case FQ_DTYPE_F16: return launch_mx_ste<F16>(rot, a, st);
+        default: return launch_mx_ste<BF16>(rot, a, st);
+    }
 }
 
 // Every check comes before any HIP call.

@@ -194,15 +194,29 @@ struct MxFmt {
 struct MxArgs {
     const void* x;
     void* y;             // MX_FWD / MX_ROT
-    uint8_t* elems;      // MX_EXP4 / MX_EXP8
+    uint8_t* elems;      // MX_EXP4 / MX_EXP8; MX_FWD with the saturation bitmap (launch_mx_ex, mask = true): the bitmap, one little-endian
+                         // 32-bit word per block (bit = 0: saturation changed the element)
     uint8_t* scales;     // MX_EXP4 / MX_EXP8
     int64_t nvec;        // 16-byte vectors of the tensor: a multiple of the block's vector count
     int ntl;             // non-temporal loads (the tensor is larger than NT_LOAD_MIN_BYTES): uniform over the launch
 };
+// the masked straight-through backward (fq_mx_ste_bwd): gx = g where the bit is 1, else +0.0; ROT: gx = (g masked) R
+struct MxSteArgs {
+    const void* g;
+    const uint32_t* mask;   // one word per block of 32 elements
+    void* gx;               // may be g itself without ROT (every lane stores the vector it loaded)
+    int64_t nvec;
+    int ntl;
+};
+template <int DT> FQ_HIDDEN int launch_mx_ste(bool rot, MxSteArgs a, hipStream_t st);
 template <int DT> FQ_HIDDEN int launch_mx(int kind, MxArgs a, MxFmt f, hipStream_t st);
 // the same kinds on x R (R block-diagonal along the last dimension, blocks H64 / 8), and MX_ROT: y = x R alone (f unused); nvec is a
 // multiple of the run's vector count
 template <int DT> FQ_HIDDEN int launch_mx_rot(int kind, MxArgs a, MxFmt f, hipStream_t st);
+// the forms of section 16 (fq_mx_fwd_ex / fq_mx_export_ex with the ceil rule and / or the bitmap): kind MX_FWD / MX_EXP4 / MX_EXP8, on x or
+// (rot) x R; ceil: the no-clip scale rule; mask (MX_FWD only): also write the bitmap to a.elems.  The rule is a template parameter of the
+// kernels, so launch_mx / launch_mx_rot run the code they always ran.
+template <int DT> FQ_HIDDEN int launch_mx_ex(int kind, bool rot, bool ceil, bool mask, MxArgs a, MxFmt f, hipStream_t st);
 // MX block-scaled GEMM (fq_mx_gemm.h / fq_mx_gemm.hip): out[m, n] = sum_k A[m, k] * W[n, k] over two MX exports
 struct MxGemmArgs {
     const uint8_t* we;   // W: [N, K] element codes, E8M0 scales [N, K / 32]

@@ -15,6 +15,15 @@
 // The format is a kernel argument (MxFmt): the rounding chain is the same for all five, so only the dtype, the output kind and the
 // rotation are template parameters.
 //
+// Scale rule and saturation mask.  CEIL picks the no-clip rule: E is one higher where amax * 2^-E would exceed
+// max-normal, so no element of a finite block saturates.  It is a template parameter: as a kernel argument it cost the existing entry
+// points 1 - 2 % on a bf16 [4096, 11008] tensor, several times their run-to-run scatter, and with CEIL = false and MASK = false the kernels
+// are the ones that were there before.  MASK (MX_FWD only) also writes one bit per element, 0 where the rounded value on the unbounded grid exceeds
+// max-normal (saturation changed it): a lane's EPV bits go to their place in the block's 32-bit word, the word is an OR over the block's BV
+// lanes (group_reduce) and one lane stores it.  Under ROT the bits are those of the elements of x R.
+//   mx_ste_kernel       the masked straight-through backward: gx = g where the bit is 1, else +0.0, a select on bit patterns; ROT: the
+//                       masked gradient goes through mx_rotate and is rounded once, as KIND = MX_ROT does (one launch).
+//
 // ROT: the kernel quantizes x R instead of x.  R is block-diagonal along the last dimension with blocks H64 / 8
 // (H64 the 64 x 64 Sylvester Hadamard matrix): orthonormal, symmetric, its own inverse, entries +-0.125.  A run of 64 elements is 8
 // consecutive vectors of a 16-bit tensor (16 of an fp32 one), held by 8 (16) lanes of one DPP row.  The run is widened to fp32, the
@@ -31,11 +40,23 @@ namespace fq {
 
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
+struct OpOrU {   // idempotent, so group_reduce's butterfly serves it
+    __device__ static __forceinline__ uint32_t f(uint32_t a, uint32_t b) { return a | b; }
+};
+
 // E of a finite block from the fp32 bits of its amax, read from the bits (a subnormal amax included)
 __device__ __forceinline__ int mx_shared_exp(uint32_t ab, int emax) {
     const int f = (int)(ab >> 23);
     int e = f ? f - 127 : 31 - (int)__builtin_clz(ab | 1u) - 149;
     e = ab ? e - emax : -127;
+    return e < -127 ? -127 : (e > 127 ? 127 : e);
+}
+// the ceil rule: amax * 2^-Ef (exact, in [2^emax, 2^(emax + 1))) above max-normal takes Ef + 1, before the clamp
+__device__ __forceinline__ int mx_shared_exp_ceil(uint32_t ab, int emax, float maxnorm) {
+    const int f = (int)(ab >> 23);
+    int e = (f ? f - 127 : 31 - (int)__builtin_clz(ab | 1u) - 149) - emax;
+    e += (int)(__builtin_amdgcn_ldexpf(as_f(ab), -e) > maxnorm);
+    e = ab ? e : -127;
     return e < -127 ? -127 : (e > 127 ? 127 : e);
 }
 
@@ -53,6 +74,12 @@ __device__ __forceinline__ float mx_rint(float v, int nE, int bmin, int mbits, i
 __device__ __forceinline__ float mx_value(float v, float r, int sb, int yk, float maxx) {
     const float q = __builtin_fminf(__builtin_fabsf(__builtin_amdgcn_ldexpf(r, sb + yk)), maxx);
     return __builtin_copysignf(q, v);
+}
+// the same, and sat <- whether the saturation changed the value (the rounded magnitude, before the min, is above maxx)
+__device__ __forceinline__ float mx_value_sat(float v, float r, int sb, int yk, float maxx, bool& sat) {
+    const float u = __builtin_fabsf(__builtin_amdgcn_ldexpf(r, sb + yk));
+    sat = u > maxx;
+    return __builtin_copysignf(__builtin_fminf(u, maxx), v);
 }
 
 // code of one element: ((binade - smallest normal binade) << mbits) + |r| is the OCP encoding of |q| (a carry of r into the next
@@ -100,12 +127,13 @@ template <int EPV> __device__ __forceinline__ void mx_rotate(float (&v)[EPV], ui
     for (int e = 0; e < EPV; ++e) v[e] = v[e] * 0.125f;
 }
 
-template <int DT, int KIND, int VPT, bool ROT>
+template <int DT, int KIND, int VPT, bool ROT, bool MASK, bool CEIL>
 __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE;     // elements per vector
     constexpr int BV = 32 / EPV;           // vectors per block
     static_assert(ROT || KIND != MX_ROT, "the rotation alone is a rotated launch");
+    static_assert(!MASK || KIND == MX_FWD, "the saturation bitmap belongs to the forward");
     const uint32_t slot = ROT ? mx_rot_slot<EPV>(threadIdx.x) : threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * (MX_TPB * VPT) + slot;
     const uint4* __restrict__ xv = (const uint4*)a.x;
@@ -166,11 +194,12 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
         }
         const uint32_t ab = group_reduce<OpMaxU>(acc, BV);   // fp32 bits of the block's amax (NaN sorts above Inf)
         const bool bad = ab >= 0x7F800000u;                   // a NaN or Inf in the block
-        const int E = mx_shared_exp(ab, f.emax);
+        const int E = CEIL ? mx_shared_exp_ceil(ab, f.emax, f.maxnorm) : mx_shared_exp(ab, f.emax);
         const int nE = -E, yk = E - 127 - f.mbits;
         const float maxx = __builtin_amdgcn_ldexpf(f.maxnorm, E);
         if constexpr (KIND == MX_FWD) {
             uint32_t o[4];
+            uint32_t keep = 0;   // MASK: bit e set = the lane's element e was not changed by the saturation
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 float fd[T::EPD];
@@ -184,11 +213,22 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
                 for (int k = 0; k < T::EPD; ++k) {
                     int sb;
                     const float rr = mx_rint(fd[k], nE, bmin, f.mbits, sb);
-                    fd[k] = bad ? as_f(0x7FC00000u) : mx_value(fd[k], rr, sb, yk, maxx);
+                    if constexpr (MASK) {
+                        bool sat;
+                        const float yv = mx_value_sat(fd[k], rr, sb, yk, maxx, sat);
+                        fd[k] = bad ? as_f(0x7FC00000u) : yv;
+                        keep |= (uint32_t)(bad || !sat) << (d * T::EPD + k);
+                    } else {
+                        fd[k] = bad ? as_f(0x7FC00000u) : mx_value(fd[k], rr, sb, yk, maxx);
+                    }
                 }
                 o[d] = T::pack(fd);
             }
             if (v < a.nvec) st16<true>(&((uint4*)a.y)[v], make_uint4(o[0], o[1], o[2], o[3]));
+            if constexpr (MASK) {   // flat element i is bit i & 31 of word i >> 5: vector v holds the bits (v % BV) * EPV .. of word v / BV
+                const uint32_t word = group_reduce<OpOrU>(keep << ((uint32_t)(v & (BV - 1)) * EPV), BV);
+                if (v < a.nvec && (threadIdx.x & (BV - 1)) == 0) ((uint32_t*)a.elems)[v / BV] = word;
+            }
         } else {
             uint32_t c[EPV];
 #pragma unroll
@@ -232,9 +272,96 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
     }
 }
 
-template <int DT, int KIND, bool ROT = false> static void launch_mx_kind(const MxArgs& a, const MxFmt& f, hipStream_t st) {
+// gx = g where the mask bit is 1, else +0.0 (a select on the bit patterns: a NaN g at a masked position gives +0.0); ROT: the masked
+// values times R, rounded once.  Loads, slots and stores as mx_kernel; a lane's EPV bits are bits (v % BV) * EPV .. of mask word v / BV.
+template <int DT, int VPT, bool ROT>
+__global__ __launch_bounds__(MX_TPB) void mx_ste_kernel(MxSteArgs a) {
+    using T = Ty<DT>;
+    constexpr int EPV = 16 / T::ESIZE;
+    constexpr int BV = 32 / EPV;
+    const uint32_t slot = ROT ? mx_rot_slot<EPV>(threadIdx.x) : threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * (MX_TPB * VPT) + slot;
+    const uint4* gv = (const uint4*)a.g;
+
+    uint4 r[VPT];
+    uint32_t m[VPT];
+    if (a.ntl) {
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) {
+            const int64_t v = base + i * MX_TPB, c = v < a.nvec ? v : a.nvec - 1;
+            r[i] = ld16<true>(&gv[c]);
+            m[i] = a.mask[c / BV] >> ((uint32_t)(c & (BV - 1)) * EPV);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) {
+            const int64_t v = base + i * MX_TPB, c = v < a.nvec ? v : a.nvec - 1;
+            r[i] = ld16<false>(&gv[c]);
+            m[i] = a.mask[c / BV] >> ((uint32_t)(c & (BV - 1)) * EPV);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const int64_t v = base + i * MX_TPB;
+        uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            uint32_t keep = 0;
+#pragma unroll
+            for (int k = 0; k < T::EPD; ++k)
+                if ((m[i] >> (d * T::EPD + k)) & 1u) keep |= (T::EPD == 1 ? 0xFFFFFFFFu : 0xFFFFu << (16 * k));
+            w[d] &= keep;
+        }
+        if constexpr (ROT) {
+            float xr[EPV];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                float fd[T::EPD];
+                T::unpack(w[d], fd);
+#pragma unroll
+                for (int k = 0; k < T::EPD; ++k) xr[d * T::EPD + k] = fd[k];
+            }
+            mx_rotate<EPV>(xr, slot);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                float fd[T::EPD];
+#pragma unroll
+                for (int k = 0; k < T::EPD; ++k) fd[k] = xr[d * T::EPD + k];
+                w[d] = T::pack(fd);
+            }
+        }
+        if (v < a.nvec) st16<true>(&((uint4*)a.gx)[v], make_uint4(w[0], w[1], w[2], w[3]));
+    }
+}
+
+template <int DT, int KIND, bool ROT = false, bool MASK = false, bool CEIL = false>
+static void launch_mx_kind(const MxArgs& a, const MxFmt& f, hipStream_t st) {
     const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
-    FQ_LAUNCHK((mx_kernel<DT, KIND, MX_VPT, ROT>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a, f);
+    FQ_LAUNCHK((mx_kernel<DT, KIND, MX_VPT, ROT, MASK, CEIL>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a, f);
+}
+template <int DT, bool ROT, bool CEIL> static void launch_mx_ex_kind(int kind, bool mask, const MxArgs& a, const MxFmt& f, hipStream_t st) {
+    if (kind == MX_FWD && mask) launch_mx_kind<DT, MX_FWD, ROT, true, CEIL>(a, f, st);
+    else if (kind == MX_FWD) launch_mx_kind<DT, MX_FWD, ROT, false, CEIL>(a, f, st);
+    else if (kind == MX_EXP4) launch_mx_kind<DT, MX_EXP4, ROT, false, CEIL>(a, f, st);
+    else launch_mx_kind<DT, MX_EXP8, ROT, false, CEIL>(a, f, st);
+}
+// validated by fq_mx_fwd_ex / fq_mx_export_ex; the combinations without ceil and without mask go through launch_mx / launch_mx_rot
+template <int DT> int launch_mx_ex(int kind, bool rot, bool ceil, bool mask, MxArgs a, MxFmt f, hipStream_t st) {
+    begin_launches();
+    if (rot && ceil) launch_mx_ex_kind<DT, true, true>(kind, mask, a, f, st);
+    else if (rot) launch_mx_ex_kind<DT, true, false>(kind, mask, a, f, st);
+    else if (ceil) launch_mx_ex_kind<DT, false, true>(kind, mask, a, f, st);
+    else launch_mx_ex_kind<DT, false, false>(kind, mask, a, f, st);
+    return launch_result();
+}
+
+// a validated by fq_mx_ste_bwd (nvec > 0, grid within limits; rot: whole runs)
+template <int DT> int launch_mx_ste(bool rot, MxSteArgs a, hipStream_t st) {
+    begin_launches();
+    const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
+    if (rot) FQ_LAUNCHK((mx_ste_kernel<DT, MX_VPT, true>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a);
+    else FQ_LAUNCHK((mx_ste_kernel<DT, MX_VPT, false>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a);
+    return launch_result();
 }
 
 // kind: MX_FWD / MX_EXP4 / MX_EXP8; a and f validated by fq_mx_fwd / fq_mx_export (nvec > 0, grid within limits)
@@ -258,6 +385,8 @@ template <int DT> int launch_mx_rot(int kind, MxArgs a, MxFmt f, hipStream_t st)
 
 #define FQ_INSTANTIATE_MX(DT)                                              \
     template int launch_mx<DT>(int, MxArgs, MxFmt, hipStream_t); \
-    template int launch_mx_rot<DT>(int, MxArgs, MxFmt, hipStream_t);
+    template int launch_mx_rot<DT>(int, MxArgs, MxFmt, hipStream_t); \
+    template int launch_mx_ste<DT>(bool, MxSteArgs, hipStream_t);        \
+    template int launch_mx_ex<DT>(int, bool, bool, bool, MxArgs, MxFmt, hipStream_t);
 
 }  // namespace fq

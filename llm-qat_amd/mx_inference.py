@@ -26,10 +26,12 @@ class MXLinear(nn.Module):
     ops.MXExport of the trained weight), no bf16 weight.  Inference only: not differentiable.  The output has x's dtype; the bias is added
     in that dtype (cast to it when the module's dtype differs).
     rotate=True: the buffers hold the export of W R and the activation's export launch rotates x, so the product
-    is (x R)(W R)^T -- still two launches, the same GEMM.  A constructor attribute like the formats: it is not in the state_dict."""
+    is (x R)(W R)^T -- still two launches, the same GEMM.  A constructor attribute like the formats: it is not in the state_dict.
+    scale_rule: the shared-exponent rule of the activation's export launch ("floor" / "ceil"); the weight buffers
+    carry whatever rule exported them, and the GEMM reads the scale bytes as they are.  A constructor attribute too."""
 
     def __init__(self, in_features, out_features, weight_format="mxfp4", act_format="mxfp8_e4m3", bias=False, device=None, dtype=None,
-                 rotate=False):
+                 rotate=False, scale_rule="floor"):
         super().__init__()
         for what, fmt in (("weight_format", weight_format), ("act_format", act_format)):
             if fmt not in ops.MX_GEMM_FORMATS:
@@ -39,6 +41,8 @@ class MXLinear(nn.Module):
         self.in_features, self.out_features = in_features, out_features
         self.weight_format, self.act_format = weight_format, act_format
         self.rotate = bool(rotate)   # (in_features % 128 == 0 holds whole 64-element rotation runs)
+        ops.check_mx_scale_rule(scale_rule, "MXLinear")
+        self.scale_rule = scale_rule
         ebytes = in_features // 2 if weight_format == "mxfp4" else in_features
         self.register_buffer("weight_elements", torch.zeros(out_features, ebytes, dtype=torch.uint8, device=device))
         self.register_buffer("weight_scales", torch.zeros(out_features, in_features // ops.MX_BLOCK, dtype=torch.uint8, device=device))
@@ -54,9 +58,11 @@ class MXLinear(nn.Module):
             raise ValueError(f"MXLinear.from_quantize_linear: {why}")
         has_bias = getattr(layer, "bias", None) is not None
         rotate = bool(getattr(layer, "mx_rotate", False))
+        rule = getattr(layer, "mx_scale_rule", "floor")
         m = cls(layer.in_features, layer.out_features, layer.weight_format, layer.act_format, bias=has_bias, device=layer.weight.device,
-                dtype=layer.weight.dtype, rotate=rotate)
-        e = layer.export_weight() if hasattr(layer, "export_weight") else ops.mx_export(layer.weight.detach(), layer.weight_format, rotate=rotate)
+                dtype=layer.weight.dtype, rotate=rotate, scale_rule=rule)
+        e = (layer.export_weight() if hasattr(layer, "export_weight")
+             else ops.mx_export(layer.weight.detach(), layer.weight_format, rotate=rotate, scale_rule=rule))
         m.weight_elements.copy_(e.elements)
         m.weight_scales.copy_(e.scales)
         if has_bias:
@@ -71,18 +77,22 @@ class MXLinear(nn.Module):
     def forward(self, x):
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("MXLinear is an inference module and is not differentiable: call it under torch.no_grad() or on a detached input")
-        if torch.compiler.is_compiling():
+        if torch.compiler.is_compiling() and self.scale_rule != "floor":
+            ae, asc = compiled.mx_export_rule_op(x, self.act_format, self.rotate, self.scale_rule)
+            y = compiled.mx_matmul_op(ae, asc, self.act_format, self.weight_elements, self.weight_scales, self.weight_format, list(x.shape), x.dtype)
+        elif torch.compiler.is_compiling():
             ae, asc = (compiled.mx_export_rot_op if self.rotate else compiled.mx_export_op)(x, self.act_format)
             y = compiled.mx_matmul_op(ae, asc, self.act_format, self.weight_elements, self.weight_scales, self.weight_format, list(x.shape), x.dtype)
         else:
-            a = ops.mx_export(x, self.act_format, rotate=self.rotate)
+            a = ops.mx_export(x, self.act_format, rotate=self.rotate, scale_rule=self.scale_rule)
             y = ops.mx_matmul_tensors(a.elements, a.scales, a.fmt, self.weight_elements, self.weight_scales, self.weight_format, a.shape, x.dtype)
         # the bias in x's dtype: the output dtype follows x (fp16 + bf16 would promote the sum to fp32)
         return y if self.bias is None else y + self.bias.to(y.dtype)
 
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, weight_format={self.weight_format!r}, "
-                f"act_format={self.act_format!r}, bias={self.bias is not None}" + (", rotate=True" if self.rotate else ""))
+                f"act_format={self.act_format!r}, bias={self.bias is not None}" + (", rotate=True" if self.rotate else "")
+                + (f", scale_rule={self.scale_rule!r}" if self.scale_rule != "floor" else ""))
 
 
 def convert_to_mx_inference(model):

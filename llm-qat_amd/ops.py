@@ -1066,8 +1066,12 @@ MX_BLOCK = 32
 # 64 x 64 Sylvester Hadamard matrix, normalised: orthonormal, symmetric, its own inverse).  Rotating both operands of a product along K
 # leaves the product unchanged and spreads an outlier over its 64-element run before the block scales are taken.
 MX_ROTATE = 64
+# scale_rule: "floor" is OCP's E = floor(log2 amax) - emax, under which the top binade of a block may saturate;
+# "ceil" is the smallest E with amax * 2^-E <= max-normal, under which nothing does.  The saturation mask (return_mask) has one bit per
+# element, bit i & 7 of byte i >> 3 for flat element i, 0 where saturation changed the rounded value; mx_ste_backward applies it.
+MX_SCALE_RULES = ("floor", "ceil")
 mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm_launch": 0, "mx_gemm_skinny": 0, "mx_gemm_tiled": 0,
-             "mx_rotate_launch": 0}
+             "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0}
 
 
 def check_mx(shape, fmt):
@@ -1089,6 +1093,13 @@ def check_mx_rotate(shape, what="mx_rotate"):
         raise ValueError(f"{what}: the rotation takes tensors with at least one dimension")
     if shape[-1] % MX_ROTATE:
         raise ValueError(f"{what}: the block-Hadamard rotation needs a last dimension that is a multiple of {MX_ROTATE}, got {shape[-1]}")
+
+
+def check_mx_scale_rule(scale_rule, what="mx_quantize"):
+    """-> FQ_MX_FLAG_CEIL or 0; ValueError for anything but "floor" / "ceil"."""
+    if not isinstance(scale_rule, str) or scale_rule not in MX_SCALE_RULES:
+        raise ValueError(f"{what}: unknown scale_rule {scale_rule!r}: one of {', '.join(MX_SCALE_RULES)}")
+    return _lib.MX_FLAG_CEIL if scale_rule == "ceil" else 0
 
 
 def _mx_input(x, fmt, what, rotate=False):
@@ -1118,20 +1129,74 @@ def mx_rotate(x):
     return y
 
 
-def mx_quantize(x, fmt, rotate=False):
+def mx_quantize(x, fmt, rotate=False, scale_rule="floor", return_mask=False):
     """MX fake quantization of x (same shape and dtype): each block of 32 elements along the last dimension scaled by its shared power
     of two, rounded onto the element grid of `fmt` and saturated, then scaled back and rounded once to x's dtype.  rotate=True: of the
-    fp32 values of x R (mx_rotate) instead, in the same single launch; the result is in the rotated basis."""
+    fp32 values of x R (mx_rotate) instead, in the same single launch; the result is in the rotated basis.
+    scale_rule="ceil": the shared exponent under which no element of a finite block saturates.  return_mask=True -> (y, mask): mask is a
+    uint8 tensor of numel / 8 bytes written by the same launch, a 0 bit where saturation changed the element (of x R under rotate)."""
+    flags = check_mx_scale_rule(scale_rule)
     x, code, dt = _mx_input(x, fmt, "mx_quantize", rotate)
     y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    mask = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device) if return_mask else None
     if x.numel():
         cols = x.shape[-1]
         rows = x.numel() // cols
         L = _lib.lib()
-        fwd = L.fq_mx_fwd_rot if rotate else L.fq_mx_fwd
-        _lib.check(_on_device(x, lambda st: fwd(x.data_ptr(), y.data_ptr(), rows, cols, code, dt, st)), "mx_quantize")
+        if flags or return_mask:
+            flags |= _lib.MX_FLAG_ROTATE if rotate else 0
+            mp = mask.data_ptr() if return_mask else None
+            _lib.check(_on_device(x, lambda st: L.fq_mx_fwd_ex(x.data_ptr(), y.data_ptr(), mp, rows, cols, code, dt, flags, st)), "mx_quantize")
+        else:
+            fwd = L.fq_mx_fwd_rot if rotate else L.fq_mx_fwd
+            _lib.check(_on_device(x, lambda st: fwd(x.data_ptr(), y.data_ptr(), rows, cols, code, dt, st)), "mx_quantize")
         mx_counts["mx_launch"] += 1
-    return y
+        if return_mask:
+            mx_counts["mx_mask_launch"] += 1
+    return (y, mask) if return_mask else y
+
+
+def check_mx_ste(g_shape, mask_shape, mask_dtype, rotate):
+    """The argument checks of mx_ste_backward on shapes alone (the fake implementation of the compiled op runs them too)."""
+    if len(g_shape) == 0 or g_shape[-1] % MX_BLOCK:
+        raise ValueError(f"mx_ste_backward: the gradient needs a last dimension that is a multiple of {MX_BLOCK}, got shape {tuple(g_shape)}")
+    if rotate:
+        check_mx_rotate(tuple(g_shape), "mx_ste_backward")
+    if mask_dtype != torch.uint8:
+        raise TypeError(f"mx_ste_backward: the mask is a uint8 bitmap (mx_quantize(return_mask=True)), got {mask_dtype}")
+    n = 1
+    for d in g_shape:
+        n *= d
+    m = 1
+    for d in mask_shape:
+        m *= d
+    if m * 8 != n:
+        raise ValueError(f"mx_ste_backward: the mask holds {m} bytes, the gradient {n} elements: one bit per element is {n // 8} bytes")
+
+
+def mx_ste_backward(g, mask, rotate=False):
+    """The straight-through gradient of mx_quantize under its saturation mask: g where the element's bit is 1, +0.0 where it is 0 (a
+    select: a NaN / Inf g there gives +0.0).  rotate=True: the masked gradient times R, rounded once to g's dtype -- mx_rotate of the
+    masked gradient bit for bit, in the same single launch.  -> a new tensor of g's shape and dtype."""
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError(f"mx_ste_backward: expected a torch.Tensor mask, got {type(mask).__name__}")
+    if isinstance(g, torch.Tensor):
+        check_mx_ste(tuple(g.shape), tuple(mask.shape), mask.dtype, rotate)
+    g, _, dt = _mx_input(g, None, "mx_ste_backward", False)
+    if mask.device != g.device:
+        raise RuntimeError(f"mx_ste_backward: the mask is on '{mask.device}', the gradient on '{g.device}'")
+    if not mask.is_contiguous() or mask.data_ptr() & 15:
+        mx_counts["mx_copy_route"] += 1
+        mask = mask.contiguous() if not mask.is_contiguous() else mask.clone()
+    gx = torch.empty_like(g, memory_format=torch.contiguous_format)
+    if g.numel():
+        cols = g.shape[-1]
+        rows = g.numel() // cols
+        L = _lib.lib()
+        flags = _lib.MX_FLAG_ROTATE if rotate else 0
+        _lib.check(_on_device(g, lambda st: L.fq_mx_ste_bwd(g.data_ptr(), mask.data_ptr(), gx.data_ptr(), rows, cols, dt, flags, st)), "mx_ste_backward")
+        mx_counts["mx_ste_launch"] += 1
+    return gx
 
 
 # E2M1 values of the 16 FP4 codes (sign in bit 3)
@@ -1172,9 +1237,11 @@ class MXExport:
         return y.reshape(self.shape).to(self.dtype)
 
 
-def mx_export(x, fmt, rotate=False):
-    """-> MXExport(elements, scales, fmt, shape, dtype, rotated): the codes and E8M0 scales of mx_quantize(x, fmt, rotate).  mxfp4 and
-    mxfp8_* only (FP6 has no packing here: ValueError)."""
+def mx_export(x, fmt, rotate=False, scale_rule="floor"):
+    """-> MXExport(elements, scales, fmt, shape, dtype, rotated): the codes and E8M0 scales of mx_quantize(x, fmt, rotate, scale_rule).
+    mxfp4 and mxfp8_* only (FP6 has no packing here: ValueError).  The export does not record the rule: dequantize() and mx_matmul read
+    whatever scale byte it wrote."""
+    flags = check_mx_scale_rule(scale_rule, "mx_export")
     code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) else None
     if code in (_lib.MX_FP6_E2M3, _lib.MX_FP6_E3M2):
         raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
@@ -1186,8 +1253,13 @@ def mx_export(x, fmt, rotate=False):
     if x.numel():
         rows = x.numel() // cols
         L = _lib.lib()
-        exp = L.fq_mx_export_rot if rotate else L.fq_mx_export
-        _lib.check(_on_device(x, lambda st: exp(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, st)), "mx_export")
+        if flags:
+            flags |= _lib.MX_FLAG_ROTATE if rotate else 0
+            _lib.check(_on_device(x, lambda st: L.fq_mx_export_ex(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, flags, st)),
+                       "mx_export")
+        else:
+            exp = L.fq_mx_export_rot if rotate else L.fq_mx_export
+            _lib.check(_on_device(x, lambda st: exp(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, st)), "mx_export")
         mx_counts["mx_export_launch"] += 1
     return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype, rotate)
 

@@ -112,6 +112,8 @@ def stats(reset=False):
                                          either that took one .contiguous() copy first (non-contiguous or misaligned)
       mx_rotate_launch                   block-Hadamard rotations launched on their own (ops.mx_rotate, block_rotate, the backward of the rotated
                                          MX quantizer); the fused rotated forms count as mx_launch / mx_export_launch
+      mx_mask_launch / mx_ste_launch     MX forwards that also wrote the saturation bitmap (ops.mx_quantize(return_mask=True), mx_ste="clip"; each
+                                         is an mx_launch too) and masked straight-through backwards launched (ops.mx_ste_backward)
       mx_gemm_launch / mx_gemm_skinny / mx_gemm_tiled
                                          MX block-scaled GEMMs (ops.mx_matmul, MXLinear) launched, and which kernel served them (M <= 32: skinny)
       cpp_pair_forward / cpp_weight_forward / cpp_pair_backward / cpp_one_backward / cpp_slow_backward
@@ -466,6 +468,56 @@ class _MXRotQuantizer(torch.autograd.Function):
         return (None if grad_output is None else _BlockRotate.apply(grad_output)), None
 
 
+class _MXQuantizerEx(torch.autograd.Function):
+    """The MX quantizer under a non-default scale rule and / or the saturation-masked gradient; the defaults keep
+    _MXQuantizer / _MXRotQuantizer.  clip: the forward launch also writes the saturation bitmap, the only tensor saved, and the backward
+    is one launch: grad_x = grad_y where the bit is 1, +0.0 elsewhere (times R under rotate, in that launch).  Without clip nothing is
+    saved and the gradient is the identity (times R under rotate)."""
+
+    @staticmethod
+    def forward(ctx, x, fmt, rotate, scale_rule, clip):
+        ctx.set_materialize_grads(False)
+        ctx.rotate, ctx.clip = rotate, clip
+        if not clip:
+            return ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule)
+        y, mask = ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, return_mask=True)
+        ctx.save_for_backward(mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if grad_output is None:
+            return None, None, None, None, None
+        if not ctx.clip:
+            return (_BlockRotate.apply(grad_output) if ctx.rotate else grad_output), None, None, None, None
+        mask, = ctx.saved_tensors
+        if torch.is_grad_enabled():   # create_graph: the mask does not depend on the gradient (as _graph_aware) -- learn it on ones
+            with torch.no_grad():
+                keep = ops.mx_ste_backward(torch.ones_like(grad_output), mask)
+            g = torch.where(keep != 0, grad_output, torch.zeros((), dtype=grad_output.dtype, device=grad_output.device))
+            return (_BlockRotate.apply(g) if ctx.rotate else g), None, None, None, None
+        return ops.mx_ste_backward(grad_output, mask, ctx.rotate), None, None, None, None
+
+
+MX_STE_MODES = ("identity", "clip")
+
+
+def _check_mx_ste(ste, what="mx_quantize"):
+    if not isinstance(ste, str) or ste not in MX_STE_MODES:
+        raise ValueError(f"{what}: unknown ste {ste!r}: one of {', '.join(MX_STE_MODES)}")
+    return ste
+
+
+def _mx_apply(x, fmt, rotate, scale_rule, ste):
+    """the MX quantizer of (rotate, scale_rule, ste) on x, eager or while compiling; the arguments are checked by the callers"""
+    clip = ste == "clip" and torch.is_grad_enabled() and x.requires_grad   # no backward will come: no bitmap is written
+    if torch.compiler.is_compiling():
+        return compiled.mx_fake_quant(x, fmt, rotate, scale_rule, clip)
+    if clip or scale_rule != "floor":
+        return _MXQuantizerEx.apply(x, fmt, rotate, scale_rule, clip)
+    return _MXRotQuantizer.apply(x, fmt) if rotate else _MXQuantizer.apply(x, fmt)
+
+
 def block_rotate(x):
     """x R: every run of 64 consecutive elements of the last dimension (a multiple of 64) times H64 / 8, the normalised 64 x 64 Sylvester
     Hadamard matrix; fp32 arithmetic, rounded once to x's dtype.  Differentiable; its backward is itself."""
@@ -477,21 +529,21 @@ def block_rotate(x):
     return _BlockRotate.apply(x)
 
 
-def mx_quantize(x, fmt, rotate=False):
+def mx_quantize(x, fmt, rotate=False, scale_rule="floor", ste="identity"):
     """OCP MX fake quantization ("mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8_e4m3", "mxfp8_e5m2"): every 32 consecutive elements of the
     last dimension share one power-of-two scale.  Same shape and dtype as x; the gradient is the identity (straight-through).
-    rotate=True quantizes x R (block_rotate) in the same launch; the result is in the rotated basis and the gradient is grad R."""
+    rotate=True quantizes x R (block_rotate) in the same launch; the result is in the rotated basis and the gradient is grad R.
+    scale_rule="ceil" takes the shared exponent under which no element saturates ("floor": OCP's round-down rule, under which the top
+    binade of a block may).  ste="clip" zeroes the gradient of the elements that saturation changed: the forward launch also writes a
+    bitmap (numel / 8 bytes, all that is saved) and the backward is one launch, with or without the rotation."""
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
     ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule)
+    _check_mx_ste(ste)
     if rotate:
         ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
-        if torch.compiler.is_compiling():
-            return compiled.mx_fake_quant_rot_op(x, fmt)
-        return _MXRotQuantizer.apply(x, fmt)
-    if torch.compiler.is_compiling():
-        return compiled.mx_fake_quant_op(x, fmt)
-    return _MXQuantizer.apply(x, fmt)
+    return _mx_apply(x, fmt, bool(rotate), scale_rule, ste)
 
 
 _DEFAULT_MX = (None, None)   # (weight, activation) MX formats of QuantizeLinears constructed without explicit ones
@@ -520,6 +572,30 @@ def default_mx_rotate(flag):
     global _DEFAULT_MX_ROTATE
     prev = _DEFAULT_MX_ROTATE
     _DEFAULT_MX_ROTATE = bool(flag)
+    return prev
+
+
+_DEFAULT_MX_SCALE_RULE = "floor"   # mx_scale_rule / mx_ste of QuantizeLinears constructed without explicit ones
+_DEFAULT_MX_STE = "identity"
+
+
+def default_mx_scale_rule(rule):
+    """The scale rule ("floor" / "ceil") the QuantizeLinears constructed from now on take for their MX operands when their own
+    mx_scale_rule is not given.  Layers without an MX operand are not affected.  -> the previous rule."""
+    global _DEFAULT_MX_SCALE_RULE
+    ops.check_mx_scale_rule(rule, "default_mx_scale_rule")
+    prev = _DEFAULT_MX_SCALE_RULE
+    _DEFAULT_MX_SCALE_RULE = rule
+    return prev
+
+
+def default_mx_ste(mode):
+    """The gradient ("identity" / "clip") the QuantizeLinears constructed from now on take for their MX operands when their own mx_ste
+    is not given.  Layers without an MX operand are not affected.  -> the previous mode."""
+    global _DEFAULT_MX_STE
+    _check_mx_ste(mode, "default_mx_ste")
+    prev = _DEFAULT_MX_STE
+    _DEFAULT_MX_STE = mode
     return prev
 
 
@@ -1288,9 +1364,12 @@ class QuantizeLinear(nn.Linear):
     weight_format = None       # MX formats (ops.MX_FORMATS): replace that operand's integer quantizer
     act_format = None
     mx_rotate = False          # both operands are rotated along K before they are quantized: F.linear(Q(x R), Q(W R)) (a plain attribute)
+    mx_scale_rule = "floor"    # shared-exponent rule of the MX operands ("ceil": nothing saturates) and their gradient ("clip": zero where
+    mx_ste = "identity"        # saturation changed the element); plain attributes
 
     def __init__(self, *kargs, symmetric=True, bias=False, w_bits=32, a_bits=32, act_layerwise=False,
-                 weight_layerwise=False, weight_group_size=None, act_group_size=None, weight_format=None, act_format=None, mx_rotate=None):
+                 weight_layerwise=False, weight_group_size=None, act_group_size=None, weight_format=None, act_format=None, mx_rotate=None,
+                 mx_scale_rule=None, mx_ste=None):
         super().__init__(*kargs, bias=False)  # `bias` is accepted and ignored, as in the reference (:176)
         self.w_bits = w_bits
         self.a_bits = a_bits
@@ -1326,6 +1405,22 @@ class QuantizeLinear(nn.Linear):
             self.mx_rotate = True
         elif mx_rotate is None and _DEFAULT_MX_ROTATE and both_mx and self.in_features % ops.MX_ROTATE == 0:
             self.mx_rotate = True
+        # scale rule and gradient of the MX operands: an explicit argument needs one; the process defaults apply to the layers that have one
+        any_mx = self.weight_format is not None or self.act_format is not None
+        if mx_scale_rule is not None:
+            ops.check_mx_scale_rule(mx_scale_rule, "mx_scale_rule")
+            if not any_mx:
+                raise ValueError("mx_scale_rule applies to MX operands: this layer has neither weight_format nor act_format")
+            self.mx_scale_rule = mx_scale_rule
+        elif any_mx:
+            self.mx_scale_rule = _DEFAULT_MX_SCALE_RULE
+        if mx_ste is not None:
+            _check_mx_ste(mx_ste, "mx_ste")
+            if not any_mx:
+                raise ValueError("mx_ste applies to MX operands: this layer has neither weight_format nor act_format")
+            self.mx_ste = mx_ste
+        elif any_mx:
+            self.mx_ste = _DEFAULT_MX_STE
         # group sizes: an explicit argument is checked and kept; the process default (default_group_sizes) applies where it means something
         dw, da = _DEFAULT_GROUPS
         if self.weight_format is not None:
@@ -1550,17 +1645,15 @@ class QuantizeLinear(nn.Linear):
         w_bits <= 4, int8 / int16 above) + per-output-channel {s, t2} (ops.QuantExport; `dequantize()` gives back the
         value the forward multiplies with, bit for bit where overflow == 0).  Serves the w_bits >= 3 path (:195-201)."""
         if self.weight_format is not None:   # MX weights: codes + E8M0 scales (ops.MXExport); FP6 has no packing (ValueError)
-            return ops.mx_export(self.weight.detach(), self.weight_format, rotate=self.mx_rotate)   # rotated: the export of W R
+            return ops.mx_export(self.weight.detach(), self.weight_format, rotate=self.mx_rotate, scale_rule=self.mx_scale_rule)   # rotated: of W R
         if not 3 <= self.w_bits < 32:
             raise ValueError(f"export_weight serves 3 <= w_bits < 32 (SymQuantizer weights), this layer has w_bits={self.w_bits}")
         return ops.sym_export(self.weight.detach(), self.w_bits, self.weight_layerwise, container=container, group_size=self.weight_group_size)
 
     def _forward_compiled(self, input_):
         """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
-        if self.weight_format is not None and self.mx_rotate:   # llmqat_amd::mx_fake_quant_rot: Q(W R), gradient g R
-            weight = compiled.mx_fake_quant_rot_op(self.weight, self.weight_format)
-        elif self.weight_format is not None:   # MX: llmqat_amd::mx_fake_quant, identity gradient
-            weight = compiled.mx_fake_quant_op(self.weight, self.weight_format)
+        if self.weight_format is not None:   # MX: llmqat_amd::mx_fake_quant (identity gradient) / mx_fake_quant_rot (Q(W R), gradient g R), or
+            weight = _mx_apply(self.weight, self.weight_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)   # the section 16 ops
         elif self.w_bits >= 32:
             weight = self.weight
         elif self.w_bits >= 3 and self.weight_group_size is not None:   # grouped: the same custom ops on the [-1, g] view
@@ -1573,10 +1666,8 @@ class QuantizeLinear(nn.Linear):
                 absmean = self.weight.abs().mean() if self.weight_layerwise else self.weight.abs().mean(dim=1, keepdim=True)
                 sc = absmean if self.w_bits == 1 else 2 * absmean
             weight = compiled.low_bit_weight_op(self.weight, sc, self.w_bits)
-        if self.act_format is not None and self.mx_rotate:
-            input_ = compiled.mx_fake_quant_rot_op(input_, self.act_format)
-        elif self.act_format is not None:
-            input_ = compiled.mx_fake_quant_op(input_, self.act_format)
+        if self.act_format is not None:
+            input_ = _mx_apply(input_, self.act_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)
         elif 2 < self.a_bits < 32 and self.act_group_size is not None:
             g = self.act_group_size
             input_ = compiled.fake_quant(self._act_kind, input_.reshape(-1, g), _CLIP, self.a_bits, False, narrow=True).reshape(input_.shape)
@@ -1590,14 +1681,16 @@ class QuantizeLinear(nn.Linear):
     def _forward_mx(self, input_):
         """an MX layer (eager): one launch per quantized operand forward, none backward (identity gradient).  No operand pair, C++ pair
         node, weight cache or activation sharing; an operand without a format keeps its integer quantizer (uncached, unshared).
-        mx_rotate: F.linear(Q(x R), Q(W R)), still one launch per operand forward, and one rotate launch per operand gradient."""
+        mx_rotate: F.linear(Q(x R), Q(W R)), still one launch per operand forward, and one rotate launch per operand gradient.
+        mx_ste="clip": each MX operand's forward launch also writes its saturation bitmap, and its gradient is one masked launch."""
+        rule, ste = self.mx_scale_rule, self.mx_ste
         if self.mx_rotate:   # both operands have a format (the constructor's check)
-            out = nn.functional.linear(_MXRotQuantizer.apply(input_, self.act_format), _MXRotQuantizer.apply(self.weight, self.weight_format))
+            out = nn.functional.linear(_mx_apply(input_, self.act_format, True, rule, ste), _mx_apply(self.weight, self.weight_format, True, rule, ste))
             if self.bias is not None:
                 out += self.bias.view(1, -1).expand_as(out)
             return out
         if self.weight_format is not None:
-            weight = _MXQuantizer.apply(self.weight, self.weight_format)
+            weight = _mx_apply(self.weight, self.weight_format, False, rule, ste)
         elif self.w_bits >= 32:
             weight = self.weight
         elif self.weight_group_size is not None:
@@ -1607,7 +1700,7 @@ class QuantizeLinear(nn.Linear):
         else:
             weight = self._low_bit_weight(self.weight)
         if self.act_format is not None:
-            input_ = _MXQuantizer.apply(input_, self.act_format)
+            input_ = _mx_apply(input_, self.act_format, False, rule, ste)
         elif 2 < self.a_bits < 32:
             if self.act_group_size is not None:
                 input_ = _GroupQuantizer.apply(input_, _CLIP, self.a_bits, self.act_group_size, self._act_kind, True, False)

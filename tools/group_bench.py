@@ -31,6 +31,11 @@ def rotation(shape, dtype, scale=0.05):
 
 def time_variants(variants, iters, rounds, warmup=5):
     """variants: name -> fn(i) launching once on buffer set i.  -> name -> median microseconds per call"""
+    return {k: v["median"] for k, v in time_rounds(variants, iters, rounds, warmup).items()}
+
+
+def time_rounds(variants, iters, rounds, warmup=5):
+    """the same loop, keeping the spread of the rounds: name -> {"median", "min", "max"} microseconds per call"""
     for fn in variants.values():
         for i in range(warmup):
             fn(i)
@@ -45,7 +50,7 @@ def time_variants(variants, iters, rounds, warmup=5):
             b.record()
             b.synchronize()
             res[name].append(a.elapsed_time(b) * 1e3 / iters)
-    return {k: round(statistics.median(v), 2) for k, v in res.items()}
+    return {k: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)} for k, v in res.items()}
 
 
 def weight_cases(shape, dtype, groups, iters, rounds):
