@@ -359,7 +359,7 @@ int fq_sym_row_scales(const void* x, float* scales_out, int64_t rows, int64_t co
  *   row_bounds_out  optional float[rows][2]: bounds of the WHOLE row ({+m, -m} / {max, min}, as fq_*_fwd_train writes them)
  *   mask_out        optional (needs row_bounds_out): the ABI-3 row bitmap of fq_*_fwd_train, fq_ste_mask_bytes(rows, cols, dtype) bytes;
  *                   lo / hi = the STE clip.  The STE backward does not depend on the group: fq_ste_bwd_mask (copying or in place) serves it.
- * Served: groups of 4..64 16-byte vectors (bf16 / fp16: group 32, 64, 128, 256; fp32: 64, 128, 256) in rows of <= 8192 vectors.
+ * Served: groups of 4..64 16-byte vectors (bf16 / fp16: group 32, 64, 128, 256, 512; fp32: 16, 32, 64, 128, 256) in rows of <= 8192 vectors.
  * FQ_ERR_UNSUPPORTED for anything else (other divisors, float64, misaligned tensors): quantize the [rows * cols / group, group] view with
  * the row-wise entry points instead -- same values.
  */

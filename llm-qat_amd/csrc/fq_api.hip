@@ -457,7 +457,7 @@ FQ_API int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t 
     const int64_t gbytes = group * es;   // group <= cols <= 8 * REG_MAX_VEC: no overflow
     const int64_t gv = gbytes / 16;
     if (gbytes % 16 != 0 || !(gv == 4 || gv == 8 || gv == 16 || gv == 32 || gv == 64))
-        return fail(FQ_ERR_UNSUPPORTED, "group=%lld: the kernel serves groups of 4..64 16-byte vectors (bf16 / fp16 g = 32..256, fp32 g = 64..256)", (long long)group);
+        return fail(FQ_ERR_UNSUPPORTED, "group=%lld: the kernel serves groups of 4..64 16-byte vectors (bf16 / fp16 g = 32..512, fp32 g = 16..256)", (long long)group);
     if (rows > 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "rows=%lld exceeds the grid limit", (long long)rows);
     if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "x / y must be 16-byte aligned");
     const Consts c = make_consts(bits, dtype, sem);

@@ -747,7 +747,8 @@ def low_bit_weight_fused(w, w_bits):
 
 # ---- group-wise scales: every run of `group_size` consecutive elements of a row has its own scale ------------------------------------
 # y = Q(x.reshape(-1, g)).reshape(x.shape), in the arithmetic the row-wise path uses for that tensor.  Where fq_group_fwd serves the shape
-# (contiguous 16-byte aligned bf16 / fp16 / fp32, groups of 4..64 16-byte vectors, rows that fit the register kernels) it runs one launch
+# (contiguous 16-byte aligned bf16 / fp16 / fp32, groups of 4..64 16-byte vectors -- bf16 / fp16 g = 32, 64, 128, 256, 512; fp32 g = 16, 32,
+# 64, 128, 256 --, rows that fit the register kernels) it runs one launch
 # with the side outputs of the FULL row; everything else takes the row-wise kernels on the [rows * C / g, g] view (same values).  Which of
 # the two ran is counted here (utils_quant.stats() reports it): the route follows from the inputs alone.
 group_counts = {"group_launch": 0, "group_view_route": 0}
