@@ -55,6 +55,19 @@ bool set_pitch(RowPitch& p, const fq_rows_view* v, int64_t rows, int64_t cols, i
     return true;
 }
 
+// the training-mode outputs of a forward: the bitmap's place and size, the clip rounded to the dtype and its integer form
+int set_mask_args(RowArgs& a, void* mask, size_t bytes, float lo, float hi, int dtype) {
+    const int64_t mrw = mask_row_words(a.cols, esize_of(dtype));
+    if (!mrw) return fail(FQ_ERR_UNSUPPORTED, "shape not served by the STE-mask path (see fq_ste_mask_bytes)");
+    if (bytes < (size_t)a.rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)a.rows * mrw * 8);
+    a.mask = (uint64_t*)mask;
+    a.mask_row_words = mrw;
+    a.lo = host_rb(lo, dtype);
+    a.hi = host_rb(hi, dtype);
+    a.clipk = ste_clip_key(a.lo, a.hi, dtype);
+    return FQ_OK;
+}
+
 template <bool ASYM>
 int rowwise(const void* x, void* y, int32_t* idx, float* scale, float* bounds, int64_t rows, int64_t cols, int bits, int dtype,
             int sem, void* ws, size_t wsb, void* stream, const MaskArgs* mk = nullptr, const fq_rows_view* xv = nullptr,
@@ -77,25 +90,14 @@ int rowwise(const void* x, void* y, int32_t* idx, float* scale, float* bounds, i
         return fail(FQ_ERR_SHAPE, "fq_rows_view: negative stride, or more than 2^31 - 1 rows");
     if (mk) {
         if (!mk->mask || !bounds) return fail(FQ_ERR_NULL, "train-mode forward needs row_bounds_out and mask_out");
-        const int64_t mrw = mask_row_words(cols, esize_of(dtype));
-        if (!mrw) return fail(FQ_ERR_UNSUPPORTED, "shape not served by the STE-mask path (see fq_ste_mask_bytes)");
-        if (mk->bytes < (size_t)rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)rows * mrw * 8);
-        a.mask = (uint64_t*)mk->mask;
-        a.mask_row_words = mrw;
-        a.lo = host_rb(mk->lo, dtype);
-        a.hi = host_rb(mk->hi, dtype);
-        a.clipk = ste_clip_key(a.lo, a.hi, dtype);
+        if (const int rc = set_mask_args(a, mk->mask, mk->bytes, mk->lo, mk->hi, dtype)) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     // reciprocal-multiply instead of IEEE divide (only honoured for bf16).  Sym: valid for every bit width, because
     // the bin index is rint() of a bf16 value and so has an 8-bit significand itself; Asym: the divisor 2^bits-1 must
     // have one too, i.e. bits <= 8.
     const bool fast = ASYM ? bits <= 8 : true;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_rowwise<F32>(ASYM, fast, a, ws, wsb, st);
-        case FQ_DTYPE_F16: return launch_rowwise<F16>(ASYM, fast, a, ws, wsb, st);
-        default: return launch_rowwise<BF16>(ASYM, fast, a, ws, wsb, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_rowwise<decltype(dt)::value>(ASYM, fast, a, ws, wsb, st); });
 }
 
 }  // namespace
@@ -171,18 +173,10 @@ FQ_API int fq_sym_fwd_autocast(const void* x, void* y, int64_t rows, int64_t col
     RowArgs a{x, y, nullptr, nullptr, row_bounds_out, rows, cols, c.sym, c.asym, nullptr, 0, 0.f, 0.f, 0u, rows, 0, {}};
     if (mask_out) {
         if (!row_bounds_out) return fail(FQ_ERR_NULL, "a mask needs row_bounds_out too");
-        const int64_t mrw = mask_row_words(cols, 2);
-        if (!mrw) return fail(FQ_ERR_UNSUPPORTED, "shape not served by the STE-mask path (see fq_ste_mask_bytes)");
-        if (mask_bytes < (size_t)rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)rows * mrw * 8);
-        a.mask = (uint64_t*)mask_out;
-        a.mask_row_words = mrw;
-        a.lo = host_rb(lo, dtype);
-        a.hi = host_rb(hi, dtype);
-        a.clipk = ste_clip_key(a.lo, a.hi, dtype);
+        if (const int rc = set_mask_args(a, mask_out, mask_bytes, lo, hi, dtype)) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
-    return dtype == FQ_DTYPE_BF16 ? launch_sym_autocast<BF16>(wide_out != 0, a, workspace, workspace_bytes, st)
-                                  : launch_sym_autocast<F16>(wide_out != 0, a, workspace, workspace_bytes, st);
+    return by_dtype(dtype, [&](auto dt) { return launch_sym_autocast<decltype(dt)::value>(wide_out != 0, a, workspace, workspace_bytes, st); });
 }
 
 static int sym_fwd_multi_impl(int n, const fq_fwd_tensor* t, const fq_rows_view* const* xv, const fq_rows_view* const* yv, int64_t cols, int dtype,
@@ -225,13 +219,9 @@ static int sym_fwd_multi_impl(int n, const fq_fwd_tensor* t, const fq_rows_view*
     hipStream_t st = (hipStream_t)stream;
     if (autocast) {
         const bool wide = autocast == 2;  // the y are fp32; masks (if any) in the wide layout, for fq_ste_bwd_mask_wide
-        return dtype == FQ_DTYPE_BF16 ? launch_sym_autocast<BF16>(wide, a, nullptr, 0, st) : launch_sym_autocast<F16>(wide, a, nullptr, 0, st);
+        return by_dtype(dtype, [&](auto dt) { return launch_sym_autocast<decltype(dt)::value>(wide, a, nullptr, 0, st); });
     }
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_rowwise<F32>(false, true, a, nullptr, 0, st);
-        case FQ_DTYPE_F16: return launch_rowwise<F16>(false, true, a, nullptr, 0, st);
-        default: return launch_rowwise<BF16>(false, true, a, nullptr, 0, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_rowwise<decltype(dt)::value>(false, true, a, nullptr, 0, st); });
 }
 
 FQ_API int fq_sym_fwd_multi(int n, const fq_fwd_tensor* t, int64_t cols, int dtype, int sem, int autocast, float lo, float hi, void* stream) {
@@ -292,12 +282,8 @@ static int ste_bwd_mask_multi_impl(int n, const fq_bwd_tensor* t, const fq_rows_
             return fail(FQ_ERR_ARG, "an in-place tensor (gx == g) needs equal views");
     }
     hipStream_t st = (hipStream_t)stream;
-    if (wide_grad) return dtype == FQ_DTYPE_BF16 ? launch_ste_mask_wide<BF16>(L, cols, lo, hi, st) : launch_ste_mask_wide<F16>(L, cols, lo, hi, st);
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_ste_mask<F32>(L, cols, lo, hi, st);
-        case FQ_DTYPE_F16: return launch_ste_mask<F16>(L, cols, lo, hi, st);
-        default: return launch_ste_mask<BF16>(L, cols, lo, hi, st);
-    }
+    if (wide_grad) return by_dtype(dtype, [&](auto dt) { return launch_ste_mask_wide<decltype(dt)::value>(L, cols, lo, hi, st); });
+    return by_dtype(dtype, [&](auto dt) { return launch_ste_mask<decltype(dt)::value>(L, cols, lo, hi, st); });
 }
 
 FQ_API int fq_ste_bwd_mask_multi(int n, const fq_bwd_tensor* t, int64_t cols, float lo, float hi, int dtype, int wide_grad, void* stream) {
@@ -359,11 +345,7 @@ FQ_API int fq_w12_fwd(const void* w, const void* scale, void* out, int64_t rows,
     // tensor dtype on the CPU -- both give the same results (DESIGN.md "Numerics"), fp32 is used here
     const float cv = (float)(1.0 - 1e-2);
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_w12<F32>(w, scale, out, rows, cols, w_bits, scale_per_row, cv, st);
-        case FQ_DTYPE_F16: return launch_w12<F16>(w, scale, out, rows, cols, w_bits, scale_per_row, cv, st);
-        default: return launch_w12<BF16>(w, scale, out, rows, cols, w_bits, scale_per_row, cv, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_w12<decltype(dt)::value>(w, scale, out, rows, cols, w_bits, scale_per_row, cv, st); });
 }
 
 FQ_API int fq_w12_fwd_rows(const void* w, void* out, void* scale_out, int64_t rows, int64_t cols, int w_bits, int dtype, void* stream) {
@@ -374,11 +356,7 @@ FQ_API int fq_w12_fwd_rows(const void* w, void* out, void* scale_out, int64_t ro
     if (!w || !out) return fail(FQ_ERR_NULL, "w / out must not be NULL");
     const float cv = (float)(1.0 - 1e-2);
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_w12_rows<F32>(w, out, scale_out, rows, cols, w_bits, cv, st);
-        case FQ_DTYPE_F16: return launch_w12_rows<F16>(w, out, scale_out, rows, cols, w_bits, cv, st);
-        default: return launch_w12_rows<BF16>(w, out, scale_out, rows, cols, w_bits, cv, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_w12_rows<decltype(dt)::value>(w, out, scale_out, rows, cols, w_bits, cv, st); });
 }
 
 FQ_API int fq_ste_bwd(const void* g, const void* x, void* gx, int64_t n, float lo, float hi, int dtype, void* stream) {
@@ -390,11 +368,7 @@ FQ_API int fq_ste_bwd(const void* g, const void* x, void* gx, int64_t n, float l
     lo = host_rb(lo, dtype);  // the reference compares in the tensor dtype (utils_quant.py:85-86)
     hi = host_rb(hi, dtype);
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_ste<F32>(g, x, gx, n, lo, hi, st);
-        case FQ_DTYPE_F16: return launch_ste<F16>(g, x, gx, n, lo, hi, st);
-        default: return launch_ste<BF16>(g, x, gx, n, lo, hi, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_ste<decltype(dt)::value>(g, x, gx, n, lo, hi, st); });
 }
 
 FQ_API int fq_ste_bwd_rows(const void* g, const void* x, void* gx, int64_t rows, int64_t cols, float lo, float hi,
@@ -406,11 +380,7 @@ FQ_API int fq_ste_bwd_rows(const void* g, const void* x, void* gx, int64_t rows,
     lo = host_rb(lo, dtype);
     hi = host_rb(hi, dtype);
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_ste_rows<F32>(g, x, gx, rows, cols, lo, hi, row_bounds, st);
-        case FQ_DTYPE_F16: return launch_ste_rows<F16>(g, x, gx, rows, cols, lo, hi, row_bounds, st);
-        default: return launch_ste_rows<BF16>(g, x, gx, rows, cols, lo, hi, row_bounds, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_ste_rows<decltype(dt)::value>(g, x, gx, rows, cols, lo, hi, row_bounds, st); });
 }
 
 FQ_API int fq_ste_bwd_v(const void* g, const fq_rows_view* gv, const void* x, const fq_rows_view* xv, void* gx, const fq_rows_view* gxv, int64_t rows,
@@ -426,11 +396,7 @@ FQ_API int fq_ste_bwd_v(const void* g, const fq_rows_view* gv, const void* x, co
     lo = host_rb(lo, dtype);
     hi = host_rb(hi, dtype);
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_ste_rows<F32>(g, x, gx, rows, cols, lo, hi, row_bounds, st, p);
-        case FQ_DTYPE_F16: return launch_ste_rows<F16>(g, x, gx, rows, cols, lo, hi, row_bounds, st, p);
-        default: return launch_ste_rows<BF16>(g, x, gx, rows, cols, lo, hi, row_bounds, st, p);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_ste_rows<decltype(dt)::value>(g, x, gx, rows, cols, lo, hi, row_bounds, st, p); });
 }
 
 FQ_API int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t cols, int64_t group, int bits, int dtype, int sem, int autocast,
@@ -462,23 +428,13 @@ FQ_API int fq_group_fwd(int asym, const void* x, void* y, int64_t rows, int64_t 
     if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "x / y must be 16-byte aligned");
     const Consts c = make_consts(bits, dtype, sem);
     RowArgs a{x, y, nullptr, nullptr, row_bounds_out, rows, cols, c.sym, c.asym, nullptr, 0, 0.f, 0.f, 0u, rows, 0, {}};
-    if (mask_out) {
-        const int64_t mrw = mask_row_words(cols, es);
-        if (mask_bytes < (size_t)rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)rows * mrw * 8);
-        a.mask = (uint64_t*)mask_out;
-        a.mask_row_words = mrw;
-        a.lo = host_rb(lo, dtype);
-        a.hi = host_rb(hi, dtype);
-        a.clipk = ste_clip_key(a.lo, a.hi, dtype);
+    if (mask_out) {   // (the shape is served: whole vectors and at most REG_MAX_VEC of them, checked above)
+        if (const int rc = set_mask_args(a, mask_out, mask_bytes, lo, hi, dtype)) return rc;
     }
     seal_slots(a);
     hipStream_t st = (hipStream_t)stream;
     const bool fast = asym ? bits <= 8 : true;   // as rowwise(): only bf16 honours it
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_group<F32>(asym != 0, fast, 0, a, (int)gv, st);
-        case FQ_DTYPE_F16: return launch_group<F16>(asym != 0, fast, autocast, a, (int)gv, st);
-        default: return launch_group<BF16>(asym != 0, fast, autocast, a, (int)gv, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_group<decltype(dt)::value>(asym != 0, fast, autocast, a, (int)gv, st); });   // fp32: autocast == 0
 }
 
 namespace {
@@ -517,25 +473,7 @@ int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_
     const int kind = only_rot ? MX_ROT : !exp ? MX_FWD : (fmt == FQ_MX_FP4_E2M1 ? MX_EXP4 : MX_EXP8);
     hipStream_t st = (hipStream_t)stream;
     const MxFmt& f = kMxFmts[only_rot ? 0 : fmt];
-    if (ceil || mask) {   // the forms of section 16; without either, the kernels of the seven-argument entry points
-        switch (dtype) {
-            case FQ_DTYPE_F32: return launch_mx_ex<F32>(kind, rot, ceil, mask != nullptr, a, f, st);
-            case FQ_DTYPE_F16: return launch_mx_ex<F16>(kind, rot, ceil, mask != nullptr, a, f, st);
-            default: return launch_mx_ex<BF16>(kind, rot, ceil, mask != nullptr, a, f, st);
-        }
-    }
-    if (rot) {   // cols % 64 == 0: whole rotation runs
-        switch (dtype) {
-            case FQ_DTYPE_F32: return launch_mx_rot<F32>(kind, a, f, st);
-            case FQ_DTYPE_F16: return launch_mx_rot<F16>(kind, a, f, st);
-            default: return launch_mx_rot<BF16>(kind, a, f, st);
-        }
-    }
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_mx<F32>(kind, a, f, st);
-        case FQ_DTYPE_F16: return launch_mx<F16>(kind, a, f, st);
-        default: return launch_mx<BF16>(kind, a, f, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_mx<decltype(dt)::value>(kind, rot, ceil, mask != nullptr, a, f, st); });
 }
 const int kMxFlags = FQ_MX_FLAG_ROTATE | FQ_MX_FLAG_CEIL;
 }  // namespace
@@ -593,11 +531,7 @@ FQ_API int fq_mx_ste_bwd(const void* g, const void* mask, void* gx, int64_t rows
     if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
     const MxSteArgs a{g, (const uint32_t*)mask, gx, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return launch_mx_ste<F32>(rot, a, st);
-        case FQ_DTYPE_F16: return launch_mx_ste<F16>(rot, a, st);
-        default: return launch_mx_ste<BF16>(rot, a, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return launch_mx_ste<decltype(dt)::value>(rot, a, st); });
 }
 
 // Every check comes before any HIP call.

@@ -146,6 +146,17 @@ template <> struct Ty<F16> {
     }
 };
 
+// A load loop of the streaming kernels: the lane holds vectors first, first + STRIDE, ... of the `nvec` vectors at p.  A slot past the
+// end re-loads the last vector, so no load sits behind a branch; only stores are predicated.  NT is a template flag so that a kernel
+// whose policy is a run-time (block-uniform) choice calls this from both arms of its branch.
+template <bool NT, int N, int STRIDE> __device__ __forceinline__ void load_clamped(uint4 (&r)[N], const uint4* p, int64_t first, int64_t nvec) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int64_t v = first + i * STRIDE;
+        r[i] = ld16<NT>(&p[v < nvec ? v : nvec - 1]);
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // order-preserving float <-> uint key (for atomicMax-based cross-block min/max)
 // ------------------------------------------------------------------------------------

@@ -19,63 +19,23 @@ namespace fq {
 // the vector slots instead of 10 %, 576 x 3 for 13824, 320 x 2 for 5120 -- and with 256 x 6 for mid-sized tensors: within +-2 % of
 // the shapes below everywhere, profiles/r03_kbench_block_shapes.txt, r03_ab_mid_rows_256.txt) (11008 bf16 cols: 512 thr x 3 = 30.6 us, 256 x 6 = 31.1, 1024 x 2 = 32.2;
 // 4096 cols: 256 x 2 = 6.1 us, 128 x 4 = 6.3, 64 x 8 = 6.9, 512 x 1 = 7.7).
-template <int DT, bool ASYM, bool FAST, bool NTL, int NTS, bool DBG, bool PITCH = false>
+// The ladder itself is by_reg_shape (fq_launch.h); the plain and the autocast (AC = 1) forward both launch through here.
+template <int DT, bool ASYM, bool FAST, bool NTL, int NTS, bool DBG, int AC = 0, bool PITCH = false>
 static void launch_reg(const RowArgs& a, int64_t nvec, hipStream_t st) {
-#define R(TPR, V)                                                                                                   \
-    case V:                                                                                                         \
-        FQ_LAUNCH((row_reg_kernel<DT, TPR, V, ASYM, FAST, NTL, NTS, DBG, 0, PITCH>), (TPR == 64 ? (a.rows + 3) / 4 : a.rows), \
-                  (TPR == 64 ? 256 : TPR), st, a);                                                                  \
-        break;
-    if (nvec <= 192) {
-        switch ((int)((nvec + 63) / 64)) { R(64, 1) R(64, 2) R(64, 3) }
-    } else if (nvec <= 384) {
-        switch ((int)((nvec + 127) / 128)) { R(128, 2) R(128, 3) }
-    } else if (nvec <= 768) {
-        switch ((int)((nvec + 255) / 256)) { R(256, 2) R(256, 3) }
-    } else if (nvec <= 4096) {   // (5 and 7 vectors per thread run as 6 and 8: no model width lands there, see the table above launch_reg)
-        switch ((int)((nvec + 511) / 512)) { R(512, 2) R(512, 3) R(512, 4) case 5: R(512, 6) case 7: R(512, 8) }
-    } else {
-        switch ((int)((nvec + 1023) / 1024)) { case 5: R(1024, 6) case 7: R(1024, 8) }
-    }
-#undef R
-}
-
-template <int DT, int AC, bool NTL, bool NTS, bool PITCH = false>
-static void launch_reg_ac(const RowArgs& a, int64_t nvec, hipStream_t st) {
-#define R(TPR, V)                                                                                                            \
-    case V:                                                                                                                  \
-        FQ_LAUNCH((row_reg_kernel<DT, TPR, V, false, false, NTL, NTS, false, AC, PITCH>), (TPR == 64 ? (a.rows + 3) / 4 : a.rows),  \
-                  (TPR == 64 ? 256 : TPR), st, a);                                                                           \
-        break;
-    if (nvec <= 192) {
-        switch ((int)((nvec + 63) / 64)) { R(64, 1) R(64, 2) R(64, 3) }
-    } else if (nvec <= 384) {
-        switch ((int)((nvec + 127) / 128)) { R(128, 2) R(128, 3) }
-    } else if (nvec <= 768) {
-        switch ((int)((nvec + 255) / 256)) { R(256, 2) R(256, 3) }
-    } else if (nvec <= 4096) {   // (5 and 7 vectors per thread run as 6 and 8: no model width lands there, see the table above launch_reg)
-        switch ((int)((nvec + 511) / 512)) { R(512, 2) R(512, 3) R(512, 4) case 5: R(512, 6) case 7: R(512, 8) }
-    } else {
-        switch ((int)((nvec + 1023) / 1024)) { case 5: R(1024, 6) case 7: R(1024, 8) }
-    }
-#undef R
+    by_reg_shape(nvec, [&](auto tpr, auto vpt) {
+        constexpr int TPR = decltype(tpr)::value, VPT = decltype(vpt)::value;
+        launch_rows<TPR>(row_reg_kernel<DT, TPR, VPT, ASYM, FAST, NTL, NTS, DBG, AC, PITCH>, a.rows, st, a);
+    });
 }
 
 template <int DT, int TPR, bool NTL, bool NTS, bool PITCH = false>
 static void launch_wide(const RowArgs& a, int hpt, hipStream_t st) {
-    const int64_t grid = TPR == 64 ? (a.rows + 3) / 4 : a.rows;
-    constexpr int BLOCK = TPR == 64 ? 256 : TPR;
     const bool mask = any_mask(a) || PITCH;  // the mask-recording code lives in its own instantiation (it costs the plain one 7 %); pitched rows: one flavour
-    switch (hpt) {
-#define H(N)                                                                                            \
-    case N:                                                                                             \
-        if (mask) FQ_LAUNCH((row_reg_wide_kernel<DT, TPR, N, NTL, NTS, true, PITCH>), grid, BLOCK, st, a);     \
-        else if constexpr (!PITCH) FQ_LAUNCH((row_reg_wide_kernel<DT, TPR, N, NTL, NTS, false>), grid, BLOCK, st, a);         \
-        break;
-        H(1) H(2) H(3) H(4) H(5) H(6) case 7: H(8)
-#undef H
-        default: break;
-    }
+    by_count(hpt, [&](auto n) {
+        constexpr int HPT = decltype(n)::value == 7 ? 8 : decltype(n)::value;   // 7 half-vectors per thread run as 8
+        if (mask) launch_rows<TPR>(row_reg_wide_kernel<DT, TPR, HPT, NTL, NTS, true, PITCH>, a.rows, st, a);
+        else if constexpr (!PITCH) launch_rows<TPR>(row_reg_wide_kernel<DT, TPR, HPT, NTL, NTS, false>, a.rows, st, a);
+    });
 }
 
 template <int DT, int AC>
@@ -116,8 +76,8 @@ static int sym_autocast_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
                 return fail(FQ_ERR_UNSUPPORTED, "fp32-result forward with STE mask / second tensor: rows must be 8-byte aligned, cols %% 4 == 0, cols <= 32768");
             // other shapes: scalar-load kernel or two passes (bounds only)
             if (a.cols <= GENERIC_MAX_COLS) {
-                if (a.cols <= 1024) FQ_LAUNCH((row_generic_kernel<DT, 64, false, AC>), (a.rows + 3) / 4, 256, st, a);
-                else FQ_LAUNCH((row_generic_kernel<DT, 256, false, AC>), a.rows, 256, st, a);
+                if (a.cols <= 1024) launch_rows<64>(row_generic_kernel<DT, 64, false, AC>, a.rows, st, a);
+                else launch_rows<256>(row_generic_kernel<DT, 256, false, AC>, a.rows, st, a);
                 return launch_result();
             }
         } else {
@@ -126,15 +86,15 @@ static int sym_autocast_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
         }
         if (AC == 1 && vec_ok && nvec <= REG_MAX_VEC) {
             if constexpr (AC == 1) {
-                if (pitched) launch_reg_ac<DT, AC, false, true, true>(a, nvec, st);   // rows that do not follow one another: their own instantiations
-                else if (bytes >= NT_LOAD_MIN_BYTES) launch_reg_ac<DT, AC, true, true>(a, nvec, st);
-                else launch_reg_ac<DT, AC, false, true>(a, nvec, st);
+                if (pitched) launch_reg<DT, false, false, false, ST_NT, false, AC, true>(a, nvec, st);   // rows that do not follow one another: their own instantiations
+                else if (bytes >= NT_LOAD_MIN_BYTES) launch_reg<DT, false, false, true, ST_NT, false, AC>(a, nvec, st);
+                else launch_reg<DT, false, false, false, ST_NT, false, AC>(a, nvec, st);
             }
         } else if (a.mask) {
             return fail(FQ_ERR_UNSUPPORTED, "STE-mask forward needs 16-byte aligned rows that fit the register kernels");
         } else if (a.cols <= GENERIC_MAX_COLS) {
-            if (a.cols <= 1024) FQ_LAUNCH((row_generic_kernel<DT, 64, false, AC>), (a.rows + 3) / 4, 256, st, a);
-            else FQ_LAUNCH((row_generic_kernel<DT, 256, false, AC>), a.rows, 256, st, a);
+            if (a.cols <= 1024) launch_rows<64>(row_generic_kernel<DT, 64, false, AC>, a.rows, st, a);
+            else launch_rows<256>(row_generic_kernel<DT, 256, false, AC>, a.rows, st, a);
         } else {  // very long rows (layerwise): two passes -- |x| max per row through atomics, then apply
             if (pitched) return fail(FQ_ERR_UNSUPPORTED, "rows that do not follow one another: not served by the two-pass path");
             if (!ws || wsb < (size_t)a.rows * 8)
@@ -177,7 +137,7 @@ static int rowwise_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
         // the diagnostic outputs (bin indices, scales) live in their own instantiation so the product
         // kernels carry none of that code; it runs the same arithmetic with the default cache policy
         if (a.idx || a.scale) launch_reg<DT, ASYM, FAST, false, false, true>(a, nvec, st);
-        else if (pitched) launch_reg<DT, ASYM, FAST, false, true, false, true>(a, nvec, st);   // rows that do not follow one another: their own instantiations
+        else if (pitched) launch_reg<DT, ASYM, FAST, false, true, false, 0, true>(a, nvec, st);   // rows that do not follow one another: their own instantiations
         // streamed Sym tensors (the pair forward): y stores nt sc1, 2.5 % faster than nt on the W4 + A8 [4096, 11008] pair
         // (59.6 -> 58.1 us, tools/fwd_variants.hip, profiles/r06_ab_store_policy.txt); Asym keeps nt (not measured)
         else if (ntl) launch_reg<DT, ASYM, FAST, true, ASYM ? ST_NT : ST_NT_SC1, false>(a, nvec, st);
@@ -188,8 +148,8 @@ static int rowwise_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
         two_pass = two_pass_vec = true;
     } else if (a.cols <= GENERIC_MAX_COLS) {
         if (a.rows > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "rows=%lld exceeds the grid limit", (long long)a.rows);
-        if (a.cols <= 1024) FQ_LAUNCH((row_generic_kernel<DT, 64, ASYM>), (a.rows + 3) / 4, 256, st, a);
-        else FQ_LAUNCH((row_generic_kernel<DT, 256, ASYM>), a.rows, 256, st, a);
+        if (a.cols <= 1024) launch_rows<64>(row_generic_kernel<DT, 64, ASYM>, a.rows, st, a);
+        else launch_rows<256>(row_generic_kernel<DT, 256, ASYM>, a.rows, st, a);
     } else {
         two_pass = true;
     }
@@ -267,14 +227,13 @@ int launch_ste_rows(const void* g, const void* x, void* gx, int64_t rows, int64_
     if (rows * chunks > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "rows*chunks exceeds the grid limit");
     const int64_t bytes = rows * cols * T::ESIZE;
     const bool ntl = bytes >= NT_LOAD_MIN_BYTES;
-#define S(V)                                                                                                                              \
-    case V:                                                                                                                               \
-        if (pitched) FQ_LAUNCH((ste_rows_kernel<DT, V, false, true, true>), rows * chunks, STE_THREADS, st, g, x, gx, nvec_row, chunks, cv, bounds, lo, hi, pitch);  \
-        else if (ntl) FQ_LAUNCH((ste_rows_kernel<DT, V, true, true>), rows * chunks, STE_THREADS, st, g, x, gx, nvec_row, chunks, cv, bounds, lo, hi, pitch);        \
-        else FQ_LAUNCH((ste_rows_kernel<DT, V, false, true>), rows * chunks, STE_THREADS, st, g, x, gx, nvec_row, chunks, cv, bounds, lo, hi, pitch);           \
-        break;
-    switch (vpt) { S(1) S(2) S(3) S(4) S(5) S(6) S(7) S(8) }
-#undef S
+    by_count(vpt, [&](auto n) {
+        constexpr int V = decltype(n)::value;
+        auto go = [&](auto kern) { FQ_LAUNCH(kern, rows * chunks, STE_THREADS, st, g, x, gx, nvec_row, chunks, cv, bounds, lo, hi, pitch); };
+        if (pitched) go(ste_rows_kernel<DT, V, false, true, true>);
+        else if (ntl) go(ste_rows_kernel<DT, V, true, true>);
+        else go(ste_rows_kernel<DT, V, false, true>);
+    });
     return launch_result();
 }
 
@@ -320,37 +279,23 @@ template <int DT> int launch_ste_mask(SteLaunch L, int64_t cols, float lo, float
     const bool ntl = bytes >= NT_LOAD_MIN_BYTES;
     bool pitched = false;
     for (int i = 0; i < L.n; ++i) pitched = pitched || L.t[i].gp.on || L.t[i].op.on;
-    if (L.n == 1 && !L.t[0].inplace && !pitched) {   // one copying tensor: its own lean kernel (fq_kernels.h, ste_mask_one_kernel)
-        const SteSlot& t0 = L.t[0];
-#define S1(V)                                                                                                                                            \
-    case V:                                                                                                                                              \
-        if (ntl) FQ_LAUNCH2((ste_mask_one_kernel<DT, V, true, true>), grid, chunks, STE_THREADS, st, t0.g, t0.gx, t0.bounds, t0.mask, nvec_row, cv, mrw, lo, hi);   \
-        else FQ_LAUNCH2((ste_mask_one_kernel<DT, V, false, true>), grid, chunks, STE_THREADS, st, t0.g, t0.gx, t0.bounds, t0.mask, nvec_row, cv, mrw, lo, hi);      \
-        break;
-        switch (vpt) { S1(1) S1(2) S1(3) S1(4) S1(5) S1(6) S1(7) S1(8) }
-#undef S1
-        return launch_result();
-    }
-    // two tensors (a QuantizeLinear's weight + input): the slot pick looks at two slots instead of four.  Streamed gx stores nt sc1:
-    // the W4 + A8 [4096, 11008] forward + backward pair 2.0 % faster with both launches' stores nt sc1 (profiles/r06_ab_store_policy.txt)
-    if (L.n <= 2 && !pitched) {
-#define S2(V)                                                                                                                  \
-    case V:                                                                                                                    \
-        if (ntl) FQ_LAUNCH2((ste_mask_kernel<DT, V, true, ST_NT_SC1, false, 2>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);   \
-        else FQ_LAUNCH2((ste_mask_kernel<DT, V, false, true, false, 2>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);      \
-        break;
-        switch (vpt) { S2(1) S2(2) S2(3) S2(4) S2(5) S2(6) S2(7) S2(8) }
-#undef S2
-        return launch_result();
-    }
-#define S(V)                                                                                                               \
-    case V:                                                                                                                \
-        if (pitched) FQ_LAUNCH2((ste_mask_kernel<DT, V, false, true, true>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);   \
-        else if (ntl) FQ_LAUNCH2((ste_mask_kernel<DT, V, true, true>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);        \
-        else FQ_LAUNCH2((ste_mask_kernel<DT, V, false, true>), grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi);           \
-        break;
-    switch (vpt) { S(1) S(2) S(3) S(4) S(5) S(6) S(7) S(8) }
-#undef S
+    by_count(vpt, [&](auto n) {
+        constexpr int V = decltype(n)::value;
+        auto go = [&](auto kern) { FQ_LAUNCH2(kern, grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi); };
+        if (L.n == 1 && !L.t[0].inplace && !pitched) {   // one copying tensor: its own lean kernel (fq_kernels.h, ste_mask_one_kernel)
+            const SteSlot& t0 = L.t[0];
+            auto one = [&](auto kern) { FQ_LAUNCH2(kern, grid, chunks, STE_THREADS, st, t0.g, t0.gx, t0.bounds, t0.mask, nvec_row, cv, mrw, lo, hi); };
+            if (ntl) one(ste_mask_one_kernel<DT, V, true, true>);
+            else one(ste_mask_one_kernel<DT, V, false, true>);
+        } else if (L.n <= 2 && !pitched) {
+            // two tensors (a QuantizeLinear's weight + input): the slot pick looks at two slots instead of four.  Streamed gx stores nt sc1: the
+            // W4 + A8 [4096, 11008] forward + backward pair 2.0 % faster with both launches' stores nt sc1 (profiles/r06_ab_store_policy.txt)
+            if (ntl) go(ste_mask_kernel<DT, V, true, ST_NT_SC1, false, 2>);
+            else go(ste_mask_kernel<DT, V, false, true, false, 2>);
+        } else if (pitched) go(ste_mask_kernel<DT, V, false, true, true>);
+        else if (ntl) go(ste_mask_kernel<DT, V, true, true>);
+        else go(ste_mask_kernel<DT, V, false, true>);
+    });
     return launch_result();
 }
 
@@ -377,24 +322,16 @@ template <int DT> int launch_ste_mask_wide(SteLaunch L, int64_t cols, float lo, 
         const bool ntl = bytes >= NT_LOAD_MIN_BYTES;
         bool pitched = false;
         for (int i = 0; i < L.n; ++i) pitched = pitched || L.t[i].gp.on || L.t[i].op.on;
-        if (!ntl && !pitched && L.n <= 2) {   // the K / V-sized launches: one or two slots instead of a four-slot pick in every block's prologue
-#define SN(V)                                                                                                                                  \
-    case V:                                                                                                                                    \
-        if (L.n == 1) FQ_LAUNCH2((ste_mask_wide_kernel<DT, V, false, true, false, 1>), grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi);        \
-        else FQ_LAUNCH2((ste_mask_wide_kernel<DT, V, false, true, false, 2>), grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi);                 \
-        break;
-            switch (hpt) { SN(1) SN(2) SN(3) SN(4) SN(5) SN(6) SN(7) SN(8) }
-#undef SN
-            return launch_result();
-        }
-#define S(V)                                                                                                                  \
-    case V:                                                                                                                   \
-        if (pitched) FQ_LAUNCH2((ste_mask_wide_kernel<DT, V, false, true, true>), grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi);   \
-        else if (ntl) FQ_LAUNCH2((ste_mask_wide_kernel<DT, V, true, true>), grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi);        \
-        else FQ_LAUNCH2((ste_mask_wide_kernel<DT, V, false, true>), grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi);           \
-        break;
-        switch (hpt) { S(1) S(2) S(3) S(4) S(5) S(6) S(7) S(8) }
-#undef S
+        by_count(hpt, [&](auto n) {
+            constexpr int V = decltype(n)::value;
+            auto go = [&](auto kern) { FQ_LAUNCH2(kern, grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi); };
+            if (!ntl && !pitched && L.n <= 2) {   // the K / V-sized launches: one or two slots instead of a four-slot pick in every block's prologue
+                if (L.n == 1) go(ste_mask_wide_kernel<DT, V, false, true, false, 1>);
+                else go(ste_mask_wide_kernel<DT, V, false, true, false, 2>);
+            } else if (pitched) go(ste_mask_wide_kernel<DT, V, false, true, true>);
+            else if (ntl) go(ste_mask_wide_kernel<DT, V, true, true>);
+            else go(ste_mask_wide_kernel<DT, V, false, true>);
+        });
         return launch_result();
     }
 }

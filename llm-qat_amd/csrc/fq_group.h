@@ -44,14 +44,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void group_reg_kernel(RowArg
 
     int64_t row;
     int t;
-    if constexpr (TPR == 64) {
-        row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-        t = threadIdx.x & 63;
-        if (row >= a.rows) return;  // wave-uniform
-    } else {
-        row = blockIdx.x;
-        t = threadIdx.x;
-    }
+    if (!row_and_lane<TPR>(a.rows, row, t)) return;
     const int nvec = (int)(a.cols / EPV);
     const uint4* __restrict__ xr = (const uint4*)((const char*)a.x + row * a.cols * T::ESIZE);
     uint4* __restrict__ yr = (uint4*)((char*)a.y + row * a.cols * T::ESIZE);
@@ -193,24 +186,27 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void group_reg_kernel(RowArg
     }
 }
 
-// Launch shapes: the (threads per row, vectors per thread) of launch_reg for the model widths (bf16 4096 -> 256 x 2, 5120 -> 256 x 3,
-// 11008 -> 512 x 3, 13824 -> 512 x 4), fewer in between; the vector count must also hold every group (nvec <= TPR * VPT).
+// Launch shapes: the (threads per row, vectors per thread) of by_reg_shape for the model widths (bf16 4096 -> 256 x 2, 5120 -> 256 x 3,
+// 11008 -> 512 x 3, 13824 -> 512 x 4), fewer in between and a ladder of its own: every rung must hold whole groups (TPR * VPT a
+// multiple of 64 vectors, nvec <= TPR * VPT), which 64 x 3, 128 x 3, 512 x 6 and 1024 x 6 do not for gv = 64.
+template <class F> inline void by_group_shape(int64_t nvec, F&& f) {
+    if (nvec <= 64) f(Const<64>{}, Const<1>{});
+    else if (nvec <= 128) f(Const<64>{}, Const<2>{});
+    else if (nvec <= 256) f(Const<128>{}, Const<2>{});
+    else if (nvec <= 512) f(Const<256>{}, Const<2>{});
+    else if (nvec <= 768) f(Const<256>{}, Const<3>{});
+    else if (nvec <= 1024) f(Const<512>{}, Const<2>{});
+    else if (nvec <= 1536) f(Const<512>{}, Const<3>{});
+    else if (nvec <= 2048) f(Const<512>{}, Const<4>{});
+    else if (nvec <= 4096) f(Const<1024>{}, Const<4>{});
+    else f(Const<1024>{}, Const<8>{});
+}
 template <int DT, bool ASYM, bool FAST, int AC>
 static void launch_group_shape(const RowArgs& a, int64_t nvec, GroupArgs ga, hipStream_t st) {
-#define G(TPR, V)                                                                                                                   \
-    FQ_LAUNCHK((group_reg_kernel<DT, TPR, V, ASYM, FAST, AC>), dim3((unsigned)(TPR == 64 ? (a.rows + 3) / 4 : a.rows)),            \
-               dim3(TPR == 64 ? 256 : TPR), 0, st, a, ga)
-    if (nvec <= 64) G(64, 1);
-    else if (nvec <= 128) G(64, 2);
-    else if (nvec <= 256) G(128, 2);
-    else if (nvec <= 512) G(256, 2);
-    else if (nvec <= 768) G(256, 3);
-    else if (nvec <= 1024) G(512, 2);
-    else if (nvec <= 1536) G(512, 3);
-    else if (nvec <= 2048) G(512, 4);
-    else if (nvec <= 4096) G(1024, 4);
-    else G(1024, 8);
-#undef G
+    by_group_shape(nvec, [&](auto tpr, auto vpt) {
+        constexpr int TPR = decltype(tpr)::value, VPT = decltype(vpt)::value;
+        launch_rows<TPR>(group_reg_kernel<DT, TPR, VPT, ASYM, FAST, AC>, a.rows, st, a, ga);
+    });
 }
 
 // a: x / y / rows / cols / sym / asym constants and (training mode) bounds + mask, validated by fq_group_fwd; gv: vectors per group

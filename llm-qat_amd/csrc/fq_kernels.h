@@ -163,10 +163,28 @@ template <int DT> __device__ __forceinline__ uint4 ste_mask_apply(const uint4& g
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// (Which tensor of a multi-tensor launch a row belongs to is decided by a short branch chain in the kernels below: a
-// branch-free variant -- all slots' kernarg fields loaded up front, chosen with selects, as the mask backward does -- measured
-// 2-4 % SLOWER on the [2048,4096] forward launches, profiles/r03_ab_forward_pick_tensor.txt: the single-tensor launch pays one
-// compare today.)
+// Which row and which lane a thread of a row kernel is: TPR == 64 puts four rows, one per wave, into a 256-thread block; wider rows own
+// a block each.  false (TPR == 64 only, wave-uniform): the wave's row lies past the last one and the kernel returns.
+// (row_reg_kernel and row_reg_wide_kernel keep these lines written out: through the helper the register allocation of their TPR == 64
+// instantiations for pitched rows comes out differently.)
+template <int TPR> __device__ __forceinline__ bool row_and_lane(int64_t rows, int64_t& row, int& t) {
+    if constexpr (TPR == 64) {
+        row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+        t = threadIdx.x & 63;
+        return row < rows;
+    } else {
+        row = blockIdx.x;
+        t = threadIdx.x;
+        return true;
+    }
+}
+
+// Which tensor of a multi-tensor launch a row belongs to is decided by a short branch chain, written out in row_reg_kernel and in
+// row_reg_wide_kernel ("which tensor of the launch").  Two forms were tried and dropped.  A branch-free variant -- all slots' kernarg
+// fields loaded up front, chosen with selects, as the mask backward does -- measured 2-4 % SLOWER on the [2048,4096] forward launches,
+// profiles/r03_ab_forward_pick_tensor.txt: the single-tensor launch pays one compare today.  And the chain as a function of its own
+// (by reference, by pointer or returning a struct) compiles to that select form again: the compiler simplifies the function before it
+// inlines it, and there the slots' loads no longer sit behind the branches.
 // ------------------------------------------------------------------------------------
 // Register-resident row kernel.
 //   nvec = cols / elements-per-16B must satisfy nvec <= TPR * VPT.
@@ -537,14 +555,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_generic_kernel(RowA
     __shared__ uint32_t red[3][NW > 1 ? NW : 1];
     int64_t row;
     int t;
-    if constexpr (TPR == 64) {
-        row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-        t = threadIdx.x & 63;
-        if (row >= a.rows) return;
-    } else {
-        row = blockIdx.x;
-        t = threadIdx.x;
-    }
+    if (!row_and_lane<TPR>(a.rows, row, t)) return;
     const int64_t base = row * a.cols;   // (the debug index output is always contiguous)
     const int64_t cols = a.cols;
     const int64_t xbase = row_byte_off(row, cols * T::ESIZE, a.xp) / T::ESIZE;                                       // in elements

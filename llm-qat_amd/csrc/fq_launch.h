@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -47,6 +48,54 @@ inline int launch_result() {
 // (drop-in for the hipLaunchKernelGGL call shape; the kernels use no dynamic LDS)
 #define FQ_LAUNCHK(kern, grid, block, shmem, st, ...) ::fq::launch(kern, grid, block, st, __VA_ARGS__)
 
+// ---- run-time choices -> template arguments: the callable receives std::integral_constant values and reads them as constants ----
+template <int V> using Const = std::integral_constant<int, V>;
+// element type of the three per-dtype translation units (dtype: a validated FQ_DTYPE_* code other than F64)
+template <class F> inline int by_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case FQ_DTYPE_F32: return f(Const<F32>{});
+        case FQ_DTYPE_F16: return f(Const<F16>{});
+        default: return f(Const<BF16>{});
+    }
+}
+// a count of 16-byte vectors (or 8-byte half-vectors) per thread, 1 .. 8, as the backward kernels and the fp32-result forward take it
+template <class F> inline void by_count(int n, F&& f) {
+    switch (n) {
+        case 1: f(Const<1>{}); break;
+        case 2: f(Const<2>{}); break;
+        case 3: f(Const<3>{}); break;
+        case 4: f(Const<4>{}); break;
+        case 5: f(Const<5>{}); break;
+        case 6: f(Const<6>{}); break;
+        case 7: f(Const<7>{}); break;
+        case 8: f(Const<8>{}); break;
+        default: break;
+    }
+}
+// Launch shape of the register-resident row kernels for a row of nvec 16-byte vectors (nvec <= REG_MAX_VEC): f(threads per row,
+// vectors per thread), the smallest rung that holds the row.  5 and 7 vectors per thread run as 6 and 8 (no model width lands there;
+// why these rungs: the comment above launch_reg in fq_dtype_impl.h).
+template <class F> inline void by_reg_shape(int64_t nvec, F&& f) {
+    if (nvec <= 64) f(Const<64>{}, Const<1>{});
+    else if (nvec <= 128) f(Const<64>{}, Const<2>{});
+    else if (nvec <= 192) f(Const<64>{}, Const<3>{});
+    else if (nvec <= 256) f(Const<128>{}, Const<2>{});
+    else if (nvec <= 384) f(Const<128>{}, Const<3>{});
+    else if (nvec <= 512) f(Const<256>{}, Const<2>{});
+    else if (nvec <= 768) f(Const<256>{}, Const<3>{});
+    else if (nvec <= 1024) f(Const<512>{}, Const<2>{});
+    else if (nvec <= 1536) f(Const<512>{}, Const<3>{});
+    else if (nvec <= 2048) f(Const<512>{}, Const<4>{});
+    else if (nvec <= 3072) f(Const<512>{}, Const<6>{});
+    else if (nvec <= 4096) f(Const<512>{}, Const<8>{});
+    else if (nvec <= 6144) f(Const<1024>{}, Const<6>{});
+    else f(Const<1024>{}, Const<8>{});
+}
+// one launch of a row kernel over `rows` rows: TPR == 64 puts four rows into a 256-thread block (fq_kernels.h row_and_lane)
+template <int TPR, typename... P, typename... A> inline void launch_rows(void (*kernel)(P...), int64_t rows, hipStream_t st, A&&... a) {
+    launch(kernel, dim3((unsigned)(TPR == 64 ? (rows + 3) / 4 : rows)), dim3(TPR == 64 ? 256 : TPR), st, std::forward<A>(a)...);
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // pitched rows (RowPitch): every row start must keep the alignment the vector kernels assume
 inline bool pitch_aligned(const RowPitch& p, int64_t mask) { return !p.on || (((p.outer | p.inner) & mask) == 0); }
@@ -67,7 +116,7 @@ inline bool more_aligned(const RowArgs& a, uintptr_t xmask, uintptr_t ymask) {
         if ((reinterpret_cast<uintptr_t>(a.more[i].x) & xmask) || (reinterpret_cast<uintptr_t>(a.more[i].y) & ymask)) return false;
     return true;
 }
-// the kernels compare a row against every slot's first row (pick_tensor): unused slots must never match
+// the kernels compare a row against every slot's first row ("which tensor of the launch" in row_reg_kernel): unused slots must never match
 inline void seal_slots(RowArgs& a) {
     for (int i = a.n_more; i < MAX_MORE; ++i) {
         a.more[i] = TensorSlot{};
@@ -194,7 +243,7 @@ struct MxFmt {
 struct MxArgs {
     const void* x;
     void* y;             // MX_FWD / MX_ROT
-    uint8_t* elems;      // MX_EXP4 / MX_EXP8; MX_FWD with the saturation bitmap (launch_mx_ex, mask = true): the bitmap, one little-endian
+    uint8_t* elems;      // MX_EXP4 / MX_EXP8; MX_FWD with the saturation bitmap (launch_mx, mask = true): the bitmap, one little-endian
                          // 32-bit word per block (bit = 0: saturation changed the element)
     uint8_t* scales;     // MX_EXP4 / MX_EXP8
     int64_t nvec;        // 16-byte vectors of the tensor: a multiple of the block's vector count
@@ -209,14 +258,11 @@ struct MxSteArgs {
     int ntl;
 };
 template <int DT> FQ_HIDDEN int launch_mx_ste(bool rot, MxSteArgs a, hipStream_t st);
-template <int DT> FQ_HIDDEN int launch_mx(int kind, MxArgs a, MxFmt f, hipStream_t st);
-// the same kinds on x R (R block-diagonal along the last dimension, blocks H64 / 8), and MX_ROT: y = x R alone (f unused); nvec is a
-// multiple of the run's vector count
-template <int DT> FQ_HIDDEN int launch_mx_rot(int kind, MxArgs a, MxFmt f, hipStream_t st);
-// the forms of section 16 (fq_mx_fwd_ex / fq_mx_export_ex with the ceil rule and / or the bitmap): kind MX_FWD / MX_EXP4 / MX_EXP8, on x or
-// (rot) x R; ceil: the no-clip scale rule; mask (MX_FWD only): also write the bitmap to a.elems.  The rule is a template parameter of the
-// kernels, so launch_mx / launch_mx_rot run the code they always ran.
-template <int DT> FQ_HIDDEN int launch_mx_ex(int kind, bool rot, bool ceil, bool mask, MxArgs a, MxFmt f, hipStream_t st);
+// kind MX_FWD / MX_EXP4 / MX_EXP8 on x, or (rot) on x R (R block-diagonal along the last dimension, blocks H64 / 8; nvec is then a
+// multiple of the run's vector count); ceil: the no-clip scale rule of section 16; mask (MX_FWD only): also write the bitmap to a.elems.
+// kind MX_ROT (with rot): y = x R alone (f, ceil and mask unused).  All four are template parameters of mx_kernel, so every entry point
+// runs the instantiation it always ran.
+template <int DT> FQ_HIDDEN int launch_mx(int kind, bool rot, bool ceil, bool mask, MxArgs a, MxFmt f, hipStream_t st);
 // MX block-scaled GEMM (fq_mx_gemm.h / fq_mx_gemm.hip): out[m, n] = sum_k A[m, k] * W[n, k] over two MX exports
 struct MxGemmArgs {
     const uint8_t* we;   // W: [N, K] element codes, E8M0 scales [N, K / 32]

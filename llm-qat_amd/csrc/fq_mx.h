@@ -141,19 +141,8 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
     // Out-of-range slots re-load the last vector: nvec is a multiple of BV and segments are BV-aligned, so such a slot's whole block
     // is out of range and is never stored.  (ROT: nvec is a multiple of the run's vector count and runs are aligned, likewise.)
     uint4 r[VPT];
-    if (a.ntl) {
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int64_t v = base + i * MX_TPB;
-            r[i] = ld16<true>(&xv[v < a.nvec ? v : a.nvec - 1]);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int64_t v = base + i * MX_TPB;
-            r[i] = ld16<false>(&xv[v < a.nvec ? v : a.nvec - 1]);
-        }
-    }
+    if (a.ntl) load_clamped<true, VPT, MX_TPB>(r, xv, base, a.nvec);
+    else load_clamped<false, VPT, MX_TPB>(r, xv, base, a.nvec);
 
     const int bmin = f.emin + 127;
 #pragma unroll
@@ -339,19 +328,21 @@ static void launch_mx_kind(const MxArgs& a, const MxFmt& f, hipStream_t st) {
     const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
     FQ_LAUNCHK((mx_kernel<DT, KIND, MX_VPT, ROT, MASK, CEIL>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a, f);
 }
-template <int DT, bool ROT, bool CEIL> static void launch_mx_ex_kind(int kind, bool mask, const MxArgs& a, const MxFmt& f, hipStream_t st) {
+template <int DT, bool ROT, bool CEIL> static void launch_mx_rule(int kind, bool mask, const MxArgs& a, const MxFmt& f, hipStream_t st) {
     if (kind == MX_FWD && mask) launch_mx_kind<DT, MX_FWD, ROT, true, CEIL>(a, f, st);
     else if (kind == MX_FWD) launch_mx_kind<DT, MX_FWD, ROT, false, CEIL>(a, f, st);
     else if (kind == MX_EXP4) launch_mx_kind<DT, MX_EXP4, ROT, false, CEIL>(a, f, st);
     else launch_mx_kind<DT, MX_EXP8, ROT, false, CEIL>(a, f, st);
 }
-// validated by fq_mx_fwd_ex / fq_mx_export_ex; the combinations without ceil and without mask go through launch_mx / launch_mx_rot
-template <int DT> int launch_mx_ex(int kind, bool rot, bool ceil, bool mask, MxArgs a, MxFmt f, hipStream_t st) {
+// a and f validated by mx_entry (fq_api.hip): nvec > 0, grid within limits, rot: whole rotation runs, mask only with MX_FWD, MX_ROT only
+// with rot and without ceil / mask
+template <int DT> int launch_mx(int kind, bool rot, bool ceil, bool mask, MxArgs a, MxFmt f, hipStream_t st) {
     begin_launches();
-    if (rot && ceil) launch_mx_ex_kind<DT, true, true>(kind, mask, a, f, st);
-    else if (rot) launch_mx_ex_kind<DT, true, false>(kind, mask, a, f, st);
-    else if (ceil) launch_mx_ex_kind<DT, false, true>(kind, mask, a, f, st);
-    else launch_mx_ex_kind<DT, false, false>(kind, mask, a, f, st);
+    if (kind == MX_ROT) launch_mx_kind<DT, MX_ROT, true>(a, f, st);
+    else if (rot && ceil) launch_mx_rule<DT, true, true>(kind, mask, a, f, st);
+    else if (rot) launch_mx_rule<DT, true, false>(kind, mask, a, f, st);
+    else if (ceil) launch_mx_rule<DT, false, true>(kind, mask, a, f, st);
+    else launch_mx_rule<DT, false, false>(kind, mask, a, f, st);
     return launch_result();
 }
 
@@ -364,29 +355,8 @@ template <int DT> int launch_mx_ste(bool rot, MxSteArgs a, hipStream_t st) {
     return launch_result();
 }
 
-// kind: MX_FWD / MX_EXP4 / MX_EXP8; a and f validated by fq_mx_fwd / fq_mx_export (nvec > 0, grid within limits)
-template <int DT> int launch_mx(int kind, MxArgs a, MxFmt f, hipStream_t st) {
-    begin_launches();
-    if (kind == MX_FWD) launch_mx_kind<DT, MX_FWD>(a, f, st);
-    else if (kind == MX_EXP4) launch_mx_kind<DT, MX_EXP4>(a, f, st);
-    else launch_mx_kind<DT, MX_EXP8>(a, f, st);
-    return launch_result();
-}
-
-// kind: MX_FWD / MX_EXP4 / MX_EXP8 on x R, or MX_ROT; validated by fq_mx_fwd_rot / fq_mx_export_rot / fq_block_rotate
-template <int DT> int launch_mx_rot(int kind, MxArgs a, MxFmt f, hipStream_t st) {
-    begin_launches();
-    if (kind == MX_FWD) launch_mx_kind<DT, MX_FWD, true>(a, f, st);
-    else if (kind == MX_EXP4) launch_mx_kind<DT, MX_EXP4, true>(a, f, st);
-    else if (kind == MX_EXP8) launch_mx_kind<DT, MX_EXP8, true>(a, f, st);
-    else launch_mx_kind<DT, MX_ROT, true>(a, f, st);
-    return launch_result();
-}
-
 #define FQ_INSTANTIATE_MX(DT)                                              \
-    template int launch_mx<DT>(int, MxArgs, MxFmt, hipStream_t); \
-    template int launch_mx_rot<DT>(int, MxArgs, MxFmt, hipStream_t); \
-    template int launch_mx_ste<DT>(bool, MxSteArgs, hipStream_t);        \
-    template int launch_mx_ex<DT>(int, bool, bool, bool, MxArgs, MxFmt, hipStream_t);
+    template int launch_mx<DT>(int, bool, bool, bool, MxArgs, MxFmt, hipStream_t); \
+    template int launch_mx_ste<DT>(bool, MxSteArgs, hipStream_t);
 
 }  // namespace fq

@@ -312,7 +312,7 @@ static void launch_sym(const void* x, void* y, float* bounds, int64_t rows, int6
     a.x = x; a.y = y; a.idx = nullptr; a.scale = nullptr; a.bounds = bounds; a.rows = rows; a.rows0 = rows; a.cols = cols;
     a.sym.qmax = (float)((1 << (bits - 1)) - 1);
     a.sym.c6 = 9.98377799987793e-07f;
-    for (int i = 0; i < MAX_MORE; ++i) a.more[i].row_begin = INT64_MAX;  // single tensor: no slot may match (pick_tensor)
+    for (int i = 0; i < MAX_MORE; ++i) a.more[i].row_begin = INT64_MAX;  // single tensor: no slot may match ("which tensor of the launch" in row_reg_kernel)
     const int64_t grid = TPR == 64 ? (rows + 3) / 4 : rows;
     hipLaunchKernelGGL((row_reg_kernel<BF16, TPR, VPT, false, FAST, NTL, NTS>), dim3((unsigned)grid), dim3(TPR == 64 ? 256 : TPR), 0, 0, a);
 }
