@@ -301,6 +301,7 @@ pybind11::object pair_forward(const at::Tensor& weight, const at::Tensor& input,
     at::Tensor wq = at::empty_like(weight), xq = at::empty_like(input), side_w, side_x;
     uint8_t *pw = nullptr, *px = nullptr;
     const auto bytes = weight.options().dtype(at::kByte);
+    // the side buffer's layout (float[rows][2] bounds, then the row bitmap) is ops.py's SIDE_ROW_BYTES / _side_alloc / split_side: keep the two in step
     if (need_w) {
         side_w = at::empty({rows_w * 8 + mw}, bytes);
         pw = static_cast<uint8_t*>(side_w.data_ptr());

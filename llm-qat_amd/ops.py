@@ -78,34 +78,6 @@ def _prep(x, what):
     return code
 
 
-def _on_device(x, call):
-    """run `call(stream)` with x's device current (the common case -- it already is -- costs one C call)"""
-    idx = x.device.index
-    cur = _cur_dev()
-    if idx is None or idx == cur:
-        return call(_raw_stream(cur))
-    with torch.cuda.device(idx):
-        return call(_raw_stream(idx))
-
-
-class _DeviceOf:
-    """Make x's device current for the launch if it is not already."""
-
-    def __init__(self, x):
-        self.idx = x.device.index
-        self.prev = None
-
-    def __enter__(self):
-        cur = _cur_dev()
-        if self.idx is not None and self.idx != cur:
-            self.prev = cur
-            torch.cuda.set_device(self.idx)
-
-    def __exit__(self, *exc):
-        if self.prev is not None:
-            torch.cuda.set_device(self.prev)
-
-
 # The raw current-stream handle / current device index straight from the C bindings (what Inductor's generated code uses):
 # 0.2 us per call instead of the 2-3 us `torch.cuda.current_stream().cuda_stream` spends building a Stream object.
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -121,15 +93,84 @@ def _stream(x):
     return _raw_stream(_cur_dev() if idx is None else idx)
 
 
-_ws_bytes_memo = {}
+def _launch(t, fn, *args):
+    """fn(*args, stream) -> its status code, on the current stream of t's device; that device is made current for the call only where it
+    is not already (and restored).  Every launch function of the C ABI takes the stream last."""
+    cur = _cur_dev()
+    idx = t.device.index
+    if idx is None or idx == cur:
+        return fn(*args, _raw_stream(cur))
+    torch.cuda.set_device(idx)
+    try:
+        return fn(*args, _raw_stream(idx))
+    finally:
+        torch.cuda.set_device(cur)
 
 
-def _ws_bytes(rows, cols, code):
-    k = (rows, cols, code)
-    v = _ws_bytes_memo.get(k)
-    if v is None:
-        v = _ws_bytes_memo[k] = _lib.lib().fq_rowwise_workspace_bytes(rows, cols, code)
-    return v
+def _served(rc, what):
+    """status code of a launch -> True (done) | False (FQ_ERR_UNSUPPORTED: the caller takes its other route); anything else raises"""
+    if rc:
+        if rc == _lib.ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc, what)
+    return True
+
+
+def _size_query(name):
+    """a byte-size query of the C ABI over (rows, cols, dtype code), memoised"""
+    memo = {}
+
+    def query(rows, cols, code):
+        k = (rows, cols, code)
+        v = memo.get(k)
+        if v is None:
+            v = memo[k] = getattr(_lib.lib(), name)(rows, cols, code)
+        return v
+    return query
+
+
+_ws_bytes = _size_query("fq_rowwise_workspace_bytes")
+_mask_bytes = _size_query("fq_ste_mask_bytes")
+
+
+# ---- the side buffer of a training forward: one uint8 allocation, float[rows][2] row bounds followed by the STE row bitmap.  The C++ node
+# (csrc/fq_autograd_node.cpp) allocates and splits the same layout on its own: a change here is a change there.
+SIDE_ROW_BYTES = 8   # one row's bounds: 2 floats
+
+
+def _side_alloc(rows, mask_bytes, device):
+    """-> (side, bounds pointer, mask pointer)"""
+    side = torch.empty(rows * SIDE_ROW_BYTES + mask_bytes, dtype=torch.uint8, device=device)
+    sp = side.data_ptr()
+    return side, sp, sp + rows * SIDE_ROW_BYTES
+
+
+_NO_SIDE = (None, None, None)   # what _side_alloc's callers pass for a tensor that records nothing
+
+
+def _side_ptrs(side, rows):
+    """-> (bounds pointer, mask pointer) of a side buffer"""
+    sp = side.data_ptr()
+    return sp, sp + rows * SIDE_ROW_BYTES
+
+
+def split_side(side, rows):
+    """A side buffer -> (bounds float32 [rows, 2], mask uint8), views of its storage."""
+    n = rows * SIDE_ROW_BYTES
+    return side[:n].view(torch.float32).view(rows, 2), side[n:]
+
+
+def _contig(x):
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def _like_input(x, xc, y):
+    """y, computed from xc = _contig(x), in the layout the reference's elementwise ops give x's result (empty_like's strides)"""
+    if xc is x:
+        return y
+    out = torch.empty_like(x, dtype=y.dtype)
+    out.copy_(y)
+    return out
 
 
 def _empty_input(what, x, layerwise):
@@ -185,6 +226,11 @@ def _strided_out(x, dtype=None):
 _views_served = 0   # launches that took a view instead of a copy (tests read it)
 
 
+def _view_served():
+    global _views_served
+    _views_served += 1
+
+
 def _rowwise(kind, x, num_bits, layerwise, want_bounds, debug):
     what = f"{kind}_quantize"
     code = _prep(x, what)
@@ -199,15 +245,12 @@ def _rowwise(kind, x, num_bits, layerwise, want_bounds, debug):
         y, yv = _strided_out(x)
         if yv is not False:
             bounds = torch.empty((rows, 2), dtype=torch.float32, device=x.device) if want_bounds else None
-            with _DeviceOf(x):
-                rc = L.fq_rowwise_fwd_v(1 if kind == "asym" else 0, x.data_ptr(), _rv(xv), y.data_ptr(), _rv(yv), rows, cols, int(num_bits), code, _semantics,
-                                        0.0, 0.0, bounds.data_ptr() if want_bounds else None, None, 0, _stream(x))
-            if rc != _lib.ERR_UNSUPPORTED:
-                _lib.check(rc, what)
-                global _views_served
-                _views_served += 1
+            rc = _launch(x, L.fq_rowwise_fwd_v, 1 if kind == "asym" else 0, x.data_ptr(), _rv(xv), y.data_ptr(), _rv(yv), rows, cols, int(num_bits), code,
+                         _semantics, 0.0, 0.0, bounds.data_ptr() if want_bounds else None, None, 0)
+            if _served(rc, what):
+                _view_served()
                 return y, bounds, None, None
-    xc = x if x.is_contiguous() else x.contiguous()
+    xc = _contig(x)
     y = torch.empty_like(xc)
     ws_bytes = _ws_bytes(rows, cols, code)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
@@ -215,44 +258,26 @@ def _rowwise(kind, x, num_bits, layerwise, want_bounds, debug):
     bounds = idx = scale = None
     if code == _lib.DTYPE_F64:
         want_bounds = False   # float64: a correctness path without training-mode side buffers (the backward re-reads x)
-    with _DeviceOf(x):
-        if debug:
-            idx = torch.empty(xc.shape, dtype=torch.int32, device=x.device)
-            scale = torch.empty((rows,) if kind == "sym" else (rows, 2), dtype=torch.float32, device=x.device)
-            fn = L.fq_sym_fwd_debug if kind == "sym" else L.fq_asym_fwd_debug
-            rc = fn(xc.data_ptr(), y.data_ptr(), idx.data_ptr(), scale.data_ptr(), rows, cols, int(num_bits), code,
-                    _semantics, ws_ptr, ws_bytes, _stream(x))
-        else:
-            if want_bounds:
-                bounds = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-            fn = L.fq_sym_fwd if kind == "sym" else L.fq_asym_fwd
-            rc = fn(xc.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _semantics,
-                    bounds.data_ptr() if bounds is not None else None, ws_ptr, ws_bytes, _stream(x))
+    if debug:
+        idx = torch.empty(xc.shape, dtype=torch.int32, device=x.device)
+        scale = torch.empty((rows,) if kind == "sym" else (rows, 2), dtype=torch.float32, device=x.device)
+        rc = _launch(x, L.fq_sym_fwd_debug if kind == "sym" else L.fq_asym_fwd_debug, xc.data_ptr(), y.data_ptr(), idx.data_ptr(), scale.data_ptr(),
+                     rows, cols, int(num_bits), code, _semantics, ws_ptr, ws_bytes)
+    else:
+        if want_bounds:
+            bounds = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+        rc = _launch(x, L.fq_sym_fwd if kind == "sym" else L.fq_asym_fwd, xc.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _semantics,
+                     bounds.data_ptr() if bounds is not None else None, ws_ptr, ws_bytes)
     _lib.check(rc, what)
-    if xc is not x:  # keep the input's strides, as the reference's elementwise ops do
-        out = torch.empty_like(x)
-        out.copy_(y)
-        y = out
-        if idx is not None:
-            idx = idx.reshape(x.shape)
-    return y, bounds, idx, scale
+    if idx is not None and xc is not x:
+        idx = idx.reshape(x.shape)
+    return _like_input(x, xc, y), bounds, idx, scale
 
 
 # ---- lean path used by the autograd Functions: one side allocation (row bounds + STE mask), memoised sizes ----
-_mask_bytes_memo = {}
-
-
-def _mask_bytes(rows, cols, code):
-    k = (rows, cols, code)
-    v = _mask_bytes_memo.get(k)
-    if v is None:
-        v = _mask_bytes_memo[k] = _lib.lib().fq_ste_mask_bytes(rows, cols, code)
-    return v
-
-
 def _aligned(g):
     """contiguous and 16-byte aligned (a gradient can be an offset view into a larger buffer)"""
-    g = g if g.is_contiguous() else g.contiguous()
+    g = _contig(g)
     return g.clone() if g.data_ptr() & 15 else g
 
 
@@ -280,33 +305,19 @@ def train_forward(kind, x, num_bits, layerwise, lo, hi):
         y, yv = _strided_out(x)
         if yv is False:
             return None
-        side = torch.empty(rows * 8 + mbytes, dtype=torch.uint8, device=x.device)
-        sp = side.data_ptr()
-        with _DeviceOf(x):
-            rc = L.fq_rowwise_fwd_v(1 if kind == "asym" else 0, x.data_ptr(), _rv(xv), y.data_ptr(), _rv(yv), rows, cols, int(num_bits), code, _semantics,
-                                    lo, hi, sp, sp + rows * 8, mbytes, _stream(x))
-        if rc:
-            if rc == _lib.ERR_UNSUPPORTED:
-                return None
-            _lib.check(rc, f"{kind}_quantize_train")
-        global _views_served
-        _views_served += 1
+        side, bp, mp = _side_alloc(rows, mbytes, x.device)
+        rc = _launch(x, L.fq_rowwise_fwd_v, 1 if kind == "asym" else 0, x.data_ptr(), _rv(xv), y.data_ptr(), _rv(yv), rows, cols, int(num_bits), code,
+                     _semantics, lo, hi, bp, mp, mbytes)
+        if not _served(rc, f"{kind}_quantize_train"):
+            return None
+        _view_served()
         return y, side, rows, cols
     y = torch.empty_like(x)
-    side = torch.empty(rows * 8 + mbytes, dtype=torch.uint8, device=x.device)
-    sp = side.data_ptr()
-    fn = L.fq_sym_fwd_train if kind == "sym" else L.fq_asym_fwd_train
-    dev = x.device.index
-    cur = _cur_dev()
-    if dev is not None and dev != cur:
-        with torch.cuda.device(dev):
-            rc = fn(x.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _semantics, lo, hi, sp, sp + rows * 8, mbytes, _raw_stream(dev))
-    else:
-        rc = fn(x.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _semantics, lo, hi, sp, sp + rows * 8, mbytes, _raw_stream(cur))
-    if rc:
-        if rc == _lib.ERR_UNSUPPORTED:
-            return None
-        _lib.check(rc, f"{kind}_quantize_train")
+    side, bp, mp = _side_alloc(rows, mbytes, x.device)
+    rc = _launch(x, L.fq_sym_fwd_train if kind == "sym" else L.fq_asym_fwd_train, x.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _semantics,
+                 lo, hi, bp, mp, mbytes)
+    if rc and not _served(rc, f"{kind}_quantize_train"):   # (`rc and`: the served call builds no message)
+        return None
     return y, side, rows, cols
 
 
@@ -326,15 +337,11 @@ def _mask_backward_v(gs, sides, rows, cols, lo, hi, code, wide, inplace=None, ou
             if ov is False:
                 return None
         outs.append(o)
-        sp = sd.data_ptr()
-        arr[i] = _lib.BwdTensorV(g.data_ptr(), o.data_ptr(), r, sp, sp + r * 8, _rv(gv), _rv(ov))
-    with _DeviceOf(gs[0]):
-        rc = _lib.lib().fq_ste_bwd_mask_multi_v(n, arr, cols, float(lo), float(hi), code, 1 if wide else 0, _stream(gs[0]))
-    if rc == _lib.ERR_UNSUPPORTED:
+        arr[i] = _lib.BwdTensorV(g.data_ptr(), o.data_ptr(), r, *_side_ptrs(sd, r), _rv(gv), _rv(ov))
+    rc = _launch(gs[0], _lib.lib().fq_ste_bwd_mask_multi_v, n, arr, cols, float(lo), float(hi), code, 1 if wide else 0)
+    if not _served(rc, "ste_backward_mask[strided]"):
         return None
-    _lib.check(rc, "ste_backward_mask[strided]")
-    global _views_served
-    _views_served += 1
+    _view_served()
     return outs
 
 
@@ -350,15 +357,8 @@ def train_backward(grad_output, side, rows, cols, lo, hi, inplace=False):
             return res[0]
     g = _aligned(grad_output)
     gx = g if inplace else torch.empty_like(g)
-    sp = side.data_ptr()
-    dev = g.device.index
-    L = _lib.lib()
-    cur = _cur_dev()
-    if dev is not None and dev != cur:
-        with torch.cuda.device(dev):
-            rc = L.fq_ste_bwd_mask(g.data_ptr(), gx.data_ptr(), rows, cols, lo, hi, sp, sp + rows * 8, side.numel() - rows * 8, code, _raw_stream(dev))
-    else:
-        rc = L.fq_ste_bwd_mask(g.data_ptr(), gx.data_ptr(), rows, cols, lo, hi, sp, sp + rows * 8, side.numel() - rows * 8, code, _raw_stream(cur))
+    bp, mp = _side_ptrs(side, rows)
+    rc = _launch(g, _lib.lib().fq_ste_bwd_mask, g.data_ptr(), gx.data_ptr(), rows, cols, lo, hi, bp, mp, side.numel() - (mp - bp), code)   # (mp - bp: the bounds' bytes)
     if rc:
         _lib.check(rc, "ste_backward_mask")
     return gx
@@ -376,10 +376,8 @@ def train_backward_wide(grad_output, side, rows, cols, lo, hi, out_dtype):
             return res[0]
     g = _aligned(grad_output if grad_output.dtype == torch.float32 else grad_output.float())
     gx = torch.empty(g.shape, dtype=out_dtype, device=g.device)
-    sp = side.data_ptr()
-    with _DeviceOf(g):
-        rc = _lib.lib().fq_ste_bwd_mask_wide(g.data_ptr(), gx.data_ptr(), rows, sp, sp + rows * 8, None, None, 0, None, None,
-                                             cols, float(lo), float(hi), code, _stream(g))
+    rc = _launch(g, _lib.lib().fq_ste_bwd_mask_wide, g.data_ptr(), gx.data_ptr(), rows, *_side_ptrs(side, rows), None, None, 0, None, None,
+                 cols, float(lo), float(hi), code)
     _lib.check(rc, "ste_backward_mask_wide")
     return gx
 
@@ -417,50 +415,35 @@ def sym_forward_autocast(x, num_bits, layerwise, wide, lo=-2.0, hi=2.0, train=No
             side = got = None
             bp = mp = None
             if train == "mask":
-                side = torch.empty(rows * 8 + mbytes, dtype=torch.uint8, device=x.device)
-                bp, mp, got = side.data_ptr(), side.data_ptr() + rows * 8, "mask"
+                side, bp, mp = _side_alloc(rows, mbytes, x.device)
+                got = "mask"
             elif train == "bounds":
                 side = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
                 bp, got = side.data_ptr(), "bounds"
             arr = (_lib.FwdTensorV * 1)(_lib.FwdTensorV(x.data_ptr(), y.data_ptr(), rows, int(num_bits), bp, mp, mbytes if mp else 0, _rv(xv), _rv(yv)))
-            with _DeviceOf(x):
-                rc = L.fq_sym_fwd_multi_v(1, arr, cols, code, _SEM_AUTOCAST, 2 if wide else 1, float(lo), float(hi), _stream(x))
-            if rc != _lib.ERR_UNSUPPORTED:
-                _lib.check(rc, "sym_quantize[autocast]")
-                global _views_served
-                _views_served += 1
+            rc = _launch(x, L.fq_sym_fwd_multi_v, 1, arr, cols, code, _SEM_AUTOCAST, 2 if wide else 1, float(lo), float(hi))
+            if _served(rc, "sym_quantize[autocast]"):
+                _view_served()
                 return y, side, rows, cols, got
-    xc = x if x.is_contiguous() else x.contiguous()
+    xc = _contig(x)
     y = torch.empty(xc.shape, dtype=torch.float32 if wide else x.dtype, device=x.device)
-    side, got = None, None
     ws_bytes = _ws_bytes(rows, cols, code)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
     ws_ptr = ws.data_ptr() if ws is not None else None
-    with _DeviceOf(x):
-        st = _stream(x)
-        rc = _lib.ERR_UNSUPPORTED
-        if train == "mask" and xc is x:  # (a wide result's mask has its own layout: backward = train_backward_wide)
-            mbytes = _mask_bytes(rows, cols, code)
-            if mbytes:
-                side = torch.empty(rows * 8 + mbytes, dtype=torch.uint8, device=x.device)
-                sp = side.data_ptr()
-                rc = L.fq_sym_fwd_autocast(xc.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _SEM_AUTOCAST, int(wide), float(lo), float(hi),
-                                           sp, sp + rows * 8, mbytes, ws_ptr, ws_bytes, st)
-                got = "mask"
-        if rc == _lib.ERR_UNSUPPORTED:
-            side, got = None, None
-            bptr = None
-            if train in ("mask", "bounds"):
-                side = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-                bptr, got = side.data_ptr(), "bounds"
-            rc = L.fq_sym_fwd_autocast(xc.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _SEM_AUTOCAST, int(wide), float(lo), float(hi),
-                                       bptr, None, 0, ws_ptr, ws_bytes, st)
-    _lib.check(rc, "sym_quantize[autocast]")
-    if xc is not x:
-        out = torch.empty_like(x, dtype=y.dtype)  # keeps the input's strides, as the reference's elementwise ops do
-        out.copy_(y)
-        y = out
-    return y, side, rows, cols, got
+    head = (xc.data_ptr(), y.data_ptr(), rows, cols, int(num_bits), code, _SEM_AUTOCAST, int(wide), float(lo), float(hi))
+    what = "sym_quantize[autocast]"
+    if train == "mask" and xc is x:  # (a wide result's mask has its own layout: backward = train_backward_wide)
+        mbytes = _mask_bytes(rows, cols, code)
+        if mbytes:
+            side, bp, mp = _side_alloc(rows, mbytes, x.device)
+            if _served(_launch(x, L.fq_sym_fwd_autocast, *head, bp, mp, mbytes, ws_ptr, ws_bytes), what):
+                return y, side, rows, cols, "mask"   # (xc is x: y has its layout already)
+    side = got = bptr = None
+    if train in ("mask", "bounds"):
+        side = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+        bptr, got = side.data_ptr(), "bounds"
+    _lib.check(_launch(x, L.fq_sym_fwd_autocast, *head, bptr, None, 0, ws_ptr, ws_bytes), what)
+    return _like_input(x, xc, y), side, rows, cols, got
 
 
 def pair_forward(w, x, w_bits, a_bits, lo, hi, need_w, need_x, wide=False):
@@ -490,36 +473,29 @@ def pair_forward(w, x, w_bits, a_bits, lo, hi, need_w, need_x, wide=False):
     if ac and not wide and not autocast_narrow_ok(w):
         return None  # autocast dtype != operand dtype: the two-call path returns fp32 results, F.linear rounds once
     L = _lib.lib()
-    side_w = torch.empty(rows_w * 8 + mw, dtype=torch.uint8, device=w.device) if need_w else None
-    side_x = torch.empty(rows_x * 8 + mx, dtype=torch.uint8, device=w.device) if need_x else None
-    pw, px = (side_w.data_ptr() if need_w else None), (side_x.data_ptr() if need_x else None)
+    side_w, bw, pw = _side_alloc(rows_w, mw, w.device) if need_w else _NO_SIDE
+    side_x, bx, px = _side_alloc(rows_x, mx, w.device) if need_x else _NO_SIDE
+    mw, mx = (mw if need_w else 0), (mx if need_x else 0)
+    sem, mode = (_SEM_AUTOCAST, 2 if wide else 1) if ac else (_semantics, 0)
     if wv or xv:
         (wq, wqv), (xq, xqv) = _strided_out(w, torch.float32 if wide else None), _strided_out(x, torch.float32 if wide else None)
         if wqv is False or xqv is False:
             return None
         arr = (_lib.FwdTensorV * 2)(
-            _lib.FwdTensorV(w.data_ptr(), wq.data_ptr(), rows_w, w_bits, pw, pw + rows_w * 8 if need_w else None, mw if need_w else 0, _rv(wv), _rv(wqv)),
-            _lib.FwdTensorV(x.data_ptr(), xq.data_ptr(), rows_x, a_bits, px, px + rows_x * 8 if need_x else None, mx if need_x else 0, _rv(xv), _rv(xqv)))
-        rc = _on_device(w, lambda st: L.fq_sym_fwd_multi_v(2, arr, cols, code, _SEM_AUTOCAST if ac else _semantics, (2 if wide else 1) if ac else 0, lo, hi, st))
-        if rc:
-            if rc == _lib.ERR_UNSUPPORTED:
-                return None
-            _lib.check(rc, "quantize_pair[strided]")
-        global _views_served
-        _views_served += 1
+            _lib.FwdTensorV(w.data_ptr(), wq.data_ptr(), rows_w, w_bits, bw, pw, mw, _rv(wv), _rv(wqv)),
+            _lib.FwdTensorV(x.data_ptr(), xq.data_ptr(), rows_x, a_bits, bx, px, mx, _rv(xv), _rv(xqv)))
+        if not _served(_launch(w, L.fq_sym_fwd_multi_v, 2, arr, cols, code, sem, mode, lo, hi), "quantize_pair[strided]"):
+            return None
+        _view_served()
         return wq, xq, side_w, side_x, rows_w, rows_x, cols
     if wide:
         wq, xq = torch.empty(w.shape, dtype=torch.float32, device=w.device), torch.empty(x.shape, dtype=torch.float32, device=w.device)
     else:
         wq, xq = torch.empty_like(w), torch.empty_like(x)
-    rc = _on_device(w, lambda st: L.fq_sym_fwd_pair(
-        w.data_ptr(), wq.data_ptr(), rows_w, w_bits, pw, pw + rows_w * 8 if need_w else None, mw if need_w else 0,
-        x.data_ptr(), xq.data_ptr(), rows_x, a_bits, px, px + rows_x * 8 if need_x else None, mx if need_x else 0,
-        cols, code, _SEM_AUTOCAST if ac else _semantics, (2 if wide else 1) if ac else 0, lo, hi, st))
-    if rc:
-        if rc == _lib.ERR_UNSUPPORTED:
-            return None
-        _lib.check(rc, "quantize_pair")
+    rc = _launch(w, L.fq_sym_fwd_pair, w.data_ptr(), wq.data_ptr(), rows_w, w_bits, bw, pw, mw,
+                 x.data_ptr(), xq.data_ptr(), rows_x, a_bits, bx, px, mx, cols, code, sem, mode, lo, hi)
+    if not _served(rc, "quantize_pair"):
+        return None
     return wq, xq, side_w, side_x, rows_w, rows_x, cols
 
 
@@ -574,14 +550,10 @@ def pair_backward(gw, gx, side_w, side_x, rows_w, rows_x, cols, lo, hi, inplace_
             return res[0], res[1]
     gw, gx = _aligned(gw), _aligned(gx)
     ow, ox = (gw if inplace_w else torch.empty_like(gw)), torch.empty_like(gx)
-    pw, px = side_w.data_ptr(), side_x.data_ptr()
-    L = _lib.lib()
-    rc = _on_device(gw, lambda st: L.fq_ste_bwd_mask_pair(gw.data_ptr(), ow.data_ptr(), rows_w, pw, pw + rows_w * 8,
-                                                          gx.data_ptr(), ox.data_ptr(), rows_x, px, px + rows_x * 8, cols, lo, hi, code, st))
-    if rc:
-        if rc == _lib.ERR_UNSUPPORTED:
-            return train_backward(gw, side_w, rows_w, cols, lo, hi, inplace=inplace_w), train_backward(gx, side_x, rows_x, cols, lo, hi)
-        _lib.check(rc, "quantize_linear_pair_backward")
+    rc = _launch(gw, _lib.lib().fq_ste_bwd_mask_pair, gw.data_ptr(), ow.data_ptr(), rows_w, *_side_ptrs(side_w, rows_w),
+                 gx.data_ptr(), ox.data_ptr(), rows_x, *_side_ptrs(side_x, rows_x), cols, lo, hi, code)
+    if not _served(rc, "quantize_linear_pair_backward"):
+        return train_backward(gw, side_w, rows_w, cols, lo, hi, inplace=inplace_w), train_backward(gx, side_x, rows_x, cols, lo, hi)
     return ow, ox
 
 
@@ -595,10 +567,8 @@ def pair_backward_wide(gw, gx, side_w, side_x, rows_w, rows_x, cols, lo, hi, out
     gw = _aligned(gw if gw.dtype == torch.float32 else gw.float())
     gx = _aligned(gx if gx.dtype == torch.float32 else gx.float())
     ow, ox = torch.empty(gw.shape, dtype=out_dtype, device=gw.device), torch.empty(gx.shape, dtype=out_dtype, device=gx.device)
-    pw, px = side_w.data_ptr(), side_x.data_ptr()
-    with _DeviceOf(gw):
-        rc = _lib.lib().fq_ste_bwd_mask_wide(gw.data_ptr(), ow.data_ptr(), rows_w, pw, pw + rows_w * 8,
-                                             gx.data_ptr(), ox.data_ptr(), rows_x, px, px + rows_x * 8, cols, float(lo), float(hi), code, _stream(gw))
+    rc = _launch(gw, _lib.lib().fq_ste_bwd_mask_wide, gw.data_ptr(), ow.data_ptr(), rows_w, *_side_ptrs(side_w, rows_w),
+                 gx.data_ptr(), ox.data_ptr(), rows_x, *_side_ptrs(side_x, rows_x), cols, float(lo), float(hi), code)
     _lib.check(rc, "quantize_pair_backward_wide")
     return ow, ox
 
@@ -630,16 +600,15 @@ def multi_forward(tensors, bits, need, lo, hi):
     if ac and not autocast_narrow_ok(t0):
         return None
     ys = [torch.empty_like(t) for t in tensors]
-    sides = [torch.empty(r * 8 + mb, dtype=torch.uint8, device=t0.device) if nd else None for r, mb, nd in zip(rows, mbytes, need)]
+    sides = []
     arr = (_lib.FwdTensor * n)()
-    for i, (t, y, sd) in enumerate(zip(tensors, ys, sides)):
-        sp = sd.data_ptr() if sd is not None else None
-        arr[i] = _lib.FwdTensor(t.data_ptr(), y.data_ptr(), rows[i], int(bits[i]), sp, sp + rows[i] * 8 if sp else None, mbytes[i] if sp else 0)
-    with _DeviceOf(t0):
-        rc = _lib.lib().fq_sym_fwd_multi(n, arr, cols, code, _SEM_AUTOCAST if ac else _semantics, 1 if ac else 0, float(lo), float(hi), _stream(t0))
-    if rc == _lib.ERR_UNSUPPORTED:
+    for i, (t, y) in enumerate(zip(tensors, ys)):
+        sd, bp, mp = _side_alloc(rows[i], mbytes[i], t0.device) if need[i] else _NO_SIDE
+        sides.append(sd)
+        arr[i] = _lib.FwdTensor(t.data_ptr(), y.data_ptr(), rows[i], int(bits[i]), bp, mp, mbytes[i] if need[i] else 0)
+    rc = _launch(t0, _lib.lib().fq_sym_fwd_multi, n, arr, cols, code, _SEM_AUTOCAST if ac else _semantics, 1 if ac else 0, float(lo), float(hi))
+    if not _served(rc, "quantize_multi"):
         return None
-    _lib.check(rc, "quantize_multi")
     return ys, sides, rows, cols
 
 
@@ -660,16 +629,11 @@ def multi_backward(grads, sides, rows, cols, lo, hi, inplace=None):
     arr = (_lib.BwdTensor * len(live))()
     for j, i in enumerate(live):
         out[i] = gs[i] if inplace[i] else torch.empty_like(gs[i])
-        sp = sides[i].data_ptr()
-        arr[j] = _lib.BwdTensor(gs[i].data_ptr(), out[i].data_ptr(), rows[i], sp, sp + rows[i] * 8)
-    g0 = gs[live[0]]
-    with _DeviceOf(g0):
-        rc = _lib.lib().fq_ste_bwd_mask_multi(len(live), arr, cols, float(lo), float(hi), code, 0, _stream(g0))
-    if rc == _lib.ERR_UNSUPPORTED:
+        arr[j] = _lib.BwdTensor(gs[i].data_ptr(), out[i].data_ptr(), rows[i], *_side_ptrs(sides[i], rows[i]))
+    rc = _launch(gs[live[0]], _lib.lib().fq_ste_bwd_mask_multi, len(live), arr, cols, float(lo), float(hi), code, 0)
+    if not _served(rc, "quantize_multi_backward"):
         for i in live:
             out[i] = train_backward(gs[i], sides[i], rows[i], cols, lo, hi, inplace=inplace[i])
-        return out
-    _lib.check(rc, "quantize_multi_backward")
     return out
 
 
@@ -682,15 +646,12 @@ def quantize_train(kind, x, num_bits, layerwise, lo, hi, group_size=None):
         g = check_group(tuple(x.shape), group_size, layerwise)
         _prep(x, f"{kind}_quantize")
         res = group_forward(kind, x, num_bits, g, lo=float(lo), hi=float(hi), train=True)
-        if res is None:
-            return None
-        y, side, rows, _ = res
-        return y, side[: rows * 8].view(torch.float32).view(rows, 2), side[rows * 8:]
-    res = train_forward(kind, x, num_bits, layerwise, float(lo), float(hi))
+    else:
+        res = train_forward(kind, x, num_bits, layerwise, float(lo), float(hi))
     if res is None:
         return None
     y, side, rows, _ = res
-    return y, side[: rows * 8].view(torch.float32).view(rows, 2), side[rows * 8:]
+    return (y,) + split_side(side, rows)
 
 
 def ste_backward_mask(grad_output, lo, hi, row_bounds, mask, rows, cols, inplace=False):
@@ -700,10 +661,8 @@ def ste_backward_mask(grad_output, lo, hi, row_bounds, mask, rows, cols, inplace
     gx = g if inplace else torch.empty_like(g)
     if g.numel() == 0:
         return gx
-    L = _lib.lib()
-    with _DeviceOf(g):
-        rc = L.fq_ste_bwd_mask(g.data_ptr(), gx.data_ptr(), rows, cols, float(lo), float(hi), row_bounds.data_ptr(),
-                               mask.data_ptr(), mask.numel(), code, _stream(g))
+    rc = _launch(g, _lib.lib().fq_ste_bwd_mask, g.data_ptr(), gx.data_ptr(), rows, cols, float(lo), float(hi), row_bounds.data_ptr(),
+                 mask.data_ptr(), mask.numel(), code)
     _lib.check(rc, "ste_backward_mask")
     return gx
 
@@ -714,16 +673,14 @@ def low_bit_weight(w, scale, w_bits):
     code = _prep(w, "low_bit_weight")
     if w.dim() != 2:
         raise ValueError("low_bit_weight expects a 2-D weight")
-    wc = w if w.is_contiguous() else w.contiguous()
+    wc = _contig(w)
     sc = scale.to(w.dtype).contiguous()
     per_row = 1 if sc.numel() == w.shape[0] and sc.numel() != 1 else 0
     if not per_row and sc.numel() != 1:
         raise ValueError(f"scale has {sc.numel()} elements for a weight with {w.shape[0]} rows")
     out = torch.empty_like(wc)
     if wc.numel():
-        with _DeviceOf(w):
-            rc = _lib.lib().fq_w12_fwd(wc.data_ptr(), sc.data_ptr(), out.data_ptr(), wc.shape[0], wc.shape[1], int(w_bits),
-                                       per_row, code, _stream(w))
+        rc = _launch(w, _lib.lib().fq_w12_fwd, wc.data_ptr(), sc.data_ptr(), out.data_ptr(), wc.shape[0], wc.shape[1], int(w_bits), per_row, code)
         _lib.check(rc, "low_bit_weight")
     return out
 
@@ -737,11 +694,9 @@ def low_bit_weight_fused(w, w_bits):
         return None
     out = torch.empty_like(w)
     scale = torch.empty(w.shape[0], dtype=w.dtype, device=w.device)
-    L = _lib.lib()
-    rc = _on_device(w, lambda st: L.fq_w12_fwd_rows(w.data_ptr(), out.data_ptr(), scale.data_ptr(), w.shape[0], w.shape[1], int(w_bits), code, st))
-    if rc == _lib.ERR_UNSUPPORTED:
+    rc = _launch(w, _lib.lib().fq_w12_fwd_rows, w.data_ptr(), out.data_ptr(), scale.data_ptr(), w.shape[0], w.shape[1], int(w_bits), code)
+    if not _served(rc, "low_bit_weight_fused"):
         return None
-    _lib.check(rc, "low_bit_weight_fused")
     return out, scale
 
 
@@ -786,24 +741,18 @@ def group_forward(kind, x, num_bits, group_size, autocast=False, lo=-2.0, hi=2.0
     if code is None or code == _lib.DTYPE_F64 or not x.is_cuda or not x.is_contiguous() or x.numel() == 0 or x.data_ptr() & 15:
         return None
     rows, cols = rows_cols(tuple(x.shape), False)
-    side = None
-    bp = mp = None
+    side, bp, mp = _NO_SIDE
     mbytes = 0
     if train:
         mbytes = _mask_bytes(rows, cols, code)
         if not mbytes:
             return None
-        side = torch.empty(rows * 8 + mbytes, dtype=torch.uint8, device=x.device)
-        bp = side.data_ptr()
-        mp = bp + rows * 8
+        side, bp, mp = _side_alloc(rows, mbytes, x.device)
     y = torch.empty_like(x)
-    sem = _SEM_AUTOCAST if autocast else _semantics
-    L = _lib.lib()
-    rc = _on_device(x, lambda st: L.fq_group_fwd(1 if kind == "asym" else 0, x.data_ptr(), y.data_ptr(), rows, cols, int(group_size), int(num_bits), code,
-                                                 sem, 1 if autocast else 0, float(lo), float(hi), bp, mp, mbytes, st))
-    if rc == _lib.ERR_UNSUPPORTED:
+    rc = _launch(x, _lib.lib().fq_group_fwd, 1 if kind == "asym" else 0, x.data_ptr(), y.data_ptr(), rows, cols, int(group_size), int(num_bits), code,
+                 _SEM_AUTOCAST if autocast else _semantics, 1 if autocast else 0, float(lo), float(hi), bp, mp, mbytes)
+    if not _served(rc, f"{kind}_quantize[group]"):
         return None
-    _lib.check(rc, f"{kind}_quantize[group]")
     group_counts["group_launch"] += 1
     return y, side, rows, cols
 
@@ -821,7 +770,7 @@ def _grouped(kind, x, num_bits, group_size, want_bounds):
         res = group_forward(kind, x, num_bits, g, lo=-2.0, hi=2.0, train=True)
     if res is not None:
         y, side, rows, _ = res
-        return (y, side[: rows * 8].view(torch.float32).view(rows, 2)) if want_bounds else y
+        return (y, split_side(side, rows)[0]) if want_bounds else y
     group_counts["group_view_route"] += 1
     if x.numel() == 0:
         return (torch.empty_like(x), None) if want_bounds else torch.empty_like(x)
@@ -882,26 +831,20 @@ def ste_backward(grad_output, x, lo, hi, row_bounds=None, rows_cols_hint=None):
             gx, ov = _strided_out(grad_output)
             if ov is not False:
                 rows, cols = rows_cols(tuple(x.shape), False)
-                with _DeviceOf(x):
-                    rc = L.fq_ste_bwd_v(grad_output.data_ptr(), _rv(gv), x.data_ptr(), _rv(xv), gx.data_ptr(), _rv(ov), rows, cols, float(lo), float(hi),
-                                        None, code, _stream(x))
-                if rc != _lib.ERR_UNSUPPORTED:
-                    _lib.check(rc, "ste_backward[strided]")
-                    global _views_served
-                    _views_served += 1
+                rc = _launch(x, L.fq_ste_bwd_v, grad_output.data_ptr(), _rv(gv), x.data_ptr(), _rv(xv), gx.data_ptr(), _rv(ov), rows, cols,
+                             float(lo), float(hi), None, code)
+                if _served(rc, "ste_backward[strided]"):
+                    _view_served()
                     return gx
-    g = grad_output if grad_output.is_contiguous() else grad_output.contiguous()
-    xc = x if x.is_contiguous() else x.contiguous()
+    g, xc = _contig(grad_output), _contig(x)
     gx = torch.empty_like(g)
     if g.numel() == 0:
         return gx
-    with _DeviceOf(x):
-        if row_bounds is not None:
-            rows, cols = rows_cols_hint
-            rc = L.fq_ste_bwd_rows(g.data_ptr(), xc.data_ptr(), gx.data_ptr(), rows, cols, float(lo), float(hi),
-                                   row_bounds.data_ptr(), code, _stream(x))
-        else:
-            rc = L.fq_ste_bwd(g.data_ptr(), xc.data_ptr(), gx.data_ptr(), g.numel(), float(lo), float(hi), code, _stream(x))
+    if row_bounds is not None:
+        rows, cols = rows_cols_hint
+        rc = _launch(x, L.fq_ste_bwd_rows, g.data_ptr(), xc.data_ptr(), gx.data_ptr(), rows, cols, float(lo), float(hi), row_bounds.data_ptr(), code)
+    else:
+        rc = _launch(x, L.fq_ste_bwd, g.data_ptr(), xc.data_ptr(), gx.data_ptr(), g.numel(), float(lo), float(hi), code)
     _lib.check(rc, "ste_backward")
     return gx
 
@@ -995,19 +938,17 @@ def _export(kind, x, num_bits, layerwise, container, autocast):
     cc = _CONTAINERS.get(container)
     if cc is None:
         raise ValueError(f"{what}: container must be one of {sorted(_CONTAINERS)}, got {container!r}")
-    xc = x if x.is_contiguous() else x.contiguous()
+    xc = _contig(x)
     L = _lib.lib()
     nbytes = L.fq_export_bins_bytes(rows, cols, cc)
     raw = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     scales = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
     overflow = torch.empty(rows, dtype=torch.int32, device=x.device)
-    with _DeviceOf(x):
-        if kind == "sym":
-            rc = L.fq_sym_export(xc.data_ptr(), raw.data_ptr(), scales.data_ptr(), overflow.data_ptr(), rows, cols, int(num_bits), cc, code,
-                                 _SEM_AUTOCAST if autocast else _semantics, 1 if autocast else 0, _stream(x))
-        else:
-            rc = L.fq_asym_export(xc.data_ptr(), raw.data_ptr(), scales.data_ptr(), overflow.data_ptr(), rows, cols, int(num_bits), cc, code,
-                                  _semantics, _stream(x))
+    head = (xc.data_ptr(), raw.data_ptr(), scales.data_ptr(), overflow.data_ptr(), rows, cols, int(num_bits), cc, code)
+    if kind == "sym":
+        rc = _launch(x, L.fq_sym_export, *head, _SEM_AUTOCAST if autocast else _semantics, 1 if autocast else 0)
+    else:
+        rc = _launch(x, L.fq_asym_export, *head, _semantics)
     _lib.check(rc, what)
     if container == "int8":
         bins = (raw.view(torch.int8) if kind == "sym" else raw).view(xc.shape)
@@ -1048,11 +989,10 @@ def sym_row_scales(x, num_bits, layerwise=False, autocast=None):
     if x.numel() == 0:
         raise RuntimeError("sym_row_scales: empty tensor")
     ac = autocast_active(x) if autocast is None else bool(autocast)
-    xc = x if x.is_contiguous() else x.contiguous()
+    xc = _contig(x)
     scales = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-    with _DeviceOf(x):
-        rc = _lib.lib().fq_sym_row_scales(xc.data_ptr(), scales.data_ptr(), rows, cols, int(num_bits), code, _SEM_AUTOCAST if ac else _semantics, 1 if ac else 0,
-                                          -2.0, 2.0, None, None, 0, _stream(x))
+    rc = _launch(x, _lib.lib().fq_sym_row_scales, xc.data_ptr(), scales.data_ptr(), rows, cols, int(num_bits), code, _SEM_AUTOCAST if ac else _semantics,
+                 1 if ac else 0, -2.0, 2.0, None, None, 0)
     _lib.check(rc, "sym_row_scales")
     return scales
 
@@ -1124,8 +1064,7 @@ def mx_rotate(x):
     if x.numel():
         cols = x.shape[-1]
         rows = x.numel() // cols
-        L = _lib.lib()
-        _lib.check(_on_device(x, lambda st: L.fq_block_rotate(x.data_ptr(), y.data_ptr(), rows, cols, dt, st)), "mx_rotate")
+        _lib.check(_launch(x, _lib.lib().fq_block_rotate, x.data_ptr(), y.data_ptr(), rows, cols, dt), "mx_rotate")
         mx_counts["mx_rotate_launch"] += 1
     return y
 
@@ -1136,21 +1075,15 @@ def mx_quantize(x, fmt, rotate=False, scale_rule="floor", return_mask=False):
     fp32 values of x R (mx_rotate) instead, in the same single launch; the result is in the rotated basis.
     scale_rule="ceil": the shared exponent under which no element of a finite block saturates.  return_mask=True -> (y, mask): mask is a
     uint8 tensor of numel / 8 bytes written by the same launch, a 0 bit where saturation changed the element (of x R under rotate)."""
-    flags = check_mx_scale_rule(scale_rule)
+    flags = check_mx_scale_rule(scale_rule) | (_lib.MX_FLAG_ROTATE if rotate else 0)
     x, code, dt = _mx_input(x, fmt, "mx_quantize", rotate)
     y = torch.empty_like(x, memory_format=torch.contiguous_format)
     mask = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device) if return_mask else None
     if x.numel():
         cols = x.shape[-1]
         rows = x.numel() // cols
-        L = _lib.lib()
-        if flags or return_mask:
-            flags |= _lib.MX_FLAG_ROTATE if rotate else 0
-            mp = mask.data_ptr() if return_mask else None
-            _lib.check(_on_device(x, lambda st: L.fq_mx_fwd_ex(x.data_ptr(), y.data_ptr(), mp, rows, cols, code, dt, flags, st)), "mx_quantize")
-        else:
-            fwd = L.fq_mx_fwd_rot if rotate else L.fq_mx_fwd
-            _lib.check(_on_device(x, lambda st: fwd(x.data_ptr(), y.data_ptr(), rows, cols, code, dt, st)), "mx_quantize")
+        rc = _launch(x, _lib.lib().fq_mx_fwd_ex, x.data_ptr(), y.data_ptr(), mask.data_ptr() if return_mask else None, rows, cols, code, dt, flags)
+        _lib.check(rc, "mx_quantize")
         mx_counts["mx_launch"] += 1
         if return_mask:
             mx_counts["mx_mask_launch"] += 1
@@ -1193,9 +1126,8 @@ def mx_ste_backward(g, mask, rotate=False):
     if g.numel():
         cols = g.shape[-1]
         rows = g.numel() // cols
-        L = _lib.lib()
-        flags = _lib.MX_FLAG_ROTATE if rotate else 0
-        _lib.check(_on_device(g, lambda st: L.fq_mx_ste_bwd(g.data_ptr(), mask.data_ptr(), gx.data_ptr(), rows, cols, dt, flags, st)), "mx_ste_backward")
+        rc = _launch(g, _lib.lib().fq_mx_ste_bwd, g.data_ptr(), mask.data_ptr(), gx.data_ptr(), rows, cols, dt, _lib.MX_FLAG_ROTATE if rotate else 0)
+        _lib.check(rc, "mx_ste_backward")
         mx_counts["mx_ste_launch"] += 1
     return gx
 
@@ -1242,7 +1174,7 @@ def mx_export(x, fmt, rotate=False, scale_rule="floor"):
     """-> MXExport(elements, scales, fmt, shape, dtype, rotated): the codes and E8M0 scales of mx_quantize(x, fmt, rotate, scale_rule).
     mxfp4 and mxfp8_* only (FP6 has no packing here: ValueError).  The export does not record the rule: dequantize() and mx_matmul read
     whatever scale byte it wrote."""
-    flags = check_mx_scale_rule(scale_rule, "mx_export")
+    flags = check_mx_scale_rule(scale_rule, "mx_export") | (_lib.MX_FLAG_ROTATE if rotate else 0)
     code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) else None
     if code in (_lib.MX_FP6_E2M3, _lib.MX_FP6_E3M2):
         raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
@@ -1253,14 +1185,7 @@ def mx_export(x, fmt, rotate=False, scale_rule="floor"):
     scales = torch.empty(lead + (cols // MX_BLOCK,), dtype=torch.uint8, device=x.device)
     if x.numel():
         rows = x.numel() // cols
-        L = _lib.lib()
-        if flags:
-            flags |= _lib.MX_FLAG_ROTATE if rotate else 0
-            _lib.check(_on_device(x, lambda st: L.fq_mx_export_ex(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, flags, st)),
-                       "mx_export")
-        else:
-            exp = L.fq_mx_export_rot if rotate else L.fq_mx_export
-            _lib.check(_on_device(x, lambda st: exp(x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, st)), "mx_export")
+        _lib.check(_launch(x, _lib.lib().fq_mx_export_ex, x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, flags), "mx_export")
         mx_counts["mx_export_launch"] += 1
     return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype, rotate)
 
@@ -1314,10 +1239,9 @@ def mx_matmul_tensors(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, a_shap
     a_elems, a_scales, w_elems, w_scales = fix(a_elems), fix(a_scales), fix(w_elems), fix(w_scales)
     out = torch.empty(tuple(a_shape[:-1]) + (N,), dtype=out_dtype, device=a_elems.device)
     if M and N:
-        L = _lib.lib()
-        _lib.check(_on_device(a_elems, lambda st: L.fq_mx_gemm(a_elems.data_ptr(), a_scales.data_ptr(), MX_FORMATS[a_fmt], w_elems.data_ptr(),
-                                                               w_scales.data_ptr(), MX_FORMATS[w_fmt], out.data_ptr(), M, N, K,
-                                                               _OUT_DTYPES[out_dtype], st)), "mx_matmul")
+        rc = _launch(a_elems, _lib.lib().fq_mx_gemm, a_elems.data_ptr(), a_scales.data_ptr(), MX_FORMATS[a_fmt], w_elems.data_ptr(), w_scales.data_ptr(),
+                     MX_FORMATS[w_fmt], out.data_ptr(), M, N, K, _OUT_DTYPES[out_dtype])
+        _lib.check(rc, "mx_matmul")
         mx_counts["mx_gemm_launch"] += 1
         mx_counts["mx_gemm_skinny" if M <= MX_GEMM_SKINNY_M else "mx_gemm_tiled"] += 1
     return out

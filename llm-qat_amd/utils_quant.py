@@ -427,20 +427,6 @@ def default_group_sizes(weight=None, act=None):
     return prev
 
 
-class _MXQuantizer(torch.autograd.Function):
-    """MX block-scaled fake quantization (ops.mx_quantize) with the straight-through identity gradient: nothing is saved and no backward
-    kernel runs (as the 1-/2-bit weight branches, _LowBitWeight).  The saturated elements are not masked."""
-
-    @staticmethod
-    def forward(ctx, x, fmt):
-        ctx.set_materialize_grads(False)
-        return ops.mx_quantize(x, fmt)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        return grad_output, None
-
-
 class _BlockRotate(torch.autograd.Function):
     """x R (ops.mx_rotate): R is symmetric and its own inverse, so the backward is the forward on the gradient.  Nothing is saved."""
 
@@ -454,25 +440,12 @@ class _BlockRotate(torch.autograd.Function):
         return None if grad_output is None else _BlockRotate.apply(grad_output)
 
 
-class _MXRotQuantizer(torch.autograd.Function):
-    """MX fake quantization of x R in one launch (ops.mx_quantize(rotate=True)).  Straight-through over the quantizer only: the rotation
-    is a linear map with its own gradient, so grad_x = grad_y R -- one rotate launch, nothing saved."""
-
-    @staticmethod
-    def forward(ctx, x, fmt):
-        ctx.set_materialize_grads(False)
-        return ops.mx_quantize(x, fmt, rotate=True)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        return (None if grad_output is None else _BlockRotate.apply(grad_output)), None
-
-
-class _MXQuantizerEx(torch.autograd.Function):
-    """The MX quantizer under a non-default scale rule and / or the saturation-masked gradient; the defaults keep
-    _MXQuantizer / _MXRotQuantizer.  clip: the forward launch also writes the saturation bitmap, the only tensor saved, and the backward
-    is one launch: grad_x = grad_y where the bit is 1, +0.0 elsewhere (times R under rotate, in that launch).  Without clip nothing is
-    saved and the gradient is the identity (times R under rotate)."""
+class _MXQuantizer(torch.autograd.Function):
+    """MX block-scaled fake quantization (ops.mx_quantize; DESIGN.md sections 13, 15, 16), straight-through over the quantizer only.
+    Without clip nothing is saved and the gradient is the incoming one itself (as the 1-/2-bit weight branches, _LowBitWeight; the saturated
+    elements are not masked), times R under rotate -- the rotation is a linear map with its own gradient: one rotate launch.  clip: the
+    forward launch also writes the saturation bitmap, the only tensor saved, and the backward is one launch: grad_x = grad_y where the bit
+    is 1, +0.0 elsewhere (times R under rotate, in that launch)."""
 
     @staticmethod
     def forward(ctx, x, fmt, rotate, scale_rule, clip):
@@ -513,9 +486,7 @@ def _mx_apply(x, fmt, rotate, scale_rule, ste):
     clip = ste == "clip" and torch.is_grad_enabled() and x.requires_grad   # no backward will come: no bitmap is written
     if torch.compiler.is_compiling():
         return compiled.mx_fake_quant(x, fmt, rotate, scale_rule, clip)
-    if clip or scale_rule != "floor":
-        return _MXQuantizerEx.apply(x, fmt, rotate, scale_rule, clip)
-    return _MXRotQuantizer.apply(x, fmt) if rotate else _MXQuantizer.apply(x, fmt)
+    return _MXQuantizer.apply(x, fmt, rotate, scale_rule, clip)
 
 
 def block_rotate(x):
@@ -1488,7 +1459,7 @@ class QuantizeLinear(nn.Linear):
                 y, side, rows, _, got = ops.sym_forward_autocast(w, self.w_bits, self.weight_layerwise, wide=False,
                                                                  train=None if _BACKWARD_MODE == "plain" else _BACKWARD_MODE)
                 if got == "mask":
-                    bounds, mask = side[: rows * 8].view(torch.float32).view(rows, 2), side[rows * 8:]
+                    bounds, mask = ops.split_side(side, rows)
                 elif got == "bounds":
                     bounds = side
             else:
@@ -1630,7 +1601,7 @@ class QuantizeLinear(nn.Linear):
             # node for the input), so non-reentrant checkpointing sees identical saved tensors in both passes
             rows_w, rows_x, cols = res[4], res[5], res[6]
             side_w, side_x = res[2], res[3]
-            cached = (res[0], side_w[: rows_w * 8].view(torch.float32).view(rows_w, 2), side_w[rows_w * 8:], ops.rows_cols(tuple(weight.shape), False))
+            cached = (res[0], *ops.split_side(side_w, rows_w), ops.rows_cols(tuple(weight.shape), False))
             self._fq_wcache = (wkey, cached)
             _count("wcache_fill")
             wq = _ReuseQuantizedWeight.apply(weight, cached, _CLIP) if need_w else res[0]
