@@ -17,6 +17,7 @@ import os
 import sys
 import threading
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -172,6 +173,18 @@ class _Raw:
 
     def __init__(self, out, mode, saved=(), clip=None, rows_cols=None, grad_dtype=None):
         self.out, self.mode, self.saved, self.clip, self.rows_cols, self.grad_dtype = out, mode, saved, clip, rows_cols, grad_dtype
+
+
+# The other records the host logic keeps or hands on (plain tuples with names).  The two that are written on every forward call stay
+# bare tuples, unpacked into names where they are read: a _ThreadState.acts entry (_act_store / _act_lookup; its layout is written at
+# _ThreadState.acts) and a _ThreadState.outs record (_note_output / _kv_hook: weakref(output), its version, region, stream).  So does
+# ops.pair_forward's result, unpacked once on arrival.  Constructing a namedtuple is a Python-level call each time, and with all of these
+# named the planned route's host forward left the parent's spread (profiles/pair_route_refactor_host_ab_named_records.txt).
+_Plan = namedtuple("_Plan", "shape in_dtype w_dtype settings eligible launch bits")   # QuantizeLinear._fq_plan, see QuantizeLinear._new_plan
+_VResult = namedtuple("_VResult", "vq side rows cols clip")                 # V as a K + V launch left it, until the V call asks for it
+_KVStash = namedtuple("_KVStash", "ref version v state sig")                # _ThreadState.kv: weakref(V's input), its version, the _VResult, _kv_state, call signature
+_QWeight = namedtuple("_QWeight", "y bounds mask rows_cols")                # a fake-quantized weight as plain data (what _ReuseQuantizedWeight wraps)
+_WCache = namedtuple("_WCache", "key value")                                # QuantizeLinear._fq_wcache: _wcache_key() and the _QWeight made under it
 
 
 def _compute(kind, input, clip_val, num_bits, layerwise, narrow, need_grad):
@@ -412,19 +425,23 @@ def group_quantize(x, clip_val, num_bits, group_size, symmetric=True):
     return _GroupQuantizer.apply(x, clip_val, num_bits, g, "sym" if symmetric else "asym", False, False)
 
 
-_DEFAULT_GROUPS = (None, None)   # (weight, activation) group sizes of QuantizeLinears constructed without explicit ones
+# what the QuantizeLinears constructed from now on take for the settings they are not given explicitly (the default_* setters below):
+# (weight, activation) group sizes, (weight, activation) MX formats, and the MX operands' rotation, scale rule and gradient
+_DEFAULTS = {"groups": (None, None), "mx": (None, None), "mx_rotate": False, "mx_scale_rule": "floor", "mx_ste": "identity"}
+
+
+def _set_default(name, value):
+    prev, _DEFAULTS[name] = _DEFAULTS[name], value
+    return prev
 
 
 def default_group_sizes(weight=None, act=None):
     """Group sizes the QuantizeLinears constructed from now on take when their own weight_group_size / act_group_size are not given
     (None: one scale per row).  Lets unchanged model code (LLM-QAT's train.py) train for a group-wise export.  -> the previous pair."""
-    global _DEFAULT_GROUPS
-    prev = _DEFAULT_GROUPS
-    for name, g in (("weight", weight), ("act", act)):
+    for g in (weight, act):
         if g is not None:
             ops.check_group((g,), g)
-    _DEFAULT_GROUPS = (weight, act)
-    return prev
+    return _set_default("groups", (weight, act))
 
 
 class _BlockRotate(torch.autograd.Function):
@@ -517,100 +534,58 @@ def mx_quantize(x, fmt, rotate=False, scale_rule="floor", ste="identity"):
     return _mx_apply(x, fmt, bool(rotate), scale_rule, ste)
 
 
-_DEFAULT_MX = (None, None)   # (weight, activation) MX formats of QuantizeLinears constructed without explicit ones
-
-
 def default_mx_formats(weight=None, act=None):
     """MX formats the QuantizeLinears constructed from now on take for the operands they quantize (w_bits < 32 / a_bits < 32, not
     layerwise, no explicit group size) when their own weight_format / act_format are not given (None: the integer quantizers).  Lets
     unchanged model code (LLM-QAT's train.py) train for MXFP4.  -> the previous pair."""
-    global _DEFAULT_MX
     for f in (weight, act):
         if f is not None and f not in ops.MX_FORMATS:
             raise ValueError(f"unknown MX format {f!r}: one of {', '.join(ops.MX_FORMATS)}")
-    prev = _DEFAULT_MX
-    _DEFAULT_MX = (weight, act)
-    return prev
-
-
-_DEFAULT_MX_ROTATE = False   # mx_rotate of QuantizeLinears constructed without an explicit one
+    return _set_default("mx", (weight, act))
 
 
 def default_mx_rotate(flag):
     """Whether the QuantizeLinears constructed from now on whose two operands both resolve to an MX format, and whose in_features is a
     multiple of 64, rotate their operands (mx_rotate=True) when their own mx_rotate is not given.  Layers the rotation does not apply to
     stay unrotated.  Lets unchanged model code train with the rotation.  -> the previous flag."""
-    global _DEFAULT_MX_ROTATE
-    prev = _DEFAULT_MX_ROTATE
-    _DEFAULT_MX_ROTATE = bool(flag)
-    return prev
-
-
-_DEFAULT_MX_SCALE_RULE = "floor"   # mx_scale_rule / mx_ste of QuantizeLinears constructed without explicit ones
-_DEFAULT_MX_STE = "identity"
+    return _set_default("mx_rotate", bool(flag))
 
 
 def default_mx_scale_rule(rule):
     """The scale rule ("floor" / "ceil") the QuantizeLinears constructed from now on take for their MX operands when their own
     mx_scale_rule is not given.  Layers without an MX operand are not affected.  -> the previous rule."""
-    global _DEFAULT_MX_SCALE_RULE
     ops.check_mx_scale_rule(rule, "default_mx_scale_rule")
-    prev = _DEFAULT_MX_SCALE_RULE
-    _DEFAULT_MX_SCALE_RULE = rule
-    return prev
+    return _set_default("mx_scale_rule", rule)
 
 
 def default_mx_ste(mode):
     """The gradient ("identity" / "clip") the QuantizeLinears constructed from now on take for their MX operands when their own mx_ste
     is not given.  Layers without an MX operand are not affected.  -> the previous mode."""
-    global _DEFAULT_MX_STE
     _check_mx_ste(mode, "default_mx_ste")
-    prev = _DEFAULT_MX_STE
-    _DEFAULT_MX_STE = mode
-    return prev
-
-
-class _LowBitWeightCpu(torch.autograd.Function):
-    """the same branch for CPU tensors (opt-in, cpu_tensors.py); identity gradient"""
-
-    @staticmethod
-    def forward(ctx, w, w_bits, layerwise):
-        ctx.set_materialize_grads(False)
-        return cpu_tensors.low_bit_weight(w, w_bits, layerwise)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        return grad_output, None, None
+    return _set_default("mx_ste", mode)
 
 
 class _LowBitWeight(torch.autograd.Function):
-    """forward value of `quan_weights_no_grad.detach() - real_weights.detach() + real_weights` (:240-242);
-    its gradient w.r.t. real_weights is the identity."""
+    """forward value of `quan_weights_no_grad.detach() - real_weights.detach() + real_weights` (:240-242); its gradient w.r.t. real_weights
+    is the identity.  how: "cpu" (opt-in CPU tensors, cpu_tensors.py; arg: weight_layerwise), "fused" (the one-launch kernel, row mean in
+    ATen's order; _NotServed where the kernel does not serve the shape) or "scaled" (arg: the mean-|w| scale ATen has reduced)."""
 
     @staticmethod
-    def forward(ctx, w, scale, w_bits):
+    def forward(ctx, w, w_bits, how, arg):
         ctx.set_materialize_grads(False)
-        return ops.low_bit_weight(w, scale, w_bits)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        return grad_output, None, None
-
-
-class _LowBitWeightFused(torch.autograd.Function):
-    """the same value from the one-launch kernel (row mean in ATen's order); identity gradient"""
-
-    @staticmethod
-    def forward(ctx, w, w_bits):
-        ctx.set_materialize_grads(False)
-        res = ops.low_bit_weight_fused(w, w_bits)
-        if res is None:
+        if how == "cpu":
+            return cpu_tensors.low_bit_weight(w, w_bits, arg)
+        if how == "scaled":
+            return ops.low_bit_weight(w, arg, w_bits)
+        fused = ops.low_bit_weight_fused(w, w_bits)
+        if fused is None:
             raise _NotServed()
-        return res[0]
+        out, _ = fused
+        return out
 
     @staticmethod
     def backward(ctx, grad_output):
-        return grad_output, None
+        return grad_output, None, None, None
 
 
 class _NotServed(Exception):
@@ -649,10 +624,12 @@ def _w12_fused_verified(w):
             g = torch.Generator(device=w.device).manual_seed(1234)
             for rows, cols in ((16, 512), (9, 8128), (8, 8132), (8, 11008)):
                 p = (torch.randn(rows, cols, generator=g, device=w.device) * 0.02).to(w.dtype)
-                res = ops.low_bit_weight_fused(p, 1)
-                if res is not None and not torch.equal(res[1], p.abs().mean(dim=1)):
-                    ok = False
-                    break
+                fused = ops.low_bit_weight_fused(p, 1)
+                if fused is not None:
+                    _, scale = fused
+                    if not torch.equal(scale, p.abs().mean(dim=1)):
+                        ok = False
+                        break
         _w12_verdict[key] = ok
     if not ok:
         _count("w12_fused_unverified")
@@ -830,7 +807,7 @@ class _ThreadState:
     def __init__(self):
         self.acts = {}        # key -> (weakref(input), its version, its address, _Raw, the result's version, needs grad, region, stream)
         self.outs = []        # the last few QuantizeLinear outputs of this thread, in order (weakly): what the KV hooks pair
-        self._kv = None       # the pending half of a K + V launch (`kv`: the property below tells the C++ nodes when one is pending)
+        self._kv = None       # the pending half of a K + V launch, a _KVStash (`kv`: the property below tells the C++ nodes when one is pending)
         self.epoch = 0        # fake-quant backward passes started on graphs this thread built
         self.ref = weakref.ref(self)
         # the C++ node cannot touch this object from the engine's thread: its backward bumps a counter cell instead, and `_state()` --
@@ -940,7 +917,9 @@ def _region():
 
 
 def _state_word(x):
-    """everything ambient that decides which arithmetic / data flow a call takes, folded into one int (part of the cache keys)"""
+    """everything ambient that decides which arithmetic / data flow a call takes, folded into one int (part of the cache keys).
+    QuantizeLinear._pair_forward writes the same sum out from the values it already holds (mask mode, its own `grad` and `ac`), to keep
+    these calls off the planned route: the two must agree bit for bit, or sibling projections stop finding each other's activation."""
     return (_MODE_CODE[_BACKWARD_MODE] + 4 * ops._semantics + (8 if torch.is_grad_enabled() else 0)
             + (16 if ops.autocast_active(x) else 0))
 
@@ -982,8 +961,7 @@ class _SharedAct(torch.autograd.Function):
 def _wrap_shared(x, raw):
     if raw.mode == "none" or not (torch.is_grad_enabled() and x.requires_grad):
         return raw.out
-    out = _SharedAct.apply(x, raw)
-    return out
+    return _SharedAct.apply(x, raw)
 
 
 def _shared_activation(quantizer, x, num_bits, layerwise):
@@ -1028,8 +1006,7 @@ class _PairNode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, input, res, code, view_x):
         wq, xq, side_w, side_x, rows_w, rows_x, cols = res
-        ctx.fq = (rows_w, rows_x, cols, code, weight.dtype, _state().ref)
-        ctx.fq_foreign = False
+        ctx.fq = (rows_w, rows_x, cols, weight.dtype, _state().ref)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(side_w, side_x)  # saved tensors (either may be None): visible to saved-tensor hooks
         # (wq / xq are fresh tensors of the launch that nothing else refers to and become this node's outputs as they are; an xq that a
@@ -1049,41 +1026,36 @@ class _PairNode(torch.autograd.Function):
     def backward(ctx, gw, gx):
         # (runs on the autograd engine's device thread, where every line of Python costs 2-3x what it costs on the caller's --
         # tools/host_pieces.py --: the straight-line case is the C++ node's, this is the general form and the node's way out)
-        inplace_w = _INPLACE_WGRAD and gw is not None and not ctx.fq_foreign and _inplace_ok(gw)
-        rows_w, rows_x, cols, code, dtype, st = ctx.fq
+        inplace_w = _INPLACE_WGRAD and gw is not None and _inplace_ok(gw)
+        rows_w, rows_x, cols, dtype, st = ctx.fq
         _backward_started(st)
         side_w, side_x = ctx.saved_tensors
-        need_w, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if need_w and gw is not None and gw.dtype != dtype:
-            gw, inplace_w = gw.to(dtype), _INPLACE_WGRAD   # a fresh tensor of our own
-        elif not need_w:
-            gw = None
-        gx = gx.to(dtype) if (need_x and gx is not None and gx.dtype != dtype) else (gx if need_x else None)
-        if gw is None and gx is None:
-            return None, None, None, None, None
-        ow, ox = ops.pair_backward(gw, gx, side_w, side_x, rows_w, rows_x, cols, -2.0, 2.0, inplace_w=inplace_w)
-        return ow, ox, None, None, None
+        return _pair_backward(gw, gx, side_w, side_x, rows_w, rows_x, cols, dtype, ctx.needs_input_grad[0], ctx.needs_input_grad[1], inplace_w) + (None, None, None)
 
 
-class _CppCtx:
-    """what _PairNode.backward reads from its ctx, for a backward the C++ node hands back (see _pair_backward_from_cpp)"""
-    __slots__ = ("fq", "fq_foreign", "saved_tensors", "needs_input_grad")
+def _pair_backward(gw, gx, side_w, side_x, rows_w, rows_x, cols, dtype, need_w, need_x, inplace_w):
+    """-> the pair's two masked gradients: one launch over the side buffers.  inplace_w: the guard's decision (`_inplace_ok`), taken by the
+    caller on the gradient as it arrived."""
+    if need_w and gw is not None and gw.dtype != dtype:
+        gw, inplace_w = gw.to(dtype), _INPLACE_WGRAD   # a fresh tensor of our own
+    elif not need_w:
+        gw = None
+    gx = gx.to(dtype) if (need_x and gx is not None and gx.dtype != dtype) else (gx if need_x else None)
+    if gw is None and gx is None:
+        return None, None
+    return ops.pair_backward(gw, gx, side_w, side_x, rows_w, rows_x, cols, -2.0, 2.0, inplace_w=inplace_w)
 
 
 _CODE_DTYPE = {v: k for k, v in ops._DTYPES.items()}
+_pair_backward_slow = _graph_aware(lambda values, gw, gx: _pair_backward(gw, gx, *values))
 
 
 def _pair_backward_from_cpp(gw, gx, side_w, side_x, rows_w, rows_x, cols, code, need_w, need_x):
     """The C++ node's way out of its straight line (csrc/fq_autograd_node.cpp: a gradient of another dtype or none at all, create_graph,
     an unaligned gradient): the Python node's backward, called under the GIL on the engine's thread.  Never in place from here -- the
     reference counts `_inplace_ok` compares are those of a Python Function's arguments -- and the node has told its epoch cell already."""
-    ctx = _CppCtx()
-    ctx.fq = (rows_w, rows_x, cols, code, _CODE_DTYPE[code], None)
-    ctx.fq_foreign = True
-    ctx.saved_tensors = (side_w, side_x)
-    ctx.needs_input_grad = (need_w, need_x, False, False, False)
-    out = _PairNode.backward(ctx, gw, gx)
-    return out[0], out[1]
+    ow, ox = _pair_backward_slow((side_w, side_x, rows_w, rows_x, cols, _CODE_DTYPE[code], need_w, need_x, False), gw, gx)
+    return ow, ox
 
 
 def quantize_kv(key_states, value_states, clip_val_k, clip_val_v, num_bits):
@@ -1145,7 +1117,7 @@ def _note_output(st, out):
         return
     rec = st.outs
     if len(rec) >= 4:
-        del rec[0]
+        rec.pop(0)
     rec.append((weakref.ref(out), out._version, _region() if _top_hooks is not None else None, ops._stream(out)))
 
 
@@ -1162,8 +1134,9 @@ def _kv_discard(st):
     if stash is None:
         return
     _count("kv_pair_discarded")
-    if stash[4] not in _kv_off:
-        _kv_off.add(stash[4])
+    _, _, _, _, sig = stash     # (unpacked, not `.sig`: whoever plants a stash by hand may hand over a bare 5-tuple)
+    if sig not in _kv_off:
+        _kv_off.add(sig)
         _count("kv_pair_learned_off")
 
 
@@ -1181,26 +1154,27 @@ def _kv_hook(x, clip_val, num_bits):
     stream = ops._stream(x)
     stash = st.kv
     if stash is not None:
-        ref, ver, vres, state, sig = stash
-        if ref() is x and ver == x._version and state == _kv_state(st, clip_val, num_bits, stream):
+        if stash.ref() is x and stash.version == x._version and stash.state == _kv_state(st, clip_val, num_bits, stream):
             st.kv = None
             _count("kv_pair_hit")
-            vq, side_v, rows_v, cols, clip = vres   # V: quantized together with K a moment ago; its autograd node is built only now
-            return vq if side_v is None else _precomputed(x, vq, side_v, rows_v, cols, clip)
+            v = stash.v   # V: quantized together with K a moment ago; its autograd node is built only now
+            return v.vq if v.side is None else _precomputed(x, v.vq, v.side, v.rows, v.cols, v.clip)
         _kv_discard(st)
     rec = st.outs
     if not rec:
         return None
     for i in range(len(rec) - 1):
-        if rec[i][0]() is x:
-            if rec[i][1] != x._version:
+        k_ref, k_version, k_region, k_stream = rec[i]
+        if k_ref() is x:
+            v_ref, vver, v_region, v_stream = rec[i + 1]
+            if k_version != x._version:
                 return None
             region = _region()
-            if rec[i][2] is not region or rec[i + 1][2] is not region:
+            if k_region is not region or v_region is not region:
                 return None     # K's or V's projection ran in another saved-tensor-hooks region (see _region)
-            if rec[i][3] != stream or rec[i + 1][3] != stream:
+            if k_stream != stream or v_stream != stream:
                 return None     # produced on another stream than the one this launch would read them on: no pairing
-            v, vver = rec[i + 1][0](), rec[i + 1][1]
+            v = v_ref()
             if (v is None or v is x or vver != v._version or v.shape != x.shape or v.dtype != x.dtype or v.device != x.device
                     or not v.is_contiguous() or not x.is_contiguous() or v.requires_grad != x.requires_grad):
                 return None
@@ -1219,7 +1193,7 @@ def _kv_hook(x, clip_val, num_bits):
             # a loss that never uses V (a checkpointed producer would be recomputed and hand ZERO gradients to its parameters where the
             # reference leaves None: tests/test_gpu_random_programs.py).  Each of K and V gets its own node over its own side buffer.
             kq, vq, side_k, side_v, rows_k, rows_v, cols = res
-            st.kv = (weakref.ref(v), v._version, (vq, side_v if need else None, rows_v, cols, (lo, hi)), _kv_state(st, clip_val, num_bits, stream), sig)
+            st.kv = _KVStash(weakref.ref(v), v._version, _VResult(vq, side_v if need else None, rows_v, cols, (lo, hi)), _kv_state(st, clip_val, num_bits, stream), sig)
             return _precomputed(x, kq, side_k, rows_k, cols, (lo, hi)) if need else kq
     return None
 
@@ -1301,24 +1275,28 @@ class _PrecomputedAct(torch.autograd.Function):
             return None, None, None, None, None
         _backward_started(ctx.fq_st)
         (side,) = ctx.saved_tensors
-        lo, hi = ctx.clip
-        rows, cols = ctx.rows_cols
-        if ctx.wide:
-            return ops.train_backward_wide(grad_output, side, rows, cols, lo, hi, ctx.dtype), None, None, None, None
-        g = grad_output if grad_output.dtype == ctx.dtype else grad_output.to(ctx.dtype)
-        return ops.train_backward(g, side, rows, cols, lo, hi), None, None, None, None
+        return _one_backward(grad_output, side, *ctx.rows_cols, *ctx.clip, ctx.dtype, ctx.wide), None, None, None, None
 
 
-class _CppCtx1:
-    """what _PrecomputedAct.backward reads from its ctx, for a backward the C++ one-tensor node hands back"""
-    __slots__ = ("rows_cols", "clip", "dtype", "fq_st", "wide", "saved_tensors")
+def _one_backward(g, side, rows, cols, lo, hi, dtype, wide):
+    """-> the masked gradient of one tensor over its side buffer (wide: the fp32 gradient of the reference's fp32 result under autocast)"""
+    if wide:
+        return ops.train_backward_wide(g, side, rows, cols, lo, hi, dtype)
+    return ops.train_backward(g if g.dtype == dtype else g.to(dtype), side, rows, cols, lo, hi)
+
+
+_one_backward_slow = _graph_aware(lambda values, g: (None if g is None else _one_backward(g, *values),))
 
 
 def _one_backward_from_cpp(g, side, rows, cols, lo, hi, code, wide):
     """the C++ one-tensor node's way out of its straight line (another gradient dtype, create_graph, strided or unaligned gradients)"""
-    ctx = _CppCtx1()
-    ctx.rows_cols, ctx.clip, ctx.dtype, ctx.fq_st, ctx.wide, ctx.saved_tensors = (rows, cols), (lo, hi), _CODE_DTYPE[code], None, wide, (side,)
-    return _PrecomputedAct.backward(ctx, g)[0]
+    gx, = _one_backward_slow((side, rows, cols, lo, hi, _CODE_DTYPE[code], wide), g)
+    return gx
+
+
+def _explicit_else(explicit, default, applies):
+    """QuantizeLinear's rule for a setting it was not given: the explicit argument, else the process default where it applies to the layer"""
+    return explicit if explicit is not None else (default if applies else None)
 
 
 def _precomputed(x, y, side, rows, cols, clip):
@@ -1328,8 +1306,21 @@ def _precomputed(x, y, side, rows, cols, clip):
     return _PrecomputedAct.apply(x, (y, side), rows, cols, clip)
 
 
+def _node_over(weight, input_, res, code, view_x, need, cell):
+    """one autograd node over a QuantizeLinear's two fake-quantized operands (res: a two-tensor launch's 7-tuple, as ops.pair_forward gives
+    it) -- the C++ one where `cell` names the calling thread's epoch cell, else _PairNode -- or the bare results where neither operand
+    needs a gradient"""
+    if not need:
+        wq, xq, _, _, _, _, _ = res
+        return wq, xq
+    if cell is not None:
+        return _cnode.pair_node(weight, input_, *res, code, view_x, cell)
+    return _PairNode.apply(weight, input_, res, code, view_x)
+
+
 class QuantizeLinear(nn.Linear):
-    _fq_plan = None   # (input shape, input dtype, weight dtype, ops.pair_plan): the launch plan of the last input shape (a plain attribute)
+    _fq_plan = None   # a _Plan: the launch plan of the last input shape (a plain attribute)
+    _fq_wcache = None   # a _WCache while the weight cache holds this layer's fake-quantized weight (a plain attribute)
     weight_group_size = None   # group-wise scales (plain attributes: state_dict() keys stay the reference's)
     act_group_size = None
     weight_format = None       # MX formats (ops.MX_FORMATS): replace that operand's integer quantizer
@@ -1348,23 +1339,19 @@ class QuantizeLinear(nn.Linear):
         self.weight_layerwise = weight_layerwise
         # MX formats: an explicit argument always applies (and excludes that operand's group size and layerwise flag); the process default
         # (default_mx_formats) applies to the operands this layer quantizes, and then no default group size does
-        mw, ma = _DEFAULT_MX
-        if weight_format is not None:
-            if weight_group_size is not None or weight_layerwise:
-                raise ValueError("weight_format cannot be combined with weight_group_size or weight_layerwise")
-            ops.check_mx(tuple(self.weight.shape), weight_format)
-            self.weight_format = weight_format
-        elif mw is not None and w_bits < 32 and weight_group_size is None and not weight_layerwise:
-            self.weight_format = mw
-            ops.check_mx(tuple(self.weight.shape), mw)
-        if act_format is not None:
-            if act_group_size is not None or act_layerwise:
-                raise ValueError("act_format cannot be combined with act_group_size or act_layerwise")
-            ops.check_mx((self.in_features,), act_format)
-            self.act_format = act_format
-        elif ma is not None and a_bits < 32 and act_group_size is None and not act_layerwise:
-            self.act_format = ma
-            ops.check_mx((self.in_features,), ma)
+        mw, ma = _DEFAULTS["mx"]
+        if weight_format is not None and (weight_group_size is not None or weight_layerwise):
+            raise ValueError("weight_format cannot be combined with weight_group_size or weight_layerwise")
+        fmt = _explicit_else(weight_format, mw, w_bits < 32 and weight_group_size is None and not weight_layerwise)
+        if fmt is not None:
+            ops.check_mx(tuple(self.weight.shape), fmt)
+            self.weight_format = fmt
+        if act_format is not None and (act_group_size is not None or act_layerwise):
+            raise ValueError("act_format cannot be combined with act_group_size or act_layerwise")
+        fmt = _explicit_else(act_format, ma, a_bits < 32 and act_group_size is None and not act_layerwise)
+        if fmt is not None:
+            ops.check_mx((self.in_features,), fmt)
+            self.act_format = fmt
         # the rotation: an explicit True needs both operands in an MX format (rotating one alone changes the product) and whole 64-runs;
         # the process default (default_mx_rotate) applies to the layers that meet both
         both_mx = self.weight_format is not None and self.act_format is not None
@@ -1374,42 +1361,30 @@ class QuantizeLinear(nn.Linear):
                                  "when both are rotated")
             ops.check_mx_rotate((self.in_features,), "mx_rotate")
             self.mx_rotate = True
-        elif mx_rotate is None and _DEFAULT_MX_ROTATE and both_mx and self.in_features % ops.MX_ROTATE == 0:
+        elif mx_rotate is None and _DEFAULTS["mx_rotate"] and both_mx and self.in_features % ops.MX_ROTATE == 0:
             self.mx_rotate = True
         # scale rule and gradient of the MX operands: an explicit argument needs one; the process defaults apply to the layers that have one
         any_mx = self.weight_format is not None or self.act_format is not None
-        if mx_scale_rule is not None:
-            ops.check_mx_scale_rule(mx_scale_rule, "mx_scale_rule")
-            if not any_mx:
-                raise ValueError("mx_scale_rule applies to MX operands: this layer has neither weight_format nor act_format")
-            self.mx_scale_rule = mx_scale_rule
-        elif any_mx:
-            self.mx_scale_rule = _DEFAULT_MX_SCALE_RULE
-        if mx_ste is not None:
-            _check_mx_ste(mx_ste, "mx_ste")
-            if not any_mx:
-                raise ValueError("mx_ste applies to MX operands: this layer has neither weight_format nor act_format")
-            self.mx_ste = mx_ste
-        elif any_mx:
-            self.mx_ste = _DEFAULT_MX_STE
+        for name, given, check in (("mx_scale_rule", mx_scale_rule, ops.check_mx_scale_rule), ("mx_ste", mx_ste, _check_mx_ste)):
+            if given is not None:
+                check(given, name)
+                if not any_mx:
+                    raise ValueError(f"{name} applies to MX operands: this layer has neither weight_format nor act_format")
+            if any_mx:
+                setattr(self, name, _explicit_else(given, _DEFAULTS[name], True))
         # group sizes: an explicit argument is checked and kept; the process default (default_group_sizes) applies where it means something
-        dw, da = _DEFAULT_GROUPS
-        if self.weight_format is not None:
-            dw = None
-        if self.act_format is not None:
-            da = None
-        if weight_group_size is not None:
-            if not 3 <= w_bits < 32:
-                raise ValueError(f"weight_group_size applies to SymQuantizer weights (3 <= w_bits < 32), this layer has w_bits={w_bits}")
-            self.weight_group_size = ops.check_group(tuple(self.weight.shape), weight_group_size, weight_layerwise)
-        elif dw is not None and 3 <= w_bits < 32 and not weight_layerwise:
-            self.weight_group_size = ops.check_group(tuple(self.weight.shape), dw)
-        if act_group_size is not None:
-            if not 2 < a_bits < 32:
-                raise ValueError(f"act_group_size applies to quantized activations (2 < a_bits < 32), this layer has a_bits={a_bits}")
-            self.act_group_size = ops.check_group((self.in_features,), act_group_size, act_layerwise)
-        elif da is not None and 2 < a_bits < 32 and not act_layerwise:
-            self.act_group_size = ops.check_group((self.in_features,), da)
+        # (an operand without an MX format, of a bit width the group quantizer serves, not layerwise)
+        dw, da = _DEFAULTS["groups"]
+        if weight_group_size is not None and not 3 <= w_bits < 32:
+            raise ValueError(f"weight_group_size applies to SymQuantizer weights (3 <= w_bits < 32), this layer has w_bits={w_bits}")
+        g = _explicit_else(weight_group_size, dw, self.weight_format is None and 3 <= w_bits < 32 and not weight_layerwise)
+        if g is not None:
+            self.weight_group_size = ops.check_group(tuple(self.weight.shape), g, weight_layerwise)
+        if act_group_size is not None and not 2 < a_bits < 32:
+            raise ValueError(f"act_group_size applies to quantized activations (2 < a_bits < 32), this layer has a_bits={a_bits}")
+        g = _explicit_else(act_group_size, da, self.act_format is None and 2 < a_bits < 32 and not act_layerwise)
+        if g is not None:
+            self.act_group_size = ops.check_group((self.in_features,), g, act_layerwise)
         if 2 < self.a_bits < 32:
             self.act_quantizer = SymQuantizer if symmetric else AsymQuantizer   # (attribute absent otherwise, as in the reference :184-188)
         self._act_kind = "sym" if symmetric else "asym"  # what torch.compile's trace reads (a class identity test does not trace)
@@ -1421,16 +1396,19 @@ class QuantizeLinear(nn.Linear):
         if w.device.type == "cpu":
             if not cpu_tensors.ENABLED:
                 cpu_tensors.refuse(w, "low_bit_weight")
-            return _LowBitWeightCpu.apply(w, self.w_bits, self.weight_layerwise)
+            return _LowBitWeight.apply(w, self.w_bits, "cpu", self.weight_layerwise)
         if _W12_FUSED and not self.weight_layerwise and w.is_cuda and w.is_contiguous() and _w12_fused_verified(w):
             try:
-                return _LowBitWeightFused.apply(w, self.w_bits)
+                return _LowBitWeight.apply(w, self.w_bits, "fused", None)
             except _NotServed:
                 pass
+        return _LowBitWeight.apply(w, self.w_bits, "scaled", self._low_bit_scale(w))
+
+    def _low_bit_scale(self, w):
+        """the 1-/2-bit branches' scale as ATen reduces it: mean |w| per output channel (or of the whole weight), twice that for 2 bits"""
         with torch.no_grad():
             absmean = w.abs().mean() if self.weight_layerwise else w.abs().mean(dim=1, keepdim=True)
-            sc = absmean if self.w_bits == 1 else 2 * absmean
-        return _LowBitWeight.apply(w, sc, self.w_bits)
+            return absmean if self.w_bits == 1 else 2 * absmean
 
     def _wcache_key(self):
         w = self.weight
@@ -1438,17 +1416,15 @@ class QuantizeLinear(nn.Linear):
 
     def _quantized_weight(self):
         w = self.weight
-        if self.weight_group_size is not None:   # (no weight cache for grouped weights)
-            return _GroupQuantizer.apply(w, _CLIP, self.w_bits, self.weight_group_size, "sym", True, True)
         ac = ops.autocast_active(w)
         if not _WEIGHT_CACHE or not w.is_cuda or w.is_inference() or (ac and not ops.autocast_narrow_ok(w)):
             # (an fp16 weight inside autocast(bf16), or the reverse, gets the reference's fp32 result and an fp32 gradient:
             # the plain node handles both dtypes; the cache's node works in the weight's dtype only)
             return _SymQuantizerWeight.apply(w, _CLIP, self.w_bits, self.weight_layerwise)
         key = self._wcache_key()
-        ent = getattr(self, "_fq_wcache", None)
-        if ent is not None and ent[0] == key:
-            cached = ent[1]
+        ent = self._fq_wcache
+        if ent is not None and ent.key == key:
+            cached = ent.value
             _count("wcache_hit")
             if not _WEIGHT_CACHE_PERSISTENT:
                 self._fq_wcache = None  # second use within the step (the checkpoint recompute): done with it
@@ -1470,146 +1446,123 @@ class QuantizeLinear(nn.Linear):
                     y = ops.sym_quantize(w, self.w_bits, self.weight_layerwise)
                 else:
                     y, bounds = ops.sym_quantize(w, self.w_bits, self.weight_layerwise, want_bounds=True)
-            cached = (y, bounds, mask, rc)
-            self._fq_wcache = (key, cached)
+            cached = _QWeight(y, bounds, mask, rc)
+            self._fq_wcache = _WCache(key, cached)
             _count("wcache_fill")
         if torch.is_grad_enabled() and w.requires_grad:
             return _ReuseQuantizedWeight.apply(w, cached, _CLIP)  # launches nothing; backward = the ordinary STE
-        return cached[0]
+        return cached.y
 
-    def _pair_forward(self, input_):
-        """weight and input of this module under ONE autograd node: both in one launch, or -- when a sibling projection has already
-        fake-quantized this input -- the weight's own launch + the remembered activation.  None when not applicable (then the ordinary
-        two calls run).  What depends only on shapes / dtype / device is decided once per module and input shape (`ops.pair_plan`)."""
+    def _new_plan(self, input_, settings):
+        """What depends only on shapes / dtypes / device and the module's settings, decided once per module and input shape: whether the
+        operand pair applies at all (`eligible`; grouped layers take the single-launch route: one group launch for the weight, the
+        activation's own), and for contiguous operands the launch itself (`launch`: ops.pair_plan's tuple, `bits`: the widths as ints)."""
+        w_bits, a_bits, act_layerwise, weight_layerwise, act_quantizer, weight_group, act_group = settings
+        ok = (3 <= w_bits < 32 and 2 < a_bits < 32 and act_quantizer is SymQuantizer and not act_layerwise and not weight_layerwise
+              and weight_group is None and act_group is None)
+        return _Plan(input_.shape, input_.dtype, self.weight.dtype, settings, ok, ops.pair_plan(self.weight, input_) if ok else None,
+                     (ops.bits_arg(w_bits), ops.bits_arg(a_bits)) if ok else None)
+
+    def _pair_forward(self, input_, planned=True):
+        """weight and input of this module in ONE launch, under one autograd node -- or, when a sibling projection has already fake-quantized
+        this input, the weight's own launch.  None when not applicable (then the ordinary two calls run).
+        The planned route (contiguous operands of the planned dtype, no weight cache) launches straight from the cached plan, with the
+        C++ node in one call; the general route (strided operands, the weight cache, dtype mixes: ops.pair_forward's checks) decides per
+        call, and decides again (planned=False) when a planned launch is refused.  On a sibling hit the planned route builds one node
+        over the weight's own launch + the remembered data; the general route returns None, and the caller builds the weight's ordinary
+        node + a _SharedAct."""
         if not (_PAIR and _BACKWARD_MODE == "mask"):
             return None
         weight = self.weight
         plan = self._fq_plan
         # (the module's settings are plain attributes a caller may change after construction: they are part of what a plan is valid for)
-        if (plan is None or plan[0] != input_.shape or plan[1] is not input_.dtype or plan[2] is not weight.dtype
-                or plan[4] != (self.w_bits, self.a_bits, self.act_layerwise, self.weight_layerwise, getattr(self, "act_quantizer", None),
-                               self.weight_group_size, self.act_group_size)):
-            # (grouped layers take the single-launch route: one group launch for the weight, the activation's own)
-            ok = (3 <= self.w_bits < 32 and 2 < self.a_bits < 32 and getattr(self, "act_quantizer", None) is SymQuantizer and not self.act_layerwise
-                  and not self.weight_layerwise and self.weight_group_size is None and self.act_group_size is None)
-            plan = self._fq_plan = (input_.shape, input_.dtype, weight.dtype, ops.pair_plan(weight, input_) if ok else None,
-                                    (self.w_bits, self.a_bits, self.act_layerwise, self.weight_layerwise, getattr(self, "act_quantizer", None),
-                                     self.weight_group_size, self.act_group_size),
-                                    (ops.bits_arg(self.w_bits), ops.bits_arg(self.a_bits)) if ok else None)
-        pp = plan[3]
-        if pp is None or _WEIGHT_CACHE or not (weight.is_contiguous() and input_.is_contiguous()) or input_.is_inference() or weight.is_inference():
-            return self._pair_forward_general(input_)
+        settings = (self.w_bits, self.a_bits, self.act_layerwise, self.weight_layerwise, getattr(self, "act_quantizer", None),
+                    self.weight_group_size, self.act_group_size)
+        if (plan is None or plan.shape != input_.shape or plan.in_dtype is not input_.dtype or plan.w_dtype is not weight.dtype
+                or plan.settings != settings):
+            plan = self._fq_plan = self._new_plan(input_, settings)
+        if not plan.eligible or input_.is_inference() or weight.is_inference():
+            return None   # (no version counters under torch.inference_mode: nothing is paired, shared or remembered)
         grad = torch.is_grad_enabled()
         need_w, need_x = grad and weight.requires_grad, grad and input_.requires_grad
-        ac = pp[0] != 0 and torch.is_autocast_enabled("cuda")      # (code 0: fp32 tensors are untouched by autocast)
-        if ac and torch.get_autocast_dtype("cuda") is not weight.dtype:
-            return self._pair_forward_general(input_)
-        share = _SHARE_ACT and _top_hooks is not None
+        wkey = None
+        if planned and plan.launch is not None and not _WEIGHT_CACHE and weight.is_contiguous() and input_.is_contiguous():
+            code, cols, rows_w, rows_x, mask_w, mask_x, device = plan.launch
+            w_bits, a_bits = plan.bits
+            ac = code != 0 and torch.is_autocast_enabled("cuda")      # (code 0: fp32 tensors are untouched by autocast)
+            planned = not ac or torch.get_autocast_dtype("cuda") is weight.dtype
+        else:
+            planned = False
+            ac = ops.autocast_active(input_)
+            if _WEIGHT_CACHE:
+                # With the weight cache on, the FIRST use of a weight in a step still shares a launch with its input and fills the
+                # cache from it; the second use (the checkpoint recompute) finds the entry and launches nothing for the weight.
+                wkey = self._wcache_key()
+                ent = self._fq_wcache
+                if ent is not None and ent.key == wkey:
+                    return None
+        share = _SHARE_ACT and (_top_hooks is not None or _memory_ok("share"))   # (counts / warns where the region API is missing: nothing is remembered)
         if share:
             st = _state()
-            key = (_SymQuantizerOperand, self.a_bits, False, _MODE_CODE["mask"] + 4 * ops._semantics + (8 if grad else 0) + (16 if ac else 0))
-            region, stream = _region(), ops._raw_stream(pp[6])
+            key = (_SymQuantizerOperand, self.a_bits, False, _MODE_CODE["mask"] + 4 * ops._semantics + (8 if grad else 0) + (16 if ac else 0))   # _state_word
+            region = _region()
+            if planned:
+                stream = ops._raw_stream(device)
+            else:
+                stream = ops._stream(input_) if input_.is_cuda else 0
             raw = _act_lookup(st, key, input_, region, stream)
             if raw is not None:
                 # a sibling projection already quantized this activation: only the weight is left to do.  One node over both where the
                 # remembered data has the pair's shape (mask mode, operand dtype); otherwise the two ordinary nodes
-                if raw.mode not in ("mask", "none") or raw.out.dtype is not weight.dtype:
+                if not planned or raw.mode not in ("mask", "none") or raw.out.dtype is not weight.dtype:
                     return None
+                side_x = raw.saved[0] if need_x else None
+                pair = None
                 if _USE_CNODE:     # the weight's launch and the node in one call into C++
-                    out = _cnode.weight_forward_node(weight, input_, raw.out, raw.saved[0] if need_x else None, pp[0], pp[1], pp[2], pp[3], pp[4], plan[5][0],
-                                                     need_w, need_x, ac, ops._SEM_AUTOCAST if ac else ops._semantics, st.cell)
-                    if out is not None:
-                        _count("act_share_hit")
-                        _count("single_launch")
-                        return out
-                res = ops.weight_forward(weight, self.w_bits, -2.0, 2.0, need_w)
-                if res is None:
-                    return None
+                    pair = _cnode.weight_forward_node(weight, input_, raw.out, side_x, code, cols, rows_w, rows_x, mask_w, w_bits,
+                                                      need_w, need_x, ac, ops._SEM_AUTOCAST if ac else ops._semantics, st.cell)
+                if pair is None:
+                    alone = ops.weight_forward(weight, self.w_bits, -2.0, 2.0, need_w)
+                    if alone is None:
+                        return None
+                    wq, side_w, w_rows, w_cols = alone
+                    pair = _node_over(weight, input_, (wq, raw.out, side_w, side_x, w_rows, rows_x, w_cols), code, True, need_w or need_x,
+                                      st.cell if _USE_CNODE else None)
                 _count("act_share_hit")
                 _count("single_launch")
-                wq, side_w, rows_w, cols = res
-                if not (need_w or need_x):
-                    return wq, raw.out
-                if _USE_CNODE:
-                    return _cnode.pair_node(weight, input_, wq, raw.out, side_w, raw.saved[0] if need_x else None, rows_w, pp[3], cols, pp[0], True, st.cell)
-                return _PairNode.apply(weight, input_, (wq, raw.out, side_w, raw.saved[0] if need_x else None, rows_w, pp[3], cols), pp[0], True)
-        elif _SHARE_ACT:
-            _memory_ok("share")   # counts / warns: the region API is missing, nothing is remembered
-        if _USE_CNODE:
+                return pair
+        if planned and _USE_CNODE:
             # allocations, the launch and the node in one call into C++ (csrc/fq_autograd_node.cpp::pair_forward)
-            w_bits, a_bits = plan[5]
-            out = _cnode.pair_forward(weight, input_, pp[0], pp[1], pp[2], pp[3], pp[4], pp[5], w_bits, a_bits, need_w, need_x, ac,
-                                      ops._SEM_AUTOCAST if ac else ops._semantics, (st if share else _state()).cell)
-            if out is None:
-                return self._pair_forward_general(input_)
-            side_x = out[2]
+            made = _cnode.pair_forward(weight, input_, code, cols, rows_w, rows_x, mask_w, mask_x, w_bits, a_bits, need_w, need_x, ac,
+                                       ops._SEM_AUTOCAST if ac else ops._semantics, (st if share else _state()).cell)
+            if made is None:
+                return self._pair_forward(input_, False)
+            built_in_cpp = True
+            wq, xq, side_x = made       # (xq is the node's own output tensor; siblings never use it as a tensor of their graph)
         else:
-            res = ops.pair_forward(weight, input_, self.w_bits, self.a_bits, -2.0, 2.0, need_w, need_x)
+            built_in_cpp = False
+            res = ops.pair_forward(weight, input_, self.w_bits, self.a_bits, -2.0, 2.0, need_w or wkey is not None, need_x)
             if res is None:
-                return self._pair_forward_general(input_)
-            out = _PairNode.apply(weight, input_, res, pp[0], False) if (need_w or need_x) else (res[0], res[1])
-            side_x = res[3]
+                return self._pair_forward(input_, False) if planned else None
+            wq, xq, side_w, side_x, rows_w, rows_x, cols = res
         _count("pair_launch")
         if share:
-            # remembered for the sibling projections: the data (for a sibling's view of it: _PairNode / _SharedAct) + its side buffer.
-            # out[1] is this node's own output tensor when there is a node; siblings never use it as a tensor of their graph.
+            # remembered for the sibling projections: the data (for a sibling's view of it: _PairNode / _SharedAct) + its side buffer
             _count("act_share_miss")
-            st.acts[key] = (weakref.ref(input_), input_._version, input_.data_ptr(), _Raw(out[1], "mask", (side_x,), (-2.0, 2.0), (pp[3], pp[1])) if need_x
-                            else _Raw(out[1], "none"), out[1]._version, input_.requires_grad, region, stream)
-        return out[0], out[1]
-
-    def _pair_forward_general(self, input_):
-        """the same decision without a plan: strided operands, the weight cache, inference tensors, dtype mixes (ops.pair_forward's checks)"""
-        if not (3 <= self.w_bits < 32 and 2 < self.a_bits < 32):
-            return None
-        weight = self.weight
-        if input_.is_inference() or weight.is_inference():
-            return None   # no version counters under torch.inference_mode: nothing is paired, shared or remembered
-        if self.act_quantizer is not SymQuantizer or self.act_layerwise or self.weight_layerwise:
-            return None
-        if self.weight_group_size is not None or self.act_group_size is not None:
-            return None
-        wkey = None
-        if _WEIGHT_CACHE:
-            # With the weight cache on, the FIRST use of a weight in a step still shares a launch with its input and fills the
-            # cache from it; the second use (the checkpoint recompute) finds the entry and launches nothing for the weight.
-            wkey = self._wcache_key()
-            ent = getattr(self, "_fq_wcache", None)
-            if ent is not None and ent[0] == wkey:
-                return None
-        grad = torch.is_grad_enabled()
-        need_w, need_x = grad and weight.requires_grad, grad and input_.requires_grad
-        share = _SHARE_ACT and _memory_ok("share")
-        if share:
-            st = _state()
-            key = (_SymQuantizerOperand, self.a_bits, False, _state_word(input_))
-            region, stream = _region(), (ops._stream(input_) if input_.is_cuda else 0)
-            if _act_lookup(st, key, input_, region, stream) is not None:
-                return None   # a sibling already quantized this activation: the weight's own node + a _SharedAct over the remembered data
-        res = ops.pair_forward(weight, input_, self.w_bits, self.a_bits, -2.0, 2.0, need_w or wkey is not None, need_x)
-        if res is None:
-            return None
-        _count("pair_launch")
-        code = ops._DTYPES[weight.dtype]
-        if share:
-            _count("act_share_miss")
-            rows_x, cols = res[5], res[6]
-            _act_store(st, key, input_, _Raw(res[1], "mask", (res[3],), (-2.0, 2.0), (rows_x, cols)) if need_x else _Raw(res[1], "none"), region, stream)
+            _act_store(st, key, input_, _Raw(xq, "mask", (side_x,), (-2.0, 2.0), (rows_x, cols)) if need_x else _Raw(xq, "none"), region, stream)
+        if built_in_cpp:
+            return wq, xq
         if wkey is not None:
             # bounds + mask are recorded even without grad (the recompute pass's backward needs them), and the results are
             # wrapped in the SAME nodes the recompute pass will build (_ReuseQuantizedWeight for the weight, a side-buffer
             # node for the input), so non-reentrant checkpointing sees identical saved tensors in both passes
-            rows_w, rows_x, cols = res[4], res[5], res[6]
-            side_w, side_x = res[2], res[3]
-            cached = (res[0], *ops.split_side(side_w, rows_w), ops.rows_cols(tuple(weight.shape), False))
-            self._fq_wcache = (wkey, cached)
+            cached = _QWeight(wq, *ops.split_side(side_w, rows_w), ops.rows_cols(tuple(weight.shape), False))
+            self._fq_wcache = _WCache(wkey, cached)
             _count("wcache_fill")
-            wq = _ReuseQuantizedWeight.apply(weight, cached, _CLIP) if need_w else res[0]
-            xq = _precomputed(input_, res[1], side_x, rows_x, cols, (-2.0, 2.0)) if need_x else res[1]
-            return wq, xq
-        if need_w or need_x:
-            return _PairNode.apply(weight, input_, res, code, share)
-        return res[0], res[1]
+            return (_ReuseQuantizedWeight.apply(weight, cached, _CLIP) if need_w else wq,
+                    _precomputed(input_, xq, side_x, rows_x, cols, (-2.0, 2.0)) if need_x else xq)
+        # (on the general route with sharing the remembered xq stays plain data: the node gets a tensor of its own over the same memory)
+        return _node_over(weight, input_, res, ops._DTYPES[weight.dtype], share and not planned, need_w or need_x, None)
 
     def export_weight(self, container=None):
         """The integer form of this layer's fake-quantized weight for an inference export: packed bins (int4 for
@@ -1621,67 +1574,84 @@ class QuantizeLinear(nn.Linear):
             raise ValueError(f"export_weight serves 3 <= w_bits < 32 (SymQuantizer weights), this layer has w_bits={self.w_bits}")
         return ops.sym_export(self.weight.detach(), self.w_bits, self.weight_layerwise, container=container, group_size=self.weight_group_size)
 
-    def _forward_compiled(self, input_):
-        """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
-        if self.weight_format is not None:   # MX: llmqat_amd::mx_fake_quant (identity gradient) / mx_fake_quant_rot (Q(W R), gradient g R), or
-            weight = _mx_apply(self.weight, self.weight_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)   # the section 16 ops
-        elif self.w_bits >= 32:
-            weight = self.weight
-        elif self.w_bits >= 3 and self.weight_group_size is not None:   # grouped: the same custom ops on the [-1, g] view
-            g = self.weight_group_size
-            weight = compiled.fake_quant("sym", self.weight.reshape(-1, g), _CLIP, self.w_bits, False, narrow=True).reshape(self.weight.shape)
-        elif self.w_bits >= 3:
-            weight = compiled.fake_quant("sym", self.weight, _CLIP, self.w_bits, self.weight_layerwise, narrow=True)
-        else:
-            with torch.no_grad():
-                absmean = self.weight.abs().mean() if self.weight_layerwise else self.weight.abs().mean(dim=1, keepdim=True)
-                sc = absmean if self.w_bits == 1 else 2 * absmean
-            weight = compiled.low_bit_weight_op(self.weight, sc, self.w_bits)
+    # Which quantizer serves an operand: decided here once, applied three times -- eagerly (forward), for a layer with an MX format
+    # (_forward_mx: no pair, no cache, no sharing) and while torch.compile traces (_forward_compiled: the same kernels as custom ops).
+    def _weight_route(self):
+        """-> "mx" | "none" (w_bits >= 32) | "group" | "sym" (3 <= w_bits) | "low" (1 / 2 bits)"""
+        if self.weight_format is not None:
+            return "mx"
+        if self.w_bits >= 32:
+            return "none"
+        if self.w_bits >= 3:
+            return "sym" if self.weight_group_size is None else "group"
+        return "low"
+
+    def _act_route(self):
+        """-> "mx" | "none" (a_bits <= 2 or >= 32) | "group" | "row" (the layer's act_quantizer, one scale per row)"""
         if self.act_format is not None:
-            input_ = _mx_apply(input_, self.act_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)
-        elif 2 < self.a_bits < 32 and self.act_group_size is not None:
-            g = self.act_group_size
-            input_ = compiled.fake_quant(self._act_kind, input_.reshape(-1, g), _CLIP, self.a_bits, False, narrow=True).reshape(input_.shape)
-        elif 2 < self.a_bits < 32:
-            input_ = compiled.fake_quant(self._act_kind, input_, _CLIP, self.a_bits, self.act_layerwise, narrow=True)
+            return "mx"
+        if not 2 < self.a_bits < 32:
+            return "none"
+        return "row" if self.act_group_size is None else "group"
+
+    def _group_weight(self):
+        return _GroupQuantizer.apply(self.weight, _CLIP, self.w_bits, self.weight_group_size, "sym", True, True)   # (no weight cache for grouped weights)
+
+    def _group_act(self, input_):
+        return _GroupQuantizer.apply(input_, _CLIP, self.a_bits, self.act_group_size, self._act_kind, True, False)
+
+    def _finish(self, input_, weight):
         out = nn.functional.linear(input_, weight)
         if self.bias is not None:
             out += self.bias.view(1, -1).expand_as(out)
         return out
 
+    def _forward_compiled(self, input_):
+        """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
+        route, weight = self._weight_route(), self.weight
+        if route == "mx":   # llmqat_amd::mx_fake_quant (identity gradient) / mx_fake_quant_rot (Q(W R), gradient g R), or the section 16 ops
+            weight = _mx_apply(weight, self.weight_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)
+        elif route == "group":   # the same custom ops on the [-1, g] view
+            weight = compiled.fake_quant("sym", weight.reshape(-1, self.weight_group_size), _CLIP, self.w_bits, False, narrow=True).reshape(weight.shape)
+        elif route == "sym":
+            weight = compiled.fake_quant("sym", weight, _CLIP, self.w_bits, self.weight_layerwise, narrow=True)
+        elif route == "low":
+            weight = compiled.low_bit_weight_op(weight, self._low_bit_scale(weight), self.w_bits)
+        route = self._act_route()
+        if route == "mx":
+            input_ = _mx_apply(input_, self.act_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)
+        elif route == "group":
+            input_ = compiled.fake_quant(self._act_kind, input_.reshape(-1, self.act_group_size), _CLIP, self.a_bits, False, narrow=True).reshape(input_.shape)
+        elif route == "row":
+            input_ = compiled.fake_quant(self._act_kind, input_, _CLIP, self.a_bits, self.act_layerwise, narrow=True)
+        return self._finish(input_, weight)
+
     def _forward_mx(self, input_):
         """an MX layer (eager): one launch per quantized operand forward, none backward (identity gradient).  No operand pair, C++ pair
         node, weight cache or activation sharing; an operand without a format keeps its integer quantizer (uncached, unshared).
-        mx_rotate: F.linear(Q(x R), Q(W R)), still one launch per operand forward, and one rotate launch per operand gradient.
+        mx_rotate (both operands have a format: the constructor's check): F.linear(Q(x R), Q(W R)), still one launch per operand forward,
+        and one rotate launch per operand gradient.
         mx_ste="clip": each MX operand's forward launch also writes its saturation bitmap, and its gradient is one masked launch."""
-        rule, ste = self.mx_scale_rule, self.mx_ste
-        if self.mx_rotate:   # both operands have a format (the constructor's check)
-            out = nn.functional.linear(_mx_apply(input_, self.act_format, True, rule, ste), _mx_apply(self.weight, self.weight_format, True, rule, ste))
-            if self.bias is not None:
-                out += self.bias.view(1, -1).expand_as(out)
-            return out
-        if self.weight_format is not None:
-            weight = _mx_apply(self.weight, self.weight_format, False, rule, ste)
-        elif self.w_bits >= 32:
-            weight = self.weight
-        elif self.weight_group_size is not None:
-            weight = _GroupQuantizer.apply(self.weight, _CLIP, self.w_bits, self.weight_group_size, "sym", True, True)
-        elif self.w_bits >= 3:
-            weight = _SymQuantizerWeight.apply(self.weight, _CLIP, self.w_bits, self.weight_layerwise)
-        else:
-            weight = self._low_bit_weight(self.weight)
-        if self.act_format is not None:
-            input_ = _mx_apply(input_, self.act_format, False, rule, ste)
-        elif 2 < self.a_bits < 32:
-            if self.act_group_size is not None:
-                input_ = _GroupQuantizer.apply(input_, _CLIP, self.a_bits, self.act_group_size, self._act_kind, True, False)
-            else:
-                quantizer = _SymQuantizerOperand if self.act_quantizer is SymQuantizer else self.act_quantizer
-                input_ = quantizer.apply(input_, _CLIP, self.a_bits, self.act_layerwise)
-        out = nn.functional.linear(input_, weight)
-        if self.bias is not None:
-            out += self.bias.view(1, -1).expand_as(out)
-        return out
+        route, weight = self._weight_route(), self.weight
+        if route == "low" and self.weight_group_size is not None:
+            route = "group"    # (a group size ASSIGNED to a 1-/2-bit layer -- the constructor refuses one: this path alone has always honoured it)
+        if route == "mx":
+            weight = _mx_apply(weight, self.weight_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)
+        elif route == "group":
+            weight = self._group_weight()
+        elif route == "sym":
+            weight = _SymQuantizerWeight.apply(weight, _CLIP, self.w_bits, self.weight_layerwise)
+        elif route == "low":
+            weight = self._low_bit_weight(weight)
+        route = self._act_route()
+        if route == "mx":
+            input_ = _mx_apply(input_, self.act_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)
+        elif route == "group":
+            input_ = self._group_act(input_)
+        elif route == "row":
+            quantizer = _SymQuantizerOperand if self.act_quantizer is SymQuantizer else self.act_quantizer
+            input_ = quantizer.apply(input_, _CLIP, self.a_bits, self.act_layerwise)
+        return self._finish(input_, weight)
 
     def forward(self, input_):
         assert len(self.weight.size()) == 2
@@ -1695,20 +1665,19 @@ class QuantizeLinear(nn.Linear):
             weight, input_ = pair
         else:
             _count("single_launch")
-            if self.w_bits >= 32:
-                weight = self.weight
-            elif self.w_bits >= 3:
-                weight = self._quantized_weight()
-            else:
-                weight = self._low_bit_weight(self.weight)
-            if 2 < self.a_bits < 32:
-                if self.act_group_size is not None:
-                    input_ = _GroupQuantizer.apply(input_, _CLIP, self.a_bits, self.act_group_size, self._act_kind, True, False)
-                else:
-                    input_ = _shared_activation(self.act_quantizer, input_, self.a_bits, self.act_layerwise)
-        out = nn.functional.linear(input_, weight)
-        if self.bias is not None:
-            out += self.bias.view(1, -1).expand_as(out)
+            route, weight = self._weight_route(), self.weight
+            if route == "group":
+                weight = self._group_weight()
+            elif route == "sym":
+                weight = self._quantized_weight()     # (through the weight cache, where that is on)
+            elif route == "low":
+                weight = self._low_bit_weight(weight)
+            route = self._act_route()
+            if route == "group":
+                input_ = self._group_act(input_)
+            elif route == "row":
+                input_ = _shared_activation(self.act_quantizer, input_, self.a_bits, self.act_layerwise)
+        out = self._finish(input_, weight)
         if _PAIR_KV and out.is_cuda:
             _note_output(_state(), out)   # the KV-cache hooks may follow (point 7): ~1 us of bookkeeping
         return out
