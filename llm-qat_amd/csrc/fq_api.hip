@@ -37,9 +37,9 @@ hipError_t& launch_status() {
 namespace {
 
 struct MaskArgs {
-    void* mask = nullptr;
-    size_t bytes = 0;
-    float lo = 0.f, hi = 0.f;
+    void* mask;
+    size_t bytes;
+    float lo, hi;
 };
 
 // fq_rows_view (elements) -> RowPitch (bytes).  A view that describes contiguous rows stays off.  false: not representable.
@@ -55,17 +55,38 @@ bool set_pitch(RowPitch& p, const fq_rows_view* v, int64_t rows, int64_t cols, i
     return true;
 }
 
-// the training-mode outputs of a forward: the bitmap's place and size, the clip rounded to the dtype and its integer form
-int set_mask_args(RowArgs& a, void* mask, size_t bytes, float lo, float hi, int dtype) {
-    const int64_t mrw = mask_row_words(a.cols, esize_of(dtype));
-    if (!mrw) return fail(FQ_ERR_UNSUPPORTED, "shape not served by the STE-mask path (see fq_ste_mask_bytes)");
-    if (bytes < (size_t)a.rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)a.rows * mrw * 8);
-    a.mask = (uint64_t*)mask;
-    a.mask_row_words = mrw;
-    a.lo = host_rb(lo, dtype);
-    a.hi = host_rb(hi, dtype);
-    a.clipk = ste_clip_key(a.lo, a.hi, dtype);
-    return FQ_OK;
+// the shared check lists below return CONTINUE where the entry point goes on; any other value is the entry point's result
+constexpr int CONTINUE = 1;
+
+// what rowwise<> and fq_sym_fwd_autocast check first, behind their own dtype check (named: the site's wording of a negative shape)
+int fwd_head(const void* x, const void* y, int64_t rows, int64_t cols, int bits, int sem, bool named) {
+    if (bits < 1 || bits > 31) return fail(FQ_ERR_BITS, "num_bits=%d outside [1, 31]", bits);
+    if (sem != FQ_SEM_CPU_EAGER && sem != FQ_SEM_DEVICE_EAGER) return fail(FQ_ERR_ARG, "unknown semantics code %d", sem);
+    if (rows < 0 || cols < 0)
+        return named ? fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols) : fail(FQ_ERR_SHAPE, "negative shape");
+    if (rows == 0 || cols == 0) return ok();  // empty tensor: nothing to do (the reference returns an empty tensor)
+    if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
+    if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+    return CONTINUE;
+}
+
+// The checks every MX entry point makes, in the order they run: the dtype, `first` (the entry point's own: formats, flags), the shape,
+// `pointers` (its own: NULL, aliasing, alignment), the launch's size.  Both callables return 0 or their refusal.  CONTINUE with nvec (the
+// tensor in 16-byte vectors) set, or the entry point's result.  Every check comes before any HIP call.
+template <class First, class Pointers>
+int mx_checks(int dtype, int64_t rows, int64_t cols, bool rot, int64_t& nvec, First&& first, Pointers&& pointers) {
+    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
+    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
+    if (const int rc = first()) return rc;
+    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
+    if (rot && cols % MX_ROT_RUN != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the %d-element rotation run", (long long)cols, MX_ROT_RUN);
+    if (cols % 32 != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the 32-element MX block", (long long)cols);
+    if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
+    if (rows == 0 || cols == 0) return ok();
+    if (const int rc = pointers()) return rc;
+    nvec = rows * cols * esize_of(dtype) / 16;    // cols % 32 == 0: whole 16-byte vectors, whole blocks
+    if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
+    return CONTINUE;
 }
 
 template <bool ASYM>
@@ -73,12 +94,7 @@ int rowwise(const void* x, void* y, int32_t* idx, float* scale, float* bounds, i
             int sem, void* ws, size_t wsb, void* stream, const MaskArgs* mk = nullptr, const fq_rows_view* xv = nullptr,
             const fq_rows_view* yv = nullptr) {
     if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
-    if (bits < 1 || bits > 31) return fail(FQ_ERR_BITS, "num_bits=%d outside [1, 31]", bits);
-    if (sem != FQ_SEM_CPU_EAGER && sem != FQ_SEM_DEVICE_EAGER) return fail(FQ_ERR_ARG, "unknown semantics code %d", sem);
-    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
-    if (rows == 0 || cols == 0) return ok();  // empty tensor: nothing to do (the reference returns an empty tensor)
-    if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
-    if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+    if (const int rc = fwd_head(x, y, rows, cols, bits, sem, true); rc != CONTINUE) return rc;
     if (dtype == FQ_DTYPE_F64) {  // correctness path in double arithmetic; no training-mode side buffers
         if (bounds || mk) return fail(FQ_ERR_DTYPE, "float64 tensors: row bounds / STE mask are not produced (use fq_ste_bwd, the reference's data flow)");
         if ((xv && xv->n_inner > 0) || (yv && yv->n_inner > 0)) return fail(FQ_ERR_UNSUPPORTED, "float64 tensors: contiguous rows only");
@@ -147,14 +163,12 @@ FQ_API size_t fq_ste_mask_bytes(int64_t rows, int64_t cols, int dtype) {
 
 FQ_API int fq_sym_fwd_train(const void* x, void* y, int64_t rows, int64_t cols, int bits, int dtype, int sem, float lo, float hi,
                             float* row_bounds_out, void* mask_out, size_t mask_bytes, void* stream) {
-    MaskArgs mk;
-    mk.mask = mask_out; mk.bytes = mask_bytes; mk.lo = lo; mk.hi = hi;
+    const MaskArgs mk{mask_out, mask_bytes, lo, hi};
     return rowwise<false>(x, y, nullptr, nullptr, row_bounds_out, rows, cols, bits, dtype, sem, nullptr, 0, stream, &mk);
 }
 FQ_API int fq_asym_fwd_train(const void* x, void* y, int64_t rows, int64_t cols, int bits, int dtype, int sem, float lo, float hi,
                              float* row_bounds_out, void* mask_out, size_t mask_bytes, void* stream) {
-    MaskArgs mk;
-    mk.mask = mask_out; mk.bytes = mask_bytes; mk.lo = lo; mk.hi = hi;
+    const MaskArgs mk{mask_out, mask_bytes, lo, hi};
     return rowwise<true>(x, y, nullptr, nullptr, row_bounds_out, rows, cols, bits, dtype, sem, nullptr, 0, stream, &mk);
 }
 
@@ -163,12 +177,7 @@ FQ_API int fq_sym_fwd_autocast(const void* x, void* y, int64_t rows, int64_t col
                                void* stream) {
     if (dtype != FQ_DTYPE_BF16 && dtype != FQ_DTYPE_F16)
         return fail(FQ_ERR_DTYPE, "autocast arithmetic applies to bf16 / fp16 tensors (fp32 tensors are unaffected by autocast)");
-    if (bits < 1 || bits > 31) return fail(FQ_ERR_BITS, "num_bits=%d outside [1, 31]", bits);
-    if (sem != FQ_SEM_CPU_EAGER && sem != FQ_SEM_DEVICE_EAGER) return fail(FQ_ERR_ARG, "unknown semantics code %d", sem);
-    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape");
-    if (rows == 0 || cols == 0) return ok();
-    if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
-    if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+    if (const int rc = fwd_head(x, y, rows, cols, bits, sem, false); rc != CONTINUE) return rc;
     const Consts c = make_consts(bits, dtype, sem);  // under autocast `sem` touches `max + 1e-6` only (everything behind it is fp32)
     RowArgs a{x, y, nullptr, nullptr, row_bounds_out, rows, cols, c.sym, c.asym, nullptr, 0, 0.f, 0.f, 0u, rows, 0, {}};
     if (mask_out) {
@@ -242,8 +251,7 @@ FQ_API int fq_sym_fwd_multi_v(int n, const fq_fwd_tensor_v* tv, int64_t cols, in
 
 FQ_API int fq_rowwise_fwd_v(int asym, const void* x, const fq_rows_view* xv, void* y, const fq_rows_view* yv, int64_t rows, int64_t cols, int bits,
                             int dtype, int sem, float lo, float hi, float* row_bounds_out, void* mask_out, size_t mask_bytes, void* stream) {
-    MaskArgs mk;
-    mk.mask = mask_out; mk.bytes = mask_bytes; mk.lo = lo; mk.hi = hi;
+    const MaskArgs mk{mask_out, mask_bytes, lo, hi};
     const MaskArgs* m = mask_out ? &mk : nullptr;
     return asym ? rowwise<true>(x, y, nullptr, nullptr, row_bounds_out, rows, cols, bits, dtype, sem, nullptr, 0, stream, m, xv, yv)
                 : rowwise<false>(x, y, nullptr, nullptr, row_bounds_out, rows, cols, bits, dtype, sem, nullptr, 0, stream, m, xv, yv);
@@ -449,27 +457,25 @@ const MxFmt kMxFmts[5] = {
 
 // exp = false: fq_mx_fwd (x -> y); true: fq_mx_export (x -> elems + scales).  rot: the *_rot forms (x R is quantized); only_rot:
 // fq_block_rotate (x -> y = x R, no format).  ceil: the scale rule of the *_ex forms; mask (forward only, optional): the saturation
-// bitmap, rows * cols / 8 bytes.  Every check comes before any HIP call.
+// bitmap, rows * cols / 8 bytes.
 int mx_entry(bool exp, const void* x, void* y, void* elems, void* scales, int64_t rows, int64_t cols, int fmt, int dtype, void* stream,
              bool rot = false, bool only_rot = false, bool ceil = false, void* mask = nullptr) {
-    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
-    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
-    if (!only_rot && (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2)) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
-    if (exp && (fmt == FQ_MX_FP6_E2M3 || fmt == FQ_MX_FP6_E3M2)) return fail(FQ_ERR_ARG, "FP6 formats have no export packing");
-    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
-    if (rot && cols % MX_ROT_RUN != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the %d-element rotation run", (long long)cols, MX_ROT_RUN);
-    if (cols % 32 != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the 32-element MX block", (long long)cols);
-    if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
-    if (rows == 0 || cols == 0) return ok();
-    if (!x || (!exp && !y) || (exp && (!elems || !scales))) return fail(FQ_ERR_NULL, exp ? "x / elems / scales must not be NULL" : "x / y must not be NULL");
-    if (!exp && x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
-    if (mask && (mask == x || mask == y)) return fail(FQ_ERR_ARG, "mask_out must not alias x or y");
-    if (!aligned16(x) || (!exp && !aligned16(y)) || (exp && (!aligned16(elems) || !aligned16(scales))) || !aligned16(mask))
-        return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
-    const int es = esize_of(dtype);
-    const int64_t nvec = rows * cols * es / 16;    // cols % 32 == 0: whole 16-byte vectors, whole blocks
-    if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
-    MxArgs a{x, y, (uint8_t*)(mask ? mask : elems), (uint8_t*)scales, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    auto formats = [&] {
+        if (!only_rot && (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2)) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
+        if (exp && (fmt == FQ_MX_FP6_E2M3 || fmt == FQ_MX_FP6_E3M2)) return fail(FQ_ERR_ARG, "FP6 formats have no export packing");
+        return 0;
+    };
+    auto pointers = [&] {
+        if (!x || (!exp && !y) || (exp && (!elems || !scales))) return fail(FQ_ERR_NULL, exp ? "x / elems / scales must not be NULL" : "x / y must not be NULL");
+        if (!exp && x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+        if (mask && (mask == x || mask == y)) return fail(FQ_ERR_ARG, "mask_out must not alias x or y");
+        if (!aligned16(x) || (!exp && !aligned16(y)) || (exp && (!aligned16(elems) || !aligned16(scales))) || !aligned16(mask))
+            return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+        return 0;
+    };
+    int64_t nvec = 0;
+    if (const int rc = mx_checks(dtype, rows, cols, rot, nvec, formats, pointers); rc != CONTINUE) return rc;
+    MxArgs a{x, y, (uint8_t*)(mask ? mask : elems), (uint8_t*)scales, nvec, nvec * 16 >= NT_LOAD_MIN_BYTES ? 1 : 0};
     const int kind = only_rot ? MX_ROT : !exp ? MX_FWD : (fmt == FQ_MX_FP4_E2M1 ? MX_EXP4 : MX_EXP8);
     hipStream_t st = (hipStream_t)stream;
     const MxFmt& f = kMxFmts[only_rot ? 0 : fmt];
@@ -511,25 +517,23 @@ FQ_API int fq_mx_export_ex(const void* x, void* elems_out, void* scales_out, int
                     (flags & FQ_MX_FLAG_CEIL) != 0);
 }
 
-// Every check comes before any HIP call.  gx == g is served without the rotation (every lane stores the vector it loaded).
+// gx == g is served without the rotation (every lane stores the vector it loaded).
 FQ_API int fq_mx_ste_bwd(const void* g, const void* mask, void* gx, int64_t rows, int64_t cols, int dtype, int flags, void* stream) {
-    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
-    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
-    if (flags & ~FQ_MX_FLAG_ROTATE) return fail(FQ_ERR_ARG, "flag bits 0x%x: the backward takes FQ_MX_FLAG_ROTATE only", (unsigned)(flags & ~FQ_MX_FLAG_ROTATE));
     const bool rot = (flags & FQ_MX_FLAG_ROTATE) != 0;
-    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
-    if (rot && cols % MX_ROT_RUN != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the %d-element rotation run", (long long)cols, MX_ROT_RUN);
-    if (cols % 32 != 0) return fail(FQ_ERR_SHAPE, "cols=%lld is not a multiple of the 32-element MX block", (long long)cols);
-    if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
-    if (rows == 0 || cols == 0) return ok();
-    if (!g || !mask || !gx) return fail(FQ_ERR_NULL, "g / mask / gx must not be NULL");
-    if (mask == g || mask == gx) return fail(FQ_ERR_ARG, "mask must not alias g or gx");
-    if (rot && g == gx) return fail(FQ_ERR_ARG, "in-place (gx == g) is not supported with the rotation");
-    if (!aligned16(g) || !aligned16(mask) || !aligned16(gx)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
-    const int es = esize_of(dtype);
-    const int64_t nvec = rows * cols * es / 16;
-    if (nvec / (MX_TPB * MX_VPT) >= 0x7FFFFFFF) return fail(FQ_ERR_UNSUPPORTED, "%lld vectors exceed one launch's grid", (long long)nvec);
-    const MxSteArgs a{g, (const uint32_t*)mask, gx, nvec, rows * cols * es >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    auto flag_bits = [&] {
+        if (flags & ~FQ_MX_FLAG_ROTATE) return fail(FQ_ERR_ARG, "flag bits 0x%x: the backward takes FQ_MX_FLAG_ROTATE only", (unsigned)(flags & ~FQ_MX_FLAG_ROTATE));
+        return 0;
+    };
+    auto pointers = [&] {
+        if (!g || !mask || !gx) return fail(FQ_ERR_NULL, "g / mask / gx must not be NULL");
+        if (mask == g || mask == gx) return fail(FQ_ERR_ARG, "mask must not alias g or gx");
+        if (rot && g == gx) return fail(FQ_ERR_ARG, "in-place (gx == g) is not supported with the rotation");
+        if (!aligned16(g) || !aligned16(mask) || !aligned16(gx)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+        return 0;
+    };
+    int64_t nvec = 0;
+    if (const int rc = mx_checks(dtype, rows, cols, rot, nvec, flag_bits, pointers); rc != CONTINUE) return rc;
+    const MxSteArgs a{g, (const uint32_t*)mask, gx, nvec, nvec * 16 >= NT_LOAD_MIN_BYTES ? 1 : 0};
     hipStream_t st = (hipStream_t)stream;
     return by_dtype(dtype, [&](auto dt) { return launch_mx_ste<decltype(dt)::value>(rot, a, st); });
 }

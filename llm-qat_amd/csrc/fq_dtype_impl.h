@@ -6,8 +6,6 @@
 
 namespace fq {
 
-#define FQ_LAUNCH(kern, grid, block, st, ...) FQ_LAUNCHK(kern, dim3((unsigned)(grid)), dim3(block), 0, st, __VA_ARGS__)
-
 // Which (threads per row, 16-byte vectors per thread) the model widths select (bf16 / fp16: 8 elements per vector):
 //   4096 -> 512 vectors -> 256 x 2     5120 -> 640 -> 256 x 3     11008 -> 1376 -> 512 x 3     13824 -> 1728 -> 512 x 4
 //   tiny-LLaMA (fp32, 4 per vector): 256 -> 64 x 1, 688 -> 64 x 3.      Every other width is served by the nearest shape that holds it.
@@ -19,7 +17,7 @@ namespace fq {
 // the vector slots instead of 10 %, 576 x 3 for 13824, 320 x 2 for 5120 -- and with 256 x 6 for mid-sized tensors: within +-2 % of
 // the shapes below everywhere, profiles/r03_kbench_block_shapes.txt, r03_ab_mid_rows_256.txt) (11008 bf16 cols: 512 thr x 3 = 30.6 us, 256 x 6 = 31.1, 1024 x 2 = 32.2;
 // 4096 cols: 256 x 2 = 6.1 us, 128 x 4 = 6.3, 64 x 8 = 6.9, 512 x 1 = 7.7).
-// The ladder itself is by_reg_shape (fq_launch.h); the plain and the autocast (AC = 1) forward both launch through here.
+// The ladder itself is by_reg_shape (fq_shapes.h); the plain and the autocast (AC = 1) forward both launch through here.
 template <int DT, bool ASYM, bool FAST, bool NTL, int NTS, bool DBG, int AC = 0, bool PITCH = false>
 static void launch_reg(const RowArgs& a, int64_t nvec, hipStream_t st) {
     by_reg_shape(nvec, [&](auto tpr, auto vpt) {
@@ -36,6 +34,30 @@ static void launch_wide(const RowArgs& a, int hpt, hipStream_t st) {
         if (mask) launch_rows<TPR>(row_reg_wide_kernel<DT, TPR, HPT, NTL, NTS, true, PITCH>, a.rows, st, a);
         else if constexpr (!PITCH) launch_rows<TPR>(row_reg_wide_kernel<DT, TPR, HPT, NTL, NTS, false>, a.rows, st, a);
     });
+}
+
+// the scalar-load kernel (any width up to GENERIC_MAX_COLS, any alignment): one wave per row up to 1024 columns, a 256-thread block beyond
+template <int DT, bool ASYM, int AC = 0> static void launch_generic(const RowArgs& a, hipStream_t st) {
+    if (a.cols <= 1024) launch_rows<64>(row_generic_kernel<DT, 64, ASYM, AC>, a.rows, st, a);
+    else launch_rows<256>(row_generic_kernel<DT, 256, ASYM, AC>, a.rows, st, a);
+}
+
+// Very long rows (layerwise): two passes -- the row statistics through atomics into the workspace (vec: in 16-byte vectors), then
+// `apply`, which takes a row in chunks of `ach` elements.  Every refusal comes before the workspace is touched.
+template <int DT, bool ASYM>
+static int two_pass(const RowArgs& a, bool vec, void (*apply)(RowArgs, const uint32_t*, int64_t), int64_t ach, void* ws, size_t wsb, hipStream_t st) {
+    if (any_pitch(a)) return fail(FQ_ERR_UNSUPPORTED, "rows that do not follow one another: not served by the two-pass path");
+    if (!ws || wsb < (size_t)a.rows * 8)
+        return fail(FQ_ERR_WORKSPACE, "two-pass path needs %zu workspace bytes, got %zu", (size_t)a.rows * 8, wsb);
+    const int64_t sch = vec ? tp_chunk_elems<DT, true>() : tp_chunk_elems<DT, false>();
+    const int64_t schunks = (a.cols + sch - 1) / sch, achunks = (a.cols + ach - 1) / ach;
+    if (a.rows * schunks > 0x7FFFFFFF || a.rows * achunks > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "rows*chunks exceeds the grid limit");
+    if (hipMemsetAsync(ws, 0, (size_t)a.rows * 8, st) != hipSuccess) return fail(FQ_ERR_LAUNCH, "hipMemsetAsync failed");
+    uint32_t* w = (uint32_t*)ws;
+    if (vec) launch_grid(stats_kernel<DT, ASYM, true>, a.rows * schunks, 1, TP_THREADS, st, a, w, schunks);
+    else launch_grid(stats_kernel<DT, ASYM, false>, a.rows * schunks, 1, TP_THREADS, st, a, w, schunks);
+    launch_grid(apply, a.rows * achunks, 1, TP_THREADS, st, a, (const uint32_t*)w, achunks);
+    return launch_result();
 }
 
 template <int DT, int AC>
@@ -61,23 +83,23 @@ static int sym_autocast_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
                                  more_aligned(a, 7u, 15u) && pitches_aligned(a, 7, 15);
             if (wide_ok) {
                 const bool ntl = bytes >= NT_LOAD_MIN_BYTES;
-#define W(TPR)                                                                                          \
-    {                                                                                                   \
-        const int hpt = (int)((nh + TPR - 1) / TPR);                                                    \
-        if (pitched) launch_wide<DT, TPR, false, true, true>(a, hpt, st);                               \
-        else if (ntl) launch_wide<DT, TPR, true, true>(a, hpt, st);                                     \
-        else launch_wide<DT, TPR, false, true>(a, hpt, st);                                             \
-    }
-                if (nh <= 512) W(64) else if (nh <= 2048) W(256) else W(1024)
-#undef W
+                auto wide = [&](auto tpr) {
+                    constexpr int TPR = decltype(tpr)::value;
+                    const int hpt = (int)((nh + TPR - 1) / TPR);
+                    if (pitched) launch_wide<DT, TPR, false, true, true>(a, hpt, st);
+                    else if (ntl) launch_wide<DT, TPR, true, true>(a, hpt, st);
+                    else launch_wide<DT, TPR, false, true>(a, hpt, st);
+                };
+                if (nh <= 512) wide(Const<64>{});
+                else if (nh <= 2048) wide(Const<256>{});
+                else wide(Const<1024>{});
                 return launch_result();
             }
             if (pair || a.mask)
                 return fail(FQ_ERR_UNSUPPORTED, "fp32-result forward with STE mask / second tensor: rows must be 8-byte aligned, cols %% 4 == 0, cols <= 32768");
             // other shapes: scalar-load kernel or two passes (bounds only)
             if (a.cols <= GENERIC_MAX_COLS) {
-                if (a.cols <= 1024) launch_rows<64>(row_generic_kernel<DT, 64, false, AC>, a.rows, st, a);
-                else launch_rows<256>(row_generic_kernel<DT, 256, false, AC>, a.rows, st, a);
+                launch_generic<DT, false, AC>(a, st);
                 return launch_result();
             }
         } else {
@@ -93,21 +115,9 @@ static int sym_autocast_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
         } else if (a.mask) {
             return fail(FQ_ERR_UNSUPPORTED, "STE-mask forward needs 16-byte aligned rows that fit the register kernels");
         } else if (a.cols <= GENERIC_MAX_COLS) {
-            if (a.cols <= 1024) launch_rows<64>(row_generic_kernel<DT, 64, false, AC>, a.rows, st, a);
-            else launch_rows<256>(row_generic_kernel<DT, 256, false, AC>, a.rows, st, a);
-        } else {  // very long rows (layerwise): two passes -- |x| max per row through atomics, then apply
-            if (pitched) return fail(FQ_ERR_UNSUPPORTED, "rows that do not follow one another: not served by the two-pass path");
-            if (!ws || wsb < (size_t)a.rows * 8)
-                return fail(FQ_ERR_WORKSPACE, "two-pass path needs %zu workspace bytes, got %zu", (size_t)a.rows * 8, wsb);
-            if (hipMemsetAsync(ws, 0, (size_t)a.rows * 8, st) != hipSuccess) return fail(FQ_ERR_LAUNCH, "hipMemsetAsync failed");
-            uint32_t* w = (uint32_t*)ws;
-            const bool svec = aligned16(a.x) && a.cols % EPV == 0;
-            const int64_t sch = svec ? tp_chunk_elems<DT, true>() : tp_chunk_elems<DT, false>();
-            const int64_t schunks = (a.cols + sch - 1) / sch, ach = (int64_t)TP_THREADS * TP_EPT, achunks = (a.cols + ach - 1) / ach;
-            if (a.rows * schunks > 0x7FFFFFFF || a.rows * achunks > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "rows*chunks exceeds the grid limit");
-            if (svec) FQ_LAUNCH((stats_kernel<DT, false, true>), a.rows * schunks, TP_THREADS, st, a, w, schunks);
-            else FQ_LAUNCH((stats_kernel<DT, false, false>), a.rows * schunks, TP_THREADS, st, a, w, schunks);
-            FQ_LAUNCH((apply_autocast_kernel<DT, AC == 2>), a.rows * achunks, TP_THREADS, st, a, (const uint32_t*)w, achunks);
+            launch_generic<DT, false, AC>(a, st);
+        } else {  // very long rows (layerwise): |x| max per row through atomics, then apply in element loads
+            return two_pass<DT, false>(a, aligned16(a.x) && a.cols % EPV == 0, apply_autocast_kernel<DT, AC == 2>, TP_THREADS * TP_EPT, ws, wsb, st);
         }
         return launch_result();
     }
@@ -130,7 +140,6 @@ static int rowwise_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
     const int64_t bytes = big_rows * a.cols * T::ESIZE;  // cache policy follows the larger tensor
     const bool pitched = any_pitch(a);
     const bool ntl = bytes >= NT_LOAD_MIN_BYTES;
-    bool two_pass = false, two_pass_vec = false;
     if (pair && !(vec_ok && nvec <= REG_MAX_VEC)) return fail(FQ_ERR_UNSUPPORTED, "pair launch: rows must be 16-byte aligned and fit the register kernels");
     if (vec_ok && nvec <= REG_MAX_VEC) {
         if (a.rows > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "rows=%lld exceeds the grid limit", (long long)a.rows);
@@ -145,30 +154,12 @@ static int rowwise_t(RowArgs a, void* ws, size_t wsb, hipStream_t st) {
     } else if (a.mask) {
         return fail(FQ_ERR_UNSUPPORTED, "STE-mask forward needs 16-byte aligned rows that fit the register kernels");
     } else if (vec_ok && !pitched) {
-        two_pass = two_pass_vec = true;
+        return two_pass<DT, ASYM>(a, true, apply_kernel<DT, ASYM, FAST, true>, tp_chunk_elems<DT, true>(), ws, wsb, st);
     } else if (a.cols <= GENERIC_MAX_COLS) {
         if (a.rows > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "rows=%lld exceeds the grid limit", (long long)a.rows);
-        if (a.cols <= 1024) launch_rows<64>(row_generic_kernel<DT, 64, ASYM>, a.rows, st, a);
-        else launch_rows<256>(row_generic_kernel<DT, 256, ASYM>, a.rows, st, a);
+        launch_generic<DT, ASYM>(a, st);
     } else {
-        two_pass = true;
-    }
-    if (two_pass) {
-        if (pitched) return fail(FQ_ERR_UNSUPPORTED, "rows that do not follow one another: not served by the two-pass path");
-        if (!ws || wsb < (size_t)a.rows * 8)
-            return fail(FQ_ERR_WORKSPACE, "two-pass path needs %zu workspace bytes, got %zu", (size_t)a.rows * 8, wsb);
-        const int64_t ch = two_pass_vec ? tp_chunk_elems<DT, true>() : tp_chunk_elems<DT, false>();
-        const int64_t chunks = (a.cols + ch - 1) / ch;
-        if (a.rows * chunks > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "rows*chunks exceeds the grid limit");
-        if (hipMemsetAsync(ws, 0, (size_t)a.rows * 8, st) != hipSuccess) return fail(FQ_ERR_LAUNCH, "hipMemsetAsync failed");
-        uint32_t* w = (uint32_t*)ws;
-        if (two_pass_vec) {
-            FQ_LAUNCH((stats_kernel<DT, ASYM, true>), a.rows * chunks, TP_THREADS, st, a, w, chunks);
-            FQ_LAUNCH((apply_kernel<DT, ASYM, FAST, true>), a.rows * chunks, TP_THREADS, st, a, (const uint32_t*)w, chunks);
-        } else {
-            FQ_LAUNCH((stats_kernel<DT, ASYM, false>), a.rows * chunks, TP_THREADS, st, a, w, chunks);
-            FQ_LAUNCH((apply_kernel<DT, ASYM, FAST, false>), a.rows * chunks, TP_THREADS, st, a, (const uint32_t*)w, chunks);
-        }
+        return two_pass<DT, ASYM>(a, false, apply_kernel<DT, ASYM, FAST, false>, tp_chunk_elems<DT, false>(), ws, wsb, st);
     }
     return launch_result();
 }
@@ -196,13 +187,13 @@ template <int DT> int launch_ste(const void* g, const void* x, void* gx, int64_t
         if (grid > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "n too large");
         const int64_t bytes = n * T::ESIZE;
         if (bytes >= NT_LOAD_MIN_BYTES)
-            FQ_LAUNCH((ste_vec_kernel<DT, 1, true, true>), grid, STE_THREADS, st, (const uint4*)g, (const uint4*)x, (uint4*)gx, nvec, lo, hi);
+            launch_grid(ste_vec_kernel<DT, 1, true, true>, grid, 1, STE_THREADS, st, (const uint4*)g, (const uint4*)x, (uint4*)gx, nvec, lo, hi);
         else
-            FQ_LAUNCH((ste_vec_kernel<DT, 1, false, true>), grid, STE_THREADS, st, (const uint4*)g, (const uint4*)x, (uint4*)gx, nvec, lo, hi);
+            launch_grid(ste_vec_kernel<DT, 1, false, true>, grid, 1, STE_THREADS, st, (const uint4*)g, (const uint4*)x, (uint4*)gx, nvec, lo, hi);
     } else {
         int64_t grid = (n + STE_THREADS - 1) / STE_THREADS;
         if (grid > 8192) grid = 8192;
-        FQ_LAUNCH((ste_scalar_kernel<DT>), grid, STE_THREADS, st, g, x, gx, n, lo, hi);
+        launch_grid(ste_scalar_kernel<DT>, grid, 1, STE_THREADS, st, g, x, gx, n, lo, hi);
     }
     return launch_result();
 }
@@ -229,7 +220,7 @@ int launch_ste_rows(const void* g, const void* x, void* gx, int64_t rows, int64_
     const bool ntl = bytes >= NT_LOAD_MIN_BYTES;
     by_count(vpt, [&](auto n) {
         constexpr int V = decltype(n)::value;
-        auto go = [&](auto kern) { FQ_LAUNCH(kern, rows * chunks, STE_THREADS, st, g, x, gx, nvec_row, chunks, cv, bounds, lo, hi, pitch); };
+        auto go = [&](auto kern) { launch_grid(kern, rows * chunks, 1, STE_THREADS, st, g, x, gx, nvec_row, chunks, cv, bounds, lo, hi, pitch); };
         if (pitched) go(ste_rows_kernel<DT, V, false, true, true>);
         else if (ntl) go(ste_rows_kernel<DT, V, true, true>);
         else go(ste_rows_kernel<DT, V, false, true>);
@@ -253,7 +244,6 @@ inline int64_t ste_layout(SteLaunch& L, bool allow_inplace) {
     }
     return blk;
 }
-#define FQ_LAUNCH2(kern, gx_, gy_, block, st, ...) FQ_LAUNCHK(kern, dim3((unsigned)(gx_), (unsigned)(gy_)), dim3(block), 0, st, __VA_ARGS__)
 
 template <int DT> int launch_ste_mask(SteLaunch L, int64_t cols, float lo, float hi, hipStream_t st) {
     using T = Ty<DT>;
@@ -281,10 +271,10 @@ template <int DT> int launch_ste_mask(SteLaunch L, int64_t cols, float lo, float
     for (int i = 0; i < L.n; ++i) pitched = pitched || L.t[i].gp.on || L.t[i].op.on;
     by_count(vpt, [&](auto n) {
         constexpr int V = decltype(n)::value;
-        auto go = [&](auto kern) { FQ_LAUNCH2(kern, grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi); };
+        auto go = [&](auto kern) { launch_grid(kern, grid, chunks, STE_THREADS, st, L, nvec_row, cv, mrw, lo, hi); };
         if (L.n == 1 && !L.t[0].inplace && !pitched) {   // one copying tensor: its own lean kernel (fq_kernels.h, ste_mask_one_kernel)
             const SteSlot& t0 = L.t[0];
-            auto one = [&](auto kern) { FQ_LAUNCH2(kern, grid, chunks, STE_THREADS, st, t0.g, t0.gx, t0.bounds, t0.mask, nvec_row, cv, mrw, lo, hi); };
+            auto one = [&](auto kern) { launch_grid(kern, grid, chunks, STE_THREADS, st, t0.g, t0.gx, t0.bounds, t0.mask, nvec_row, cv, mrw, lo, hi); };
             if (ntl) one(ste_mask_one_kernel<DT, V, true, true>);
             else one(ste_mask_one_kernel<DT, V, false, true>);
         } else if (L.n <= 2 && !pitched) {
@@ -324,7 +314,7 @@ template <int DT> int launch_ste_mask_wide(SteLaunch L, int64_t cols, float lo, 
         for (int i = 0; i < L.n; ++i) pitched = pitched || L.t[i].gp.on || L.t[i].op.on;
         by_count(hpt, [&](auto n) {
             constexpr int V = decltype(n)::value;
-            auto go = [&](auto kern) { FQ_LAUNCH2(kern, grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi); };
+            auto go = [&](auto kern) { launch_grid(kern, grid, chunks, STE_THREADS, st, L, nh_row, ch, mrw, lo, hi); };
             if (!ntl && !pitched && L.n <= 2) {   // the K / V-sized launches: one or two slots instead of a four-slot pick in every block's prologue
                 if (L.n == 1) go(ste_mask_wide_kernel<DT, V, false, true, false, 1>);
                 else go(ste_mask_wide_kernel<DT, V, false, true, false, 2>);
@@ -347,11 +337,11 @@ int launch_w12(const void* w, const void* scale, void* out, int64_t rows, int64_
     if (!vec && grid > 16384) grid = 16384;
     if (grid > 0x7FFFFFFF) return fail(FQ_ERR_SHAPE, "tensor too large");
     if (w_bits == 1) {
-        if (vec) FQ_LAUNCH((w12_kernel<DT, 1, true>), grid, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
-        else FQ_LAUNCH((w12_kernel<DT, 1, false>), grid, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
+        if (vec) launch_grid(w12_kernel<DT, 1, true>, grid, 1, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
+        else launch_grid(w12_kernel<DT, 1, false>, grid, 1, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
     } else {
-        if (vec) FQ_LAUNCH((w12_kernel<DT, 2, true>), grid, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
-        else FQ_LAUNCH((w12_kernel<DT, 2, false>), grid, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
+        if (vec) launch_grid(w12_kernel<DT, 2, true>, grid, 1, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
+        else launch_grid(w12_kernel<DT, 2, false>, grid, 1, 256, st, w, scale, out, rows, cols, scale_per_row, cv);
     }
     return launch_result();
 }
@@ -374,24 +364,25 @@ int launch_w12_rows(const void* w, void* out, void* scale_out, int64_t rows, int
     const float factor = (float)rows / (float)(rows * cols);   // ATen: static_cast<float>(num_outputs) / numel
     const bool ntl = rows * cols * T::ESIZE >= NT_LOAD_MIN_BYTES;
     const int64_t grid = shared_row ? rows : (rows + 7) / 8;
-#define K(SH, G, WB)                                                                                                              \
-    {                                                                                                                             \
-        if (ntl) FQ_LAUNCH((w12_row_aten_kernel<DT, WB, SH, G, true, true>), grid, 512, st, w, out, scale_out, rows, cols, cv, factor);   \
-        else FQ_LAUNCH((w12_row_aten_kernel<DT, WB, SH, G, false, true>), grid, 512, st, w, out, scale_out, rows, cols, cv, factor);      \
-    }
-#define KW(SH, G)                    \
-    {                                \
-        if (w_bits == 1) K(SH, G, 1) \
-        else K(SH, G, 2)             \
-    }
+    auto go = [&](auto sh, auto g) {   // sh: a row is shared by the 8 waves; g: groups of 4 elements a thread holds
+        constexpr bool SH = decltype(sh)::value;
+        constexpr int G = decltype(g)::value;
+        auto bits = [&](auto wb) {
+            constexpr int WB = decltype(wb)::value;
+            if (ntl) launch_grid(w12_row_aten_kernel<DT, WB, SH, G, true, true>, grid, 1, 512, st, w, out, scale_out, rows, cols, cv, factor);
+            else launch_grid(w12_row_aten_kernel<DT, WB, SH, G, false, true>, grid, 1, 512, st, w, out, scale_out, rows, cols, cv, factor);
+        };
+        if (w_bits == 1) bits(Const<1>{});
+        else bits(Const<2>{});
+    };
     if (shared_row) {
-        if (gpt <= 6) KW(true, 6) else if (gpt <= 8) KW(true, 8) else KW(true, 16)
+        if (gpt <= 6) go(std::true_type{}, Const<6>{});
+        else if (gpt <= 8) go(std::true_type{}, Const<8>{});
+        else go(std::true_type{}, Const<16>{});
     } else {
-        if (gpt <= 16) KW(false, 16)
-        else if constexpr (DT != F32) KW(false, 32)
+        if (gpt <= 16) go(std::false_type{}, Const<16>{});
+        else if constexpr (DT != F32) go(std::false_type{}, Const<32>{});
     }
-#undef KW
-#undef K
     return launch_result();
 }
 

@@ -1,5 +1,7 @@
 // fq_export.hip -- host side of the export / scale pre-pass entry points (include/llmqat_fakequant.h):
-// fq_sym_export, fq_asym_export, fq_sym_row_scales, fq_export_bins_bytes.  No allocation, no synchronisation.
+// fq_sym_export, fq_asym_export, fq_sym_row_scales, fq_export_bins_bytes.  No allocation, no synchronisation.  The launch shape comes
+// from by_reg_shape (fq_shapes.h), the element type from by_dtype and the training-mode outputs from set_mask_args (fq_launch.h), as
+// for the forward.
 #include "../../include/llmqat_fakequant.h"
 
 #include <hip/hip_runtime.h>
@@ -11,25 +13,12 @@ using namespace fq;
 
 namespace {
 
+// launch shapes of the forward kernel (by_reg_shape, as launch_reg of fq_dtype_impl.h takes it): same loads, same reduction
 template <int DT, bool ASYM, bool NTL> void launch_export_reg(const ExportArgs& a, int64_t nvec, hipStream_t st) {
-#define R(TPR, V)                                                                                                              \
-    case V:                                                                                                                    \
-        FQ_LAUNCHK((row_export_kernel<DT, TPR, V, ASYM, NTL>), dim3((unsigned)(TPR == 64 ? (a.rows + 3) / 4 : a.rows)), \
-                           dim3(TPR == 64 ? 256 : TPR), 0, st, a);                                                             \
-        break;
-    // launch shapes of the forward kernel (fq_dtype_impl.h launch_reg): same loads, same reduction
-    if (nvec <= 192) {
-        switch ((int)((nvec + 63) / 64)) { R(64, 1) R(64, 2) R(64, 3) }
-    } else if (nvec <= 384) {
-        switch ((int)((nvec + 127) / 128)) { R(128, 2) R(128, 3) }
-    } else if (nvec <= 768) {
-        switch ((int)((nvec + 255) / 256)) { R(256, 2) R(256, 3) }
-    } else if (nvec <= 4096) {
-        switch ((int)((nvec + 511) / 512)) { R(512, 2) R(512, 3) R(512, 4) case 5: R(512, 6) case 7: R(512, 8) }
-    } else {
-        switch ((int)((nvec + 1023) / 1024)) { case 5: R(1024, 6) case 7: R(1024, 8) }
-    }
-#undef R
+    by_reg_shape(nvec, [&](auto tpr, auto vpt) {
+        constexpr int TPR = decltype(tpr)::value, VPT = decltype(vpt)::value;
+        launch_rows<TPR>(row_export_kernel<DT, TPR, VPT, ASYM, NTL>, a.rows, st, a);
+    });
 }
 
 template <int DT, bool ASYM> int export_t(const ExportArgs& a, hipStream_t st) {
@@ -47,7 +36,7 @@ template <int DT, bool ASYM> int export_t(const ExportArgs& a, hipStream_t st) {
         else launch_export_reg<DT, ASYM, false>(a, nvec, st);
     } else {
         if (a.mask) return fail(FQ_ERR_UNSUPPORTED, "STE mask: rows must be 16-byte aligned and fit the register kernels (see fq_ste_mask_bytes)");
-        FQ_LAUNCHK((row_export_generic_kernel<DT, ASYM>), dim3((unsigned)a.rows), dim3(256), 0, st, a);
+        launch(row_export_generic_kernel<DT, ASYM>, dim3((unsigned)a.rows), dim3(256), st, a);
     }
     return launch_result();
 }
@@ -84,21 +73,10 @@ int export_entry(const void* x, void* bins, float* scales, int32_t* overflow, in
     a.cmax = ASYM ? (float)((1 << cb) - 1) : (float)((1 << (cb - 1)) - 1);
     if (mask) {
         if (!bounds) return fail(FQ_ERR_NULL, "a mask needs row_bounds_out too");
-        const int64_t mrw = mask_row_words(cols, esize_of(dtype));
-        if (!mrw) return fail(FQ_ERR_UNSUPPORTED, "shape not served by the STE-mask path (see fq_ste_mask_bytes)");
-        if (mask_bytes < (size_t)rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)rows * mrw * 8);
-        a.mask = (uint64_t*)mask;
-        a.mask_row_words = mrw;
-        a.lo = host_rb(lo, dtype);
-        a.hi = host_rb(hi, dtype);
-        a.clipk = ste_clip_key(a.lo, a.hi, dtype);
+        if (const int rc = set_mask_args(a, mask, mask_bytes, lo, hi, dtype)) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case FQ_DTYPE_F32: return export_t<F32, ASYM>(a, st);
-        case FQ_DTYPE_F16: return export_t<F16, ASYM>(a, st);
-        default: return export_t<BF16, ASYM>(a, st);
-    }
+    return by_dtype(dtype, [&](auto dt) { return export_t<decltype(dt)::value, ASYM>(a, st); });
 }
 
 }  // namespace

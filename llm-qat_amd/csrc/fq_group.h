@@ -186,21 +186,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void group_reg_kernel(RowArg
     }
 }
 
-// Launch shapes: the (threads per row, vectors per thread) of by_reg_shape for the model widths (bf16 4096 -> 256 x 2, 5120 -> 256 x 3,
-// 11008 -> 512 x 3, 13824 -> 512 x 4), fewer in between and a ladder of its own: every rung must hold whole groups (TPR * VPT a
-// multiple of 64 vectors, nvec <= TPR * VPT), which 64 x 3, 128 x 3, 512 x 6 and 1024 x 6 do not for gv = 64.
-template <class F> inline void by_group_shape(int64_t nvec, F&& f) {
-    if (nvec <= 64) f(Const<64>{}, Const<1>{});
-    else if (nvec <= 128) f(Const<64>{}, Const<2>{});
-    else if (nvec <= 256) f(Const<128>{}, Const<2>{});
-    else if (nvec <= 512) f(Const<256>{}, Const<2>{});
-    else if (nvec <= 768) f(Const<256>{}, Const<3>{});
-    else if (nvec <= 1024) f(Const<512>{}, Const<2>{});
-    else if (nvec <= 1536) f(Const<512>{}, Const<3>{});
-    else if (nvec <= 2048) f(Const<512>{}, Const<4>{});
-    else if (nvec <= 4096) f(Const<1024>{}, Const<4>{});
-    else f(Const<1024>{}, Const<8>{});
-}
+// launch shapes: by_group_shape (fq_shapes.h), a ladder of its own because every rung must hold whole groups
 template <int DT, bool ASYM, bool FAST, int AC>
 static void launch_group_shape(const RowArgs& a, int64_t nvec, GroupArgs ga, hipStream_t st) {
     by_group_shape(nvec, [&](auto tpr, auto vpt) {

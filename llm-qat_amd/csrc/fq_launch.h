@@ -13,6 +13,7 @@
 
 #include "../../include/llmqat_fakequant.h"
 #include "fq_kernels.h"
+#include "fq_shapes.h"
 
 namespace fq {
 
@@ -45,11 +46,11 @@ inline int launch_result() {
     const hipError_t e = launch_status();
     return e == hipSuccess ? ok() : fail(FQ_ERR_LAUNCH, "kernel launch failed: %s", hipGetErrorString(e));
 }
-// (drop-in for the hipLaunchKernelGGL call shape; the kernels use no dynamic LDS)
-#define FQ_LAUNCHK(kern, grid, block, shmem, st, ...) ::fq::launch(kern, grid, block, st, __VA_ARGS__)
+// the same with the grid given as block counts (64-bit host arithmetic, checked against the grid limit by the caller)
+template <typename... P, typename... A> inline void launch_grid(void (*kernel)(P...), int64_t gx, int64_t gy, int block, hipStream_t st, A&&... a) {
+    launch(kernel, dim3((unsigned)gx, (unsigned)gy), dim3(block), st, std::forward<A>(a)...);
+}
 
-// ---- run-time choices -> template arguments: the callable receives std::integral_constant values and reads them as constants ----
-template <int V> using Const = std::integral_constant<int, V>;
 // element type of the three per-dtype translation units (dtype: a validated FQ_DTYPE_* code other than F64)
 template <class F> inline int by_dtype(int dtype, F&& f) {
     switch (dtype) {
@@ -57,39 +58,6 @@ template <class F> inline int by_dtype(int dtype, F&& f) {
         case FQ_DTYPE_F16: return f(Const<F16>{});
         default: return f(Const<BF16>{});
     }
-}
-// a count of 16-byte vectors (or 8-byte half-vectors) per thread, 1 .. 8, as the backward kernels and the fp32-result forward take it
-template <class F> inline void by_count(int n, F&& f) {
-    switch (n) {
-        case 1: f(Const<1>{}); break;
-        case 2: f(Const<2>{}); break;
-        case 3: f(Const<3>{}); break;
-        case 4: f(Const<4>{}); break;
-        case 5: f(Const<5>{}); break;
-        case 6: f(Const<6>{}); break;
-        case 7: f(Const<7>{}); break;
-        case 8: f(Const<8>{}); break;
-        default: break;
-    }
-}
-// Launch shape of the register-resident row kernels for a row of nvec 16-byte vectors (nvec <= REG_MAX_VEC): f(threads per row,
-// vectors per thread), the smallest rung that holds the row.  5 and 7 vectors per thread run as 6 and 8 (no model width lands there;
-// why these rungs: the comment above launch_reg in fq_dtype_impl.h).
-template <class F> inline void by_reg_shape(int64_t nvec, F&& f) {
-    if (nvec <= 64) f(Const<64>{}, Const<1>{});
-    else if (nvec <= 128) f(Const<64>{}, Const<2>{});
-    else if (nvec <= 192) f(Const<64>{}, Const<3>{});
-    else if (nvec <= 256) f(Const<128>{}, Const<2>{});
-    else if (nvec <= 384) f(Const<128>{}, Const<3>{});
-    else if (nvec <= 512) f(Const<256>{}, Const<2>{});
-    else if (nvec <= 768) f(Const<256>{}, Const<3>{});
-    else if (nvec <= 1024) f(Const<512>{}, Const<2>{});
-    else if (nvec <= 1536) f(Const<512>{}, Const<3>{});
-    else if (nvec <= 2048) f(Const<512>{}, Const<4>{});
-    else if (nvec <= 3072) f(Const<512>{}, Const<6>{});
-    else if (nvec <= 4096) f(Const<512>{}, Const<8>{});
-    else if (nvec <= 6144) f(Const<1024>{}, Const<6>{});
-    else f(Const<1024>{}, Const<8>{});
 }
 // one launch of a row kernel over `rows` rows: TPR == 64 puts four rows into a 256-thread block (fq_kernels.h row_and_lane)
 template <int TPR, typename... P, typename... A> inline void launch_rows(void (*kernel)(P...), int64_t rows, hipStream_t st, A&&... a) {
@@ -165,7 +133,6 @@ inline int64_t nt_load_min_bytes() {
 }
 #define NT_LOAD_MIN_BYTES (::fq::nt_load_min_bytes())
 
-constexpr int64_t REG_MAX_VEC = 1024 * 8;    // longest row (in 16-byte vectors) the register kernels hold
 constexpr int64_t GENERIC_MAX_COLS = 32768;  // longest row the scalar-load kernel sweeps
 constexpr int64_t WS_COLS_THRESHOLD = 32768; // rows longer than this may take the two-pass path
 
@@ -313,6 +280,19 @@ inline uint32_t ste_clip_key(float lo, float hi, int dtype) {
     const uint32_t t = dtype == FQ_DTYPE_BF16 ? (f2u(hi) >> 16) & 0x7FFFu : half_bits(hi) & 0x7FFFu;  // <= 0x7F80 / 0x7C00 (+inf)
     const uint32_t k = 0x8000u - t;
     return k | (k << 16);
+}
+// the training-mode outputs of a forward or an export (Args: RowArgs / ExportArgs, rows and cols set): the bitmap's place and size, the
+// clip rounded to the dtype and its integer form
+template <class Args> inline int set_mask_args(Args& a, void* mask, size_t bytes, float lo, float hi, int dtype) {
+    const int64_t mrw = mask_row_words(a.cols, esize_of(dtype));
+    if (!mrw) return fail(FQ_ERR_UNSUPPORTED, "shape not served by the STE-mask path (see fq_ste_mask_bytes)");
+    if (bytes < (size_t)a.rows * mrw * 8) return fail(FQ_ERR_WORKSPACE, "mask buffer too small: need %zu bytes", (size_t)a.rows * mrw * 8);
+    a.mask = (uint64_t*)mask;
+    a.mask_row_words = mrw;
+    a.lo = host_rb(lo, dtype);
+    a.hi = host_rb(hi, dtype);
+    a.clipk = ste_clip_key(a.lo, a.hi, dtype);
+    return FQ_OK;
 }
 template <int DT>
 FQ_HIDDEN int launch_ste_rows(const void* g, const void* x, void* gx, int64_t rows, int64_t cols, float lo, float hi,

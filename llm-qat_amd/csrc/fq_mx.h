@@ -326,7 +326,7 @@ __global__ __launch_bounds__(MX_TPB) void mx_ste_kernel(MxSteArgs a) {
 template <int DT, int KIND, bool ROT = false, bool MASK = false, bool CEIL = false>
 static void launch_mx_kind(const MxArgs& a, const MxFmt& f, hipStream_t st) {
     const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
-    FQ_LAUNCHK((mx_kernel<DT, KIND, MX_VPT, ROT, MASK, CEIL>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a, f);
+    launch(mx_kernel<DT, KIND, MX_VPT, ROT, MASK, CEIL>, dim3((unsigned)grid), dim3(MX_TPB), st, a, f);
 }
 template <int DT, bool ROT, bool CEIL> static void launch_mx_rule(int kind, bool mask, const MxArgs& a, const MxFmt& f, hipStream_t st) {
     if (kind == MX_FWD && mask) launch_mx_kind<DT, MX_FWD, ROT, true, CEIL>(a, f, st);
@@ -350,8 +350,8 @@ template <int DT> int launch_mx(int kind, bool rot, bool ceil, bool mask, MxArgs
 template <int DT> int launch_mx_ste(bool rot, MxSteArgs a, hipStream_t st) {
     begin_launches();
     const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
-    if (rot) FQ_LAUNCHK((mx_ste_kernel<DT, MX_VPT, true>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a);
-    else FQ_LAUNCHK((mx_ste_kernel<DT, MX_VPT, false>), dim3((unsigned)grid), dim3(MX_TPB), 0, st, a);
+    if (rot) launch(mx_ste_kernel<DT, MX_VPT, true>, dim3((unsigned)grid), dim3(MX_TPB), st, a);
+    else launch(mx_ste_kernel<DT, MX_VPT, false>, dim3((unsigned)grid), dim3(MX_TPB), st, a);
     return launch_result();
 }
 

@@ -213,11 +213,11 @@ constexpr int mxg_code(int fmt) { return fmt == 0 ? 4 : fmt == 3 ? 0 : 1; }
 template <int FW, int FA> static void launch_mx_gemm_pair(const MxGemmArgs& g, hipStream_t st) {
     if (g.M <= MXG_SKINNY_M) {
         const dim3 grid((unsigned)((g.N + 15) / 16));
-        if (g.M <= 16) FQ_LAUNCHK((mx_gemm_skinny<FW, FA, 1>), grid, dim3(64 * MXG_SKINNY_WAVES), 0, st, g);
-        else FQ_LAUNCHK((mx_gemm_skinny<FW, FA, 2>), grid, dim3(64 * MXG_SKINNY_WAVES), 0, st, g);
+        if (g.M <= 16) launch(mx_gemm_skinny<FW, FA, 1>, grid, dim3(64 * MXG_SKINNY_WAVES), st, g);
+        else launch(mx_gemm_skinny<FW, FA, 2>, grid, dim3(64 * MXG_SKINNY_WAVES), st, g);
     } else {
         const dim3 grid((unsigned)((g.M + MXG_TILE - 1) / MXG_TILE), (unsigned)((g.N + MXG_TILE - 1) / MXG_TILE));
-        FQ_LAUNCHK((mx_gemm_tiled<FW, FA>), grid, dim3(256), 0, st, g);
+        launch(mx_gemm_tiled<FW, FA>, grid, dim3(256), st, g);
     }
 }
 

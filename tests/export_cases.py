@@ -3,9 +3,9 @@ sensitive against deliberately wrong roundings, clamps, counts and packings) and
 fq_sym_export / fq_asym_export / fq_sym_row_scales on them).  numpy and torch-CPU only, no product code; the CPU oracle supplies the scales.
 
 A row of `cols` elements is nvec = cols / EPV 16-byte vectors.  launch_export_reg (llm-qat_amd/csrc/fq_export.hip) picks a (threads per row,
-vector slots per thread) instantiation of row_export_kernel from nvec with a ladder of its own; a row that needs 5 (7) slots runs the 6 (8)
-slot instantiation, so every thread's last slot re-loads the row's last vector, and so does every slot at or beyond nvec in any other row.
-The ladder as the code has it counts EIGHTEEN rungs (64 x {1, 2, 3}, 128 x {2, 3}, 256 x {2, 3}, 512 x {2, 3, 4, 5, 6, 7, 8} and
+vector slots per thread) instantiation of row_export_kernel from nvec with by_reg_shape (llm-qat_amd/csrc/fq_shapes.h), the ladder of the
+forward kernels; a row that needs 5 (7) slots runs the 6 (8) slot instantiation, so every thread's last slot re-loads the row's last vector, and so does every slot at or beyond nvec in any other row.
+Counted by the slots a row needs, the ladder has EIGHTEEN rungs (64 x {1, 2, 3}, 128 x {2, 3}, 256 x {2, 3}, 512 x {2, 3, 4, 5, 6, 7, 8} and
 1024 x {5, 6, 7, 8}); all of them are listed here.
 
 What fp16 cannot hold (and what the case builder gives it instead; the CPU tier asserts both):
@@ -27,9 +27,10 @@ import torch
 
 from group_cases import EPV, NAN, PINF, SIGN, MAXFIN, clip_predicate, differs, oracle_view, row_bounds, uint_of  # noqa: F401
 
-# ---- the ladder: mirrors launch_export_reg (llm-qat_amd/csrc/fq_export.hip) -- lo < nvec <= hi runs row_export_kernel<TPR, slots>; vpt is the
-# number of slots the row needs, slots the instantiation that runs (case 5 falls through to R(.., 6), case 7 to R(.., 8)) -----------------------
-REG_MAX_VEC = 8192          # fq_launch.h: wider rows take row_export_generic_kernel
+# ---- the ladder: mirrors by_reg_shape (llm-qat_amd/csrc/fq_shapes.h; tests/test_shape_tables_cpu.py compares the two for every nvec) --
+# lo < nvec <= hi runs row_export_kernel<TPR, slots>; vpt is the number of slots the row needs, slots the instantiation that runs (5 runs
+# as 6, 7 as 8) ----------------------------------------------------------------------------------------------------------------------------
+REG_MAX_VEC = 8192          # fq_shapes.h: wider rows take row_export_generic_kernel
 Rung = namedtuple("Rung", "lo hi tpr vpt slots")
 RUNGS = [Rung(0, 64, 64, 1, 1), Rung(64, 128, 64, 2, 2), Rung(128, 192, 64, 3, 3),
          Rung(192, 256, 128, 2, 2), Rung(256, 384, 128, 3, 3),

@@ -13,7 +13,7 @@ from mx_reference import decode, encode
 
 EPV = {"bf16": 8, "fp16": 8, "fp32": 4}
 GVS = (4, 8, 16, 32, 64)          # vectors per group the validation of fq_group_fwd accepts
-# mirrors launch_group_shape (llm-qat_amd/csrc/fq_group.h): lo < nvec <= hi runs group_reg_kernel<TPR, VPT>
+# mirrors by_group_shape (llm-qat_amd/csrc/fq_shapes.h; tests/test_shape_tables_cpu.py compares the two): lo < nvec <= hi runs group_reg_kernel<TPR, VPT>
 Bracket = namedtuple("Bracket", "lo hi tpr vpt")
 BRACKETS = [Bracket(0, 64, 64, 1), Bracket(64, 128, 64, 2), Bracket(128, 256, 128, 2), Bracket(256, 512, 256, 2), Bracket(512, 768, 256, 3),
             Bracket(768, 1024, 512, 2), Bracket(1024, 1536, 512, 3), Bracket(1536, 2048, 512, 4), Bracket(2048, 4096, 1024, 4),

@@ -1,5 +1,5 @@
 """CPU tier of the export kernels' launch-shape tests: the ladder, the shapes and the inputs of tests/export_cases.py are worth running.
-Structure (every rung of launch_export_reg with its two widths, rows of every mode in one launch, edge bins, fractions either side of
+Structure (every rung of by_reg_shape, which launch_export_reg follows, with its two widths, rows of every mode in one launch, edge bins, fractions either side of
 cmax + 0.5, exact ties, the int4 packer's nibble pairs, what fp16 cannot hold), the restatement pre_round -> round -> clamp -> pack -> count
 against the oracle on every case, and SEEDED FAULTS in that restatement: each must change a compared output (packed bytes or overflow
 counts) on EVERY case that holds what the fault touches, and the set of such cases is non-empty per dtype and per kernel body.  No kernel
@@ -97,16 +97,13 @@ def reachable(k, r, b, key=None):
 # ---- the ladder and the case list ----------------------------------------------------------------------------------------------------------
 
 def test_the_ladder_restates_launch_export_reg():
+    """launch_export_reg takes its launch shape from by_reg_shape (fq_shapes.h) and from nowhere else; that RUNGS says what by_reg_shape
+    says, for every nvec, is asserted against the compiled header in tests/test_shape_tables_cpu.py"""
     src = open(os.path.join(ROOT, "llm-qat_amd", "csrc", "fq_export.hip")).read()
-    body = src[src.index("void launch_export_reg"):src.index("#undef R")]
+    body = src[src.index("void launch_export_reg"):src.index("int export_t(")]
     flat = re.sub(r"\s+", " ", body)
-    want = ["if (nvec <= 192) { switch ((int)((nvec + 63) / 64)) { R(64, 1) R(64, 2) R(64, 3) }",
-            "else if (nvec <= 384) { switch ((int)((nvec + 127) / 128)) { R(128, 2) R(128, 3) }",
-            "else if (nvec <= 768) { switch ((int)((nvec + 255) / 256)) { R(256, 2) R(256, 3) }",
-            "else if (nvec <= 4096) { switch ((int)((nvec + 511) / 512)) { R(512, 2) R(512, 3) R(512, 4) case 5: R(512, 6) case 7: R(512, 8) }",
-            "else { switch ((int)((nvec + 1023) / 1024)) { case 5: R(1024, 6) case 7: R(1024, 8) }"]
-    for w in want:
-        assert w in flat, w
+    assert "by_reg_shape(nvec, [&](auto tpr, auto vpt) {" in flat and "launch_rows<TPR>(row_export_kernel<DT, TPR, VPT, ASYM, NTL>, a.rows, st, a);" in flat
+    assert "switch" not in body and "#define" not in body and src.count("row_export_kernel<") == 1
     assert len(RUNGS) == 18 and RUNGS[0].lo == 0 and RUNGS[-1].hi == E.REG_MAX_VEC == 8192
     for a, b in zip(RUNGS, RUNGS[1:]):
         assert a.hi == b.lo

@@ -3,8 +3,8 @@ tests/test_export_cases_cpu.py proves that these inputs expose a wrong rounding,
 byte, every scale as bits, every overflow count against the CPU oracle (`export_cases.expected`), under cpu_eager.  The one relaxation is the
 one tests/test_gpu_export.py has: Asym beta may differ in the sign of zero.
 
-The cross: 2808 launches over the 18 rungs of launch_export_reg (bf16 1188, fp16 900, fp32 720), plus a device_eager slice; dequantisation
-of the clean rows; the generic kernel on the same adversarial rows (odd widths, rows beyond the register kernels, element-aligned
+The cross: 2808 launches over the 18 rungs of by_reg_shape (fq_shapes.h), which launch_export_reg follows (bf16 1188, fp16 900,
+fp32 720), plus a device_eager slice; dequantisation of the clean rows; the generic kernel on the same adversarial rows (odd widths, rows beyond the register kernels, element-aligned
 storage); the scale pre-pass with bounds and bitmap through the C ABI; canaries around bins, scales and overflow; the non-temporal load
 instantiation in a child interpreter.  Nothing is skipped: a combination a dtype cannot hold is absent from export_cases.COMBOS."""
 import json

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 ROWS = 5
 LO, HI = -2.0, 2.0
 BITS = 4
-# threads per row -> the nvec at the top of each of its rungs (fq_launch.h by_reg_shape)
+# threads per row -> the nvec at the top of each of its rungs (fq_shapes.h by_reg_shape)
 RUNGS = {64: (64, 128, 192), 128: (256, 384), 256: (512, 768), 512: (1024, 1536, 2048, 2560, 3072, 3584, 4096), 1024: (5120, 6144, 7168, 8192)}
 NVECS = [n for tpr in RUNGS for n in RUNGS[tpr]]
 # fp32-result forward (launch_wide): nh = cols / 4 half-vectors per row, hpt = ceil(nh / TPR) of them per thread; TPR 64 up to nh = 512,

@@ -272,10 +272,10 @@ __global__ __launch_bounds__(QL_THREADS, 2) void qlinear_kernel(QLArgs a) {
 template <int QA, int QW> int launch_ql(const QLArgs& a, int ablation, hipStream_t st) {
     const dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(QL_THREADS);
     const bool dump = a.dump_x || a.dump_w;
-    if (ablation == 1) FQ_LAUNCHK((qlinear_kernel<QA, QW, false, 1>), grid, block, 0, st, a);
-    else if (ablation == 2) FQ_LAUNCHK((qlinear_kernel<QA, QW, false, 2>), grid, block, 0, st, a);
-    else if (dump) FQ_LAUNCHK((qlinear_kernel<QA, QW, true, 0>), grid, block, 0, st, a);
-    else FQ_LAUNCHK((qlinear_kernel<QA, QW, false, 0>), grid, block, 0, st, a);
+    if (ablation == 1) launch(qlinear_kernel<QA, QW, false, 1>, grid, block, st, a);
+    else if (ablation == 2) launch(qlinear_kernel<QA, QW, false, 2>, grid, block, st, a);
+    else if (dump) launch(qlinear_kernel<QA, QW, true, 0>, grid, block, st, a);
+    else launch(qlinear_kernel<QA, QW, false, 0>, grid, block, st, a);
     return launch_result();
 }
 

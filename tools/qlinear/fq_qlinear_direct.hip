@@ -365,14 +365,14 @@ template <int SH, int BK, int QW, int ABL, int CP = 0> __global__ __launch_bound
 
 template <int SH, int BK, int QW> int launch_dq(const DQArgs& a, int ablation, hipStream_t st) {
     const dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(DQ_THREADS);
-    if (ablation == 1) FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 1>), grid, block, 0, st, a);
-    else if (ablation == 2) FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 2>), grid, block, 0, st, a);
-    else if (ablation == 3) FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 3>), grid, block, 0, st, a);
-    else if (ablation == 10) FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 0, 1>), grid, block, 0, st, a);   // W loads `nt`
-    else if (ablation == 20) FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 0, 2>), grid, block, 0, st, a);   // W loads `sc1`
-    else if (ablation == 11) FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 1, 1>), grid, block, 0, st, a);   // no MFMA, W loads `nt`
-    else if (ablation == 21) FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 1, 2>), grid, block, 0, st, a);   // no MFMA, W loads `sc1`
-    else FQ_LAUNCHK((qdirect_kernel<SH, BK, QW, 0>), grid, block, 0, st, a);
+    if (ablation == 1) launch(qdirect_kernel<SH, BK, QW, 1>, grid, block, st, a);
+    else if (ablation == 2) launch(qdirect_kernel<SH, BK, QW, 2>, grid, block, st, a);
+    else if (ablation == 3) launch(qdirect_kernel<SH, BK, QW, 3>, grid, block, st, a);
+    else if (ablation == 10) launch(qdirect_kernel<SH, BK, QW, 0, 1>, grid, block, st, a);   // W loads `nt`
+    else if (ablation == 20) launch(qdirect_kernel<SH, BK, QW, 0, 2>, grid, block, st, a);   // W loads `sc1`
+    else if (ablation == 11) launch(qdirect_kernel<SH, BK, QW, 1, 1>, grid, block, st, a);   // no MFMA, W loads `nt`
+    else if (ablation == 21) launch(qdirect_kernel<SH, BK, QW, 1, 2>, grid, block, st, a);   // no MFMA, W loads `sc1`
+    else launch(qdirect_kernel<SH, BK, QW, 0>, grid, block, st, a);
     return launch_result();
 }
 

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 SRC = os.path.join(HERE, "fq_qlinear.hip")
 SRC_DIRECT = os.path.join(HERE, "fq_qlinear_direct.hip")   # round 5: W direct-to-VGPR as the MFMA operand, x by LDS-DMA
 LIB = os.path.join(HERE, "libfq_qlinear_exp.so")
-_DEPS = [SRC, SRC_DIRECT] + [os.path.join(ROOT, "llm-qat_amd", "csrc", f) for f in ("fq_device.h", "fq_kernels.h", "fq_launch.h")] + [
+_DEPS = [SRC, SRC_DIRECT] + [os.path.join(ROOT, "llm-qat_amd", "csrc", f) for f in ("fq_device.h", "fq_kernels.h", "fq_launch.h", "fq_shapes.h")] + [
     os.path.join(ROOT, "include", "llmqat_fakequant.h")]
 _lib = None
 
