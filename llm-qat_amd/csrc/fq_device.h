@@ -46,6 +46,24 @@ template <bool NT> __device__ __forceinline__ void st16(uint4* p, uint4 v) {
         *p = v;
     }
 }
+// 8-byte forms: the half-vectors of the fp32-result kernels (4 16-bit elements per lane), ATen's groups of 4 in the 1-/2-bit weight kernel
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+template <bool NT> __device__ __forceinline__ uint2 ld8(const uint2* p) {
+    if constexpr (NT) {
+        u32x2_t v = __builtin_nontemporal_load((const u32x2_t*)p);
+        return make_uint2(v.x, v.y);
+    } else {
+        return *p;
+    }
+}
+template <bool NT> __device__ __forceinline__ void st8(uint2* p, uint2 v) {
+    if constexpr (NT) {
+        u32x2_t w = {v.x, v.y};
+        __builtin_nontemporal_store(w, (u32x2_t*)p);
+    } else {
+        *p = v;
+    }
+}
 // Store cache policy of an output stream (the NTS template flag of the row kernels; `false` / `true` are ST_PLAIN / ST_NT).
 // The sc1 flavours are 16-byte buffer stores with the policy in the instruction's cache-policy operand:
 //   sc1 writes through the XCD's L2 (the line is not left dirty there); nt keeps it.  A/B: tools/kbench.hip `policy`.
@@ -146,14 +164,22 @@ template <> struct Ty<F16> {
     }
 };
 
-// A load loop of the streaming kernels: the lane holds vectors first, first + STRIDE, ... of the `nvec` vectors at p.  A slot past the
-// end re-loads the last vector, so no load sits behind a branch; only stores are predicated.  NT is a template flag so that a kernel
-// whose policy is a run-time (block-uniform) choice calls this from both arms of its branch.
-template <bool NT, int N, int STRIDE> __device__ __forceinline__ void load_clamped(uint4 (&r)[N], const uint4* p, int64_t first, int64_t nvec) {
+// The load loop of the streaming kernels: the lane holds vectors first, first + STRIDE, ... of the `nvec` vectors at p.  A slot past the
+// end re-loads the last vector (idempotent for max / min), so no load sits behind a branch; only stores are predicated.  NT is a template
+// flag so that a kernel whose policy is a run-time (block-uniform) choice calls this from both arms of its branch.  I is the index type
+// of the call site: int where a row or chunk is known to be short, int64_t for a whole tensor.  uint2: the 8-byte half-vectors.
+template <bool NT, int N, int STRIDE, class I> __device__ __forceinline__ void load_clamped(uint4 (&r)[N], const uint4* p, I first, I nvec) {
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        const int64_t v = first + i * STRIDE;
+        const I v = first + i * STRIDE;
         r[i] = ld16<NT>(&p[v < nvec ? v : nvec - 1]);
+    }
+}
+template <bool NT, int N, int STRIDE, class I> __device__ __forceinline__ void load_clamped(uint2 (&r)[N], const uint2* p, I first, I nvec) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const I v = first + i * STRIDE;
+        r[i] = ld8<NT>(&p[v < nvec ? v : nvec - 1]);
     }
 }
 
@@ -626,6 +652,114 @@ template <int DT> __device__ __forceinline__ uint32_t ste_dword(uint32_t g, uint
         if (!(f[1] >= hi || f[1] <= lo)) keep |= 0xFFFF0000u;
         return g & keep;
     }
+}
+
+template <int DT> __device__ __forceinline__ uint4 ste_vec(const uint4& g, const uint4& x, float lo, float hi) {   // a whole 16-byte vector
+    return make_uint4(ste_dword<DT>(g.x, x.x, lo, hi), ste_dword<DT>(g.y, x.y, lo, hi), ste_dword<DT>(g.z, x.z, lo, hi), ste_dword<DT>(g.w, x.w, lo, hi));
+}
+
+// ------------------------------------------------------------------------------------
+// Row statistics: what a quantizer reduces a row (or a chunk of one) to, from the vectors a lane holds in registers or by an element
+// sweep; the `lane_` forms stop before the cross-lane reduction (the two-pass kernel merges chunks with atomics behind it).
+// ------------------------------------------------------------------------------------
+// Sym: max|x| on the raw bits -> its fp32 bits
+template <int DT, int N> __device__ __forceinline__ uint32_t lane_absmax(const uint4 (&r)[N]) {
+    using T = Ty<DT>;
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        acc = T::absmax_acc(acc, r[i].x);
+        acc = T::absmax_acc(acc, r[i].y);
+        acc = T::absmax_acc(acc, r[i].z);
+        acc = T::absmax_acc(acc, r[i].w);
+    }
+    return T::absmax_finish(acc);
+}
+template <int DT, int N> __device__ __forceinline__ uint32_t lane_absmax(const uint2 (&r)[N]) {   // half-vectors
+    using T = Ty<DT>;
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc = T::absmax_acc(T::absmax_acc(acc, r[i].x), r[i].y);
+    return T::absmax_finish(acc);
+}
+template <int DT, int NW, class V, int N> __device__ __forceinline__ float row_absmax(const V (&r)[N], uint32_t* lds /*[NW]*/) {
+    return as_f(block_reduce<OpMaxU, NW>(lane_absmax<DT>(r), lds));
+}
+// Asym: min and max as fp32 with the packed |x| max next to them (v_max_f32 / v_min_f32 ignore NaN operands: absacc detects it)
+template <int DT, int N> __device__ __forceinline__ MinMax lane_minmax(const uint4 (&r)[N]) {
+    using T = Ty<DT>;
+    MinMax mm;
+    float f0[T::EPD];
+    T::unpack(r[0].x, f0);
+    mm.mx = mm.mn = f0[0];
+    mm.absacc = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        minmax_acc<DT>(mm, r[i].x);
+        minmax_acc<DT>(mm, r[i].y);
+        minmax_acc<DT>(mm, r[i].z);
+        minmax_acc<DT>(mm, r[i].w);
+    }
+    return mm;
+}
+// ... reduced over the row: 16-bit tensors on the order-preserving keys (one reduction), fp32 through lane_minmax (three behind one
+// barrier).  Both NaN if the row holds a NaN: torch.max / torch.min propagate it.  lds is [3][NW].
+template <int DT, int NW, int N> __device__ __forceinline__ void row_minmax(const uint4 (&r)[N], uint32_t (*lds)[NW > 1 ? NW : 1], float& mx, float& mn) {
+    using T = Ty<DT>;
+    if constexpr (T::ESIZE == 2) {
+        MinMaxKeys mk;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            mk.acc(r[i].x);
+            mk.acc(r[i].y);
+            mk.acc(r[i].z);
+            mk.acc(r[i].w);
+        }
+        minmax_from_keys<DT>(block_reduce<OpPkMaxU16, NW>(mk.word(), lds[0]), mx, mn);
+    } else {
+        const MinMax mm = lane_minmax<DT>(r);
+        uint32_t nb = T::absmax_finish(mm.absacc), umx = as_u(mm.mx), umn = as_u(mm.mn);
+        block_reduce3<OpMaxU, OpMaxF, OpMinF, NW>(nb, umx, umn, lds);
+        mx = as_f(umx), mn = as_f(umn);
+        if (absbits_is_nan(nb)) mx = mn = as_f(0x7FC00000u);
+    }
+}
+// The element sweeps of the kernels that take any width / alignment: elements base + c for c = c0, c0 + stride, ... < cend.
+// -> fp32 bits of the lane's max|x|
+template <int DT> __device__ __forceinline__ uint32_t sweep_absmax(const void* x, int64_t base, int64_t c0, int64_t cend, int stride) {
+    uint32_t acc = 0;
+    for (int64_t c = c0; c < cend; c += stride) {
+        const uint32_t b = as_u(Ty<DT>::load1(x, base + c)) & 0x7FFFFFFFu;
+        acc = acc > b ? acc : b;
+    }
+    return acc;
+}
+// ... and the lane's min / max on top: mx and mn come in holding any element of the row; the return value is the NaN detector
+template <int DT> __device__ __forceinline__ uint32_t sweep_minmax(const void* x, int64_t base, int64_t c0, int64_t cend, int stride, float& mx, float& mn) {
+    uint32_t acc = 0;
+    for (int64_t c = c0; c < cend; c += stride) {
+        const float v = Ty<DT>::load1(x, base + c);
+        mx = __builtin_fmaxf(mx, v);
+        mn = __builtin_fminf(mn, v);
+        const uint32_t b = as_u(v) & 0x7FFFFFFFu;
+        acc = acc > b ? acc : b;
+    }
+    return acc;
+}
+
+// The bounds record: {upper, lower} bound of a row's values, two floats per row, written by every forward for the backwards.
+__device__ __forceinline__ void store_bounds(float* bounds, int64_t row, float ub, float lb) {
+    bounds[2 * row] = ub;
+    bounds[2 * row + 1] = lb;
+}
+// "this row cannot clip": its bounds lie strictly inside (lo, hi), so no element is masked.  false when a bound is NaN
+// (The forwards name lo / hi as fields of their by-value argument struct: a reference keeps those kernarg loads where the written-out
+// predicate had them, behind its short-circuits, instead of hoisting both to the call.)
+__device__ __forceinline__ bool cannot_clip(float ub, float lb, const float& lo, const float& hi) { return (ub < hi) && (lb > lo); }
+// the same from the record (the backwards: lo / hi are kernel arguments of their own)
+__device__ __forceinline__ bool cannot_clip(const float* bounds, int64_t row, float lo, float hi) {
+    const float ub = bounds[2 * row], lb = bounds[2 * row + 1];
+    return (ub < hi) && (lb > lo);
 }
 
 }  // namespace fq

@@ -74,7 +74,7 @@ __device__ __forceinline__ uint32_t export_row_body(const ExportArgs& a, const u
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE;
     const bool ac = AC < 0 ? a.autocast != 0 : AC != 0;
-    const bool want_mask = MASK == 0 ? false : (a.mask && !((ub < a.hi) && (lb > a.lo)));  // block-uniform
+    const bool want_mask = MASK == 0 ? false : (a.mask && !cannot_clip(ub, lb, a.lo, a.hi));  // block-uniform
     const bool sym_clip = a.lo == -a.hi;
     const uint32_t clipk = (ub != ub) ? 0u : a.clipk;
     uint8_t* mrow = (uint8_t*)(a.mask + row * a.mask_row_words);
@@ -240,17 +240,10 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_export_kernel(Expor
 
     int64_t row;
     int t;
-    if constexpr (TPR == 64) {
-        row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-        t = threadIdx.x & 63;
-        if (row >= a.rows) return;  // wave-uniform; NW == 1: no barrier below
-    } else {
-        row = blockIdx.x;
-        t = threadIdx.x;
-    }
+    if (!row_and_lane<TPR>(a.rows, row, t)) return;  // NW == 1: no barrier below
     const int nvec = (int)(a.cols / EPV);
     const uint4* __restrict__ xr = (const uint4*)((const char*)a.x + row * a.cols * T::ESIZE);
-    uint4 r[VPT];
+    uint4 r[VPT];  // (load_clamped() written out: through the helper the bf16 instantiations at VPT 6 / 8 schedule one to three more or fewer s_nop)
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
         int v = t + i * TPR;
@@ -263,15 +256,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_export_kernel(Expor
     float ub, lb, top;
     const bool ac = a.autocast != 0;
     if constexpr (!ASYM) {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            acc = T::absmax_acc(acc, r[i].x);
-            acc = T::absmax_acc(acc, r[i].y);
-            acc = T::absmax_acc(acc, r[i].z);
-            acc = T::absmax_acc(acc, r[i].w);
-        }
-        const float m = as_f(block_reduce<OpMaxU, NW>(T::absmax_finish(acc), red[0]));
+        const float m = row_absmax<DT, NW>(r, red[0]);
         sr = ac ? sym_row_autocast<DT>(m, a.sym) : sym_row<DT>(m, a.sym);
         ub = m;
         lb = -m;
@@ -282,36 +267,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_export_kernel(Expor
         }
     } else {
         float mx, mn;
-        if constexpr (T::ESIZE == 2) {  // min and max on the raw bits (order-preserving 16-bit keys), one reduction
-            MinMaxKeys mk;
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) {
-                mk.acc(r[i].x);
-                mk.acc(r[i].y);
-                mk.acc(r[i].z);
-                mk.acc(r[i].w);
-            }
-            minmax_from_keys<DT>(block_reduce<OpPkMaxU16, NW>(mk.word(), red[0]), mx, mn);
-        } else {
-            MinMax mm;
-            {
-                float f0[T::EPD];
-                T::unpack(r[0].x, f0);
-                mm.mx = mm.mn = f0[0];
-                mm.absacc = 0;
-            }
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) {
-                minmax_acc<DT>(mm, r[i].x);
-                minmax_acc<DT>(mm, r[i].y);
-                minmax_acc<DT>(mm, r[i].z);
-                minmax_acc<DT>(mm, r[i].w);
-            }
-            uint32_t nb = T::absmax_finish(mm.absacc), umx = as_u(mm.mx), umn = as_u(mm.mn);
-            block_reduce3<OpMaxU, OpMaxF, OpMinF, NW>(nb, umx, umn, red);
-            mx = as_f(umx), mn = as_f(umn);
-            if (absbits_is_nan(nb)) mx = mn = as_f(0x7FC00000u);  // torch.max/min propagate NaN
-        }
+        row_minmax<DT, NW>(r, red, mx, mn);
         ar = asym_row<DT>(mx, mn, a.asym);
         ub = mx;
         lb = mn;
@@ -321,10 +277,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_export_kernel(Expor
             a.scales[2 * row + 1] = ar.mn;
         }
     }
-    if (t == 0 && a.bounds) {
-        a.bounds[2 * row] = ub;
-        a.bounds[2 * row + 1] = lb;
-    }
+    if (t == 0 && a.bounds) store_bounds(a.bounds, row, ub, lb);
 
     uint32_t nbad;  // per lane; summed over the wave below
     bool count;     // block-uniform: the row's top bin does not fit the container
@@ -372,7 +325,7 @@ template <int DT, bool ASYM> __global__ __launch_bounds__(256) void row_export_g
     SymRow sr;
     AsymRow ar;
     float ub, lb;
-    if constexpr (!ASYM) {
+    if constexpr (!ASYM) {  // (the sweeps written out: through sweep_absmax() / sweep_minmax() the 16-bit Sym instantiations lay their branches out differently)
         uint32_t acc = 0;
         for (int64_t c = t; c < cols; c += 256) {
             const uint32_t b = as_u(T::load1(a.x, base + c)) & 0x7FFFFFFFu;
@@ -409,10 +362,7 @@ template <int DT, bool ASYM> __global__ __launch_bounds__(256) void row_export_g
             a.scales[2 * row + 1] = ar.mn;
         }
     }
-    if (t == 0 && a.bounds) {
-        a.bounds[2 * row] = ub;
-        a.bounds[2 * row + 1] = lb;
-    }
+    if (t == 0 && a.bounds) store_bounds(a.bounds, row, ub, lb);
     const int cont = a.container;
     uint32_t nbad = 0;
     if (cont != BINS_NONE) {

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void group_reg_kernel(RowArg
 
     // Out-of-range slots re-load the row's last vector.  nvec is a multiple of GV and segments are GV-aligned, so such a slot's whole
     // segment is out of range: its (duplicate) values only ever meet the row bounds, where max / min are idempotent.
-    uint4 r[VPT];
+    uint4 r[VPT];  // (load_clamped() written out: through the helper the VPT == 1 instantiations swap the two arms of this branch)
     if (ga.ntl) {
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
@@ -88,10 +88,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void group_reg_kernel(RowArg
             const float m = as_f(block_reduce<OpMaxU, NW>(lane_m, red[0]));
             ub = m;
             lb = -m;
-            if (t == 0) {
-                a.bounds[2 * row] = m;
-                a.bounds[2 * row + 1] = -m;
-            }
+            if (t == 0) store_bounds(a.bounds, row, m, -m);
         }
     } else if constexpr (T::ESIZE == 2) {  // min and max on the raw bits (order-preserving 16-bit keys), as row_reg_kernel
         uint32_t lane_w = 0;
@@ -110,10 +107,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void group_reg_kernel(RowArg
         }
         if (want_bounds) {
             minmax_from_keys<DT>(block_reduce<OpPkMaxU16, NW>(lane_w, red[0]), ub, lb);
-            if (t == 0) {
-                a.bounds[2 * row] = ub;
-                a.bounds[2 * row + 1] = lb;
-            }
+            if (t == 0) store_bounds(a.bounds, row, ub, lb);
         }
     } else {  // fp32: v_max_f32 / v_min_f32 with NaN tracked through the |x| bits, as row_reg_kernel
         uint32_t lane_nb = 0, lane_mx = 0, lane_mn = 0;
@@ -141,15 +135,12 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void group_reg_kernel(RowArg
             block_reduce3<OpMaxU, OpMaxF, OpMinF, NW>(lane_nb, lane_mx, lane_mn, red);
             ub = as_f(lane_mx), lb = as_f(lane_mn);
             if (absbits_is_nan(lane_nb)) ub = lb = as_f(0x7FC00000u);
-            if (t == 0) {
-                a.bounds[2 * row] = ub;
-                a.bounds[2 * row + 1] = lb;
-            }
+            if (t == 0) store_bounds(a.bounds, row, ub, lb);
         }
     }
 
     // Elementwise pass.  Rows that can actually be clipped also emit the STE bit mask for the backward (full-row layout).
-    const bool want_mask = a.mask && !((ub < a.hi) && (lb > a.lo));  // wave-uniform
+    const bool want_mask = a.mask && !cannot_clip(ub, lb, a.lo, a.hi);  // wave-uniform
     const bool sym_clip = a.lo == -a.hi;
     const uint32_t clipk = (ub != ub) ? 0u : a.clipk;  // a row with a NaN compares as floats (NaN passes the gradient)
     uint8_t* mrow = (uint8_t*)(a.mask + row * a.mask_row_words);

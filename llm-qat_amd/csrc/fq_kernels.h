@@ -12,10 +12,16 @@
 //   w12_kernel          elementwise part of QuantizeLinear's 1-/2-bit weight branches.
 //
 // Roofline for all of them: HBM bandwidth (<= ~10 VALU ops per element, no MFMA).
+//
+// The stages these kernels share are written once: in fq_device.h the clamped register load (load_clamped), the row statistics from
+// registers (lane_absmax / row_absmax, lane_minmax / row_minmax) and by element sweep (sweep_absmax / sweep_minmax), the bounds record
+// (store_bounds) and its reading (cannot_clip), the whole-vector STE mask (ste_vec); below, the bitmap layout for producers
+// (ste_mask_record, ste_mask_record_half over ste_mask_store_nibble) and for consumers (ste_mask_apply, ste_mask_apply_half over
+// ste_mask_zero16) and the row / lane choice (row_and_lane).  Moving a stage must leave every kernel's registers, LDS and scratch where
+// they were and its listing identical or reordered (tools/isa_diff.py): a site where a helper does not manage that
+// keeps the stage written out under a one-line comment in parentheses that says what moved.
 #pragma once
 #include "fq_device.h"
-
-
 
 namespace fq {
 
@@ -122,6 +128,13 @@ template <int N, bool SYMCLIP> __device__ __forceinline__ uint32_t ste_flags_f(c
 // nibbles of a lane pair -> the even lane's byte (the odd lane's return value is not used)
 __device__ __forceinline__ uint32_t ste_nibble_pair(uint32_t nib) { return nib | (dpp<0xB1>(nib) << 4); }   // quad_perm:[1,0,3,2]
 
+// A 4-element lane (an fp32 vector, a half-vector of 16-bit elements): lane v's flags are nibble (v & 1) of the bitmap's byte v / 2.
+__device__ __forceinline__ void ste_mask_store_nibble(uint8_t* mrow, int v, bool in_range, uint32_t nib) {
+    nib = in_range ? nib : 0u;
+    const uint32_t byte = ste_nibble_pair(nib);
+    if (in_range && !(v & 1)) mrow[v >> 1] = (uint8_t)byte;
+}
+
 // Flags of this lane's 16-byte vector `v` of the row (f = its unpacked elements, raw = its dwords) into the row's bitmap.
 // in_range: v < nvec (lanes holding a clamped duplicate of the last vector contribute nothing).
 template <int DT> __device__ __forceinline__ void ste_mask_record(uint8_t* mrow, int v, bool in_range, const uint4& raw,
@@ -135,32 +148,46 @@ template <int DT> __device__ __forceinline__ void ste_mask_record(uint8_t* mrow,
         // 1 % slower on the [2048,4096] launches: profiles/r03_ab_mask_store_dword.txt)
         if (in_range) mrow[v] = (uint8_t)m;
     } else {
-        uint32_t nib = sym_clip ? ste_flags_f<4, true>(f, lo, hi) : ste_flags_f<4, false>(f, lo, hi);
-        nib = in_range ? nib : 0u;
-        const uint32_t byte = ste_nibble_pair(nib);
-        if (in_range && !(v & 1)) mrow[v >> 1] = (uint8_t)byte;
+        ste_mask_store_nibble(mrow, v, in_range, sym_clip ? ste_flags_f<4, true>(f, lo, hi) : ste_flags_f<4, false>(f, lo, hi));
     }
+}
+// The same for the 8-byte half-vector `h` of a 16-bit row (elements 4h .. 4h+3: the fp32-result kernel's lane mapping).
+__device__ __forceinline__ void ste_mask_record_half(uint8_t* mrow, int h, bool in_range, const uint2& raw, const float (&f)[4], float lo, float hi,
+                                                     bool sym_clip, uint32_t clipk) {
+    uint32_t nib;
+    if (clipk) nib = ste_flags16_pair(raw.x, raw.y, clipk);
+    else nib = sym_clip ? ste_flags_f<4, true>(f, lo, hi) : ste_flags_f<4, false>(f, lo, hi);
+    ste_mask_store_nibble(mrow, h, in_range, nib);
 }
 
 // Backward side: this lane's flag byte -> its gradient vector with the flagged elements zeroed.
 //   16-bit: m2 = m | m << 15 holds flag k at bits k and k + 15, so (m2 << (15 - 2d)) has the flags of dword d's two
 //   halves at bits 15 and 31; v_pk_ashrrev_i16 by 15 smears each into its half; v_bfi clears: 3 VALU ops per dword.
+template <int ND> __device__ __forceinline__ void ste_mask_zero16(uint32_t (&w)[ND], uint32_t m /* 2 * ND flag bits */) {
+    typedef short s16x2_t __attribute__((ext_vector_type(2)));
+    const uint32_t m2 = m | (m << 15);
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const s16x2_t t = __builtin_bit_cast(s16x2_t, m2 << (15 - 2 * d));
+        const uint32_t z = __builtin_bit_cast(uint32_t, t >> (short)15);   // v_pk_ashrrev_i16
+        w[d] &= ~z;
+    }
+}
 template <int DT> __device__ __forceinline__ uint4 ste_mask_apply(const uint4& g, uint32_t m /* 8 (4 for fp32) flag bits */) {
     uint32_t w[4] = {g.x, g.y, g.z, g.w};
     if constexpr (Ty<DT>::EPD == 1) {
 #pragma unroll
         for (int d = 0; d < 4; ++d) w[d] = ((m >> d) & 1u) ? 0u : w[d];
     } else {
-        typedef short s16x2_t __attribute__((ext_vector_type(2)));
-        const uint32_t m2 = m | (m << 15);
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const s16x2_t t = __builtin_bit_cast(s16x2_t, m2 << (15 - 2 * d));
-            const uint32_t z = __builtin_bit_cast(uint32_t, t >> (short)15);   // v_pk_ashrrev_i16
-            w[d] &= ~z;
-        }
+        ste_mask_zero16(w, m);
     }
     return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// a half-vector of 16-bit elements and its nibble
+__device__ __forceinline__ uint2 ste_mask_apply_half(uint32_t w0, uint32_t w1, uint32_t m /* 4 flag bits */) {
+    uint32_t w[2] = {w0, w1};
+    ste_mask_zero16(w, m);
+    return make_uint2(w[0], w[1]);
 }
 
 // Which row and which lane a thread of a row kernel is: TPR == 64 puts four rows, one per wave, into a 256-thread block; wider rows own
@@ -249,70 +276,24 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs 
     uint4* __restrict__ yr = (uint4*)((char*)yb + row_byte_off<PITCH>(row, a.cols * T::ESIZE, yp));
 
     uint4 r[VPT];
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        int v = t + i * TPR;
-        v = v < nvec ? v : nvec - 1;
-        r[i] = ld16<NTL>(&xr[v]);
-    }
+    load_clamped<NTL, VPT, TPR>(r, xr, t, nvec);
 
     SymRow sr;
     AsymRow ar;
     float ub, lb;  // bounds of the row's values
     if constexpr (!ASYM) {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            acc = T::absmax_acc(acc, r[i].x);
-            acc = T::absmax_acc(acc, r[i].y);
-            acc = T::absmax_acc(acc, r[i].z);
-            acc = T::absmax_acc(acc, r[i].w);
-        }
-        const uint32_t mbits = block_reduce<OpMaxU, NW>(T::absmax_finish(acc), red[0]);
-        const float m = as_f(mbits);
+        const float m = row_absmax<DT, NW>(r, red[0]);
         if constexpr (AC == 0) sr = sym_row<DT>(m, symk);
         else sr = sym_row_autocast<DT>(m, symk);
         ub = m;
         lb = -m;
         if (t == 0) {
             if (DBG && a.scale) a.scale[row] = sr.s;
-            if (bnd) {
-                bnd[2 * row] = m;
-                bnd[2 * row + 1] = -m;
-            }
+            if (bnd) store_bounds(bnd, row, m, -m);
         }
     } else {
         float mx, mn;
-        if constexpr (T::ESIZE == 2) {  // min and max on the raw bits (order-preserving 16-bit keys), one reduction
-            MinMaxKeys mk;
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) {
-                mk.acc(r[i].x);
-                mk.acc(r[i].y);
-                mk.acc(r[i].z);
-                mk.acc(r[i].w);
-            }
-            minmax_from_keys<DT>(block_reduce<OpPkMaxU16, NW>(mk.word(), red[0]), mx, mn);
-        } else {
-            MinMax mm;
-            {
-                float f0[T::EPD];
-                T::unpack(r[0].x, f0);
-                mm.mx = mm.mn = f0[0];
-                mm.absacc = 0;
-            }
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) {
-                minmax_acc<DT>(mm, r[i].x);
-                minmax_acc<DT>(mm, r[i].y);
-                minmax_acc<DT>(mm, r[i].z);
-                minmax_acc<DT>(mm, r[i].w);
-            }
-            uint32_t nb = T::absmax_finish(mm.absacc), umx = as_u(mm.mx), umn = as_u(mm.mn);
-            block_reduce3<OpMaxU, OpMaxF, OpMinF, NW>(nb, umx, umn, red);
-            mx = as_f(umx), mn = as_f(umn);
-            if (absbits_is_nan(nb)) mx = mn = as_f(0x7FC00000u);  // torch.max/min propagate NaN
-        }
+        row_minmax<DT, NW>(r, red, mx, mn);
         ar = asym_row<DT>(mx, mn, a.asym);
         ub = mx;
         lb = mn;
@@ -321,10 +302,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs 
                 a.scale[2 * row] = ar.al;
                 a.scale[2 * row + 1] = ar.mn;
             }
-            if (bnd) {
-                bnd[2 * row] = mx;
-                bnd[2 * row + 1] = mn;
-            }
+            if (bnd) store_bounds(bnd, row, mx, mn);
         }
     }
     // A row with a NaN / Inf among {alpha + 1e-8, beta} has NaN bins: it takes the plain chain (wave-uniform).
@@ -347,6 +325,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs 
     }
 
     // Elementwise pass.  Rows that can actually be clipped also emit the STE bit mask for the backward.
+    // (cannot_clip() written out: through the helper the 16-bit Sym instantiations at TPR 512 / 1024 allocate two more VGPRs)
     const bool want_mask = msk && !((ub < a.hi) && (lb > a.lo));  // wave-uniform
     const bool sym_clip = a.lo == -a.hi;
     const uint32_t clipk = (ub != ub) ? 0u : a.clipk;  // a row with a NaN compares as floats (NaN passes the gradient)
@@ -355,6 +334,8 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs 
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
         const int v = t + i * TPR;
+        // (the vector's unpacking and packing stay written out here, in group_reg_kernel and in export_row_body: as helpers of their own they
+        // change the register allocation of the TPR == 64 instantiations, whether f travels by reference or by value)
         const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
         float f[EPV];
 #pragma unroll
@@ -422,24 +403,6 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_kernel(RowArgs 
 // the same 4-elements-per-lane mapping.
 // Serves two tensors per launch like row_reg_kernel (the K and V hooks: modeling_llama_quant.py:320-327).
 // ------------------------------------------------------------------------------------
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-template <bool NT> __device__ __forceinline__ uint2 ld8(const uint2* p) {
-    if constexpr (NT) {
-        u32x2_t v = __builtin_nontemporal_load((const u32x2_t*)p);
-        return make_uint2(v.x, v.y);
-    } else {
-        return *p;
-    }
-}
-template <bool NT> __device__ __forceinline__ void st8(uint2* p, uint2 v) {
-    if constexpr (NT) {
-        u32x2_t w = {v.x, v.y};
-        __builtin_nontemporal_store(w, (u32x2_t*)p);
-    } else {
-        *p = v;
-    }
-}
-
 template <int DT, int TPR, int HPT, bool NTL, bool NTS, bool MASK, bool PITCH = false>
 __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_wide_kernel(RowArgs a) {
     using T = Ty<DT>;
@@ -485,22 +448,11 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_wide_kernel(Row
     const uint2* __restrict__ xr = (const uint2*)((const char*)xb + row_byte_off<PITCH>(row, a.cols * 2, xp));
     uint4* __restrict__ yr = (uint4*)((char*)yb + row_byte_off<PITCH>(row, a.cols * 4, yp));
     uint2 r[HPT];
-#pragma unroll
-    for (int i = 0; i < HPT; ++i) {
-        int h = t + i * TPR;
-        h = h < nh ? h : nh - 1;
-        r[i] = ld8<NTL>(&xr[h]);
-    }
-    uint32_t acc = 0;
-#pragma unroll
-    for (int i = 0; i < HPT; ++i) acc = T::absmax_acc(T::absmax_acc(acc, r[i].x), r[i].y);
-    const float m = as_f(block_reduce<OpMaxU, NW>(T::absmax_finish(acc), red));
+    load_clamped<NTL, HPT, TPR>(r, xr, t, nh);
+    const float m = row_absmax<DT, NW>(r, red);
     const SymRow sr = sym_row_autocast<DT>(m, SymConst{qmax, a.sym.c6});
-    if (t == 0 && bnd) {
-        bnd[2 * row] = m;
-        bnd[2 * row + 1] = -m;
-    }
-    const bool want_mask = MASK && msk && !((m < a.hi) && (-m > a.lo));  // wave-uniform; NaN row: mask written, all bits 0
+    if (t == 0 && bnd) store_bounds(bnd, row, m, -m);
+    const bool want_mask = MASK && msk && !cannot_clip(m, -m, a.lo, a.hi);  // wave-uniform; NaN row: mask written, all bits 0
     const bool sym_clip = a.lo == -a.hi;
     const uint32_t clipk = (m != m) ? 0u : a.clipk;
     uint8_t* mrow = (uint8_t*)(msk + row * a.mask_row_words);
@@ -514,14 +466,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_reg_wide_kernel(Row
             T::unpack(r[i].y, f1);
             f[0] = f0[0], f[1] = f0[1], f[2] = f1[0], f[3] = f1[1];
         }
-        if (MASK && want_mask) {  // half-vector h = elements 4h .. 4h+3 = nibble (h & 1) of the bitmap's byte h / 2
-            uint32_t nib;
-            if (clipk) nib = ste_flags16_pair(r[i].x, r[i].y, clipk);
-            else nib = sym_clip ? ste_flags_f<4, true>(f, a.lo, a.hi) : ste_flags_f<4, false>(f, a.lo, a.hi);
-            nib = h < nh ? nib : 0u;
-            const uint32_t byte = ste_nibble_pair(nib);
-            if (h < nh && !(h & 1)) mrow[h >> 1] = (uint8_t)byte;
-        }
+        if (MASK && want_mask) ste_mask_record_half(mrow, h, h < nh, r[i], f, a.lo, a.hi, sym_clip, clipk);
         const uint4 o = make_uint4(as_u(sym_elem_autocast(f[0], sr)), as_u(sym_elem_autocast(f[1], sr)),
                                    as_u(sym_elem_autocast(f[2], sr)), as_u(sym_elem_autocast(f[3], sr)));
         if (h < nh) st16<NTS>(&yr[h], o);
@@ -564,32 +509,16 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_generic_kernel(RowA
     SymRow sr;
     AsymRow ar;
     if constexpr (!ASYM) {
-        uint32_t acc = 0;
-        for (int64_t c = t; c < cols; c += TPR) {
-            uint32_t b = as_u(T::load1(a.x, xbase + c)) & 0x7FFFFFFFu;
-            acc = acc > b ? acc : b;
-        }
-        const float m = as_f(block_reduce<OpMaxU, NW>(acc, red[0]));
+        const float m = as_f(block_reduce<OpMaxU, NW>(sweep_absmax<DT>(a.x, xbase, t, cols, TPR), red[0]));
         if constexpr (AC == 0) sr = sym_row<DT>(m, a.sym);
         else sr = sym_row_autocast<DT>(m, a.sym);
         if (t == 0) {
             if (a.scale) a.scale[row] = sr.s;
-            if (a.bounds) {
-                a.bounds[2 * row] = m;
-                a.bounds[2 * row + 1] = -m;
-            }
+            if (a.bounds) store_bounds(a.bounds, row, m, -m);
         }
     } else {
         float mx = first, mn = first;
-        uint32_t acc = 0;
-        for (int64_t c = t; c < cols; c += TPR) {
-            float v = T::load1(a.x, xbase + c);
-            mx = __builtin_fmaxf(mx, v);
-            mn = __builtin_fminf(mn, v);
-            uint32_t b = as_u(v) & 0x7FFFFFFFu;
-            acc = acc > b ? acc : b;
-        }
-        const uint32_t nb = block_reduce<OpMaxU, NW>(acc, red[0]);
+        const uint32_t nb = block_reduce<OpMaxU, NW>(sweep_minmax<DT>(a.x, xbase, t, cols, TPR, mx, mn), red[0]);
         mx = as_f(block_reduce<OpMaxF, NW>(as_u(mx), red[1]));
         mn = as_f(block_reduce<OpMinF, NW>(as_u(mn), red[2]));
         if (absbits_is_nan(nb)) mx = mn = as_f(0x7FC00000u);
@@ -599,10 +528,7 @@ __global__ __launch_bounds__(TPR == 64 ? 256 : TPR) void row_generic_kernel(RowA
                 a.scale[2 * row] = ar.al;
                 a.scale[2 * row + 1] = ar.mn;
             }
-            if (a.bounds) {
-                a.bounds[2 * row] = mx;
-                a.bounds[2 * row + 1] = mn;
-            }
+            if (a.bounds) store_bounds(a.bounds, row, mx, mn);
         }
     }
     for (int64_t c = t; c < cols; c += TPR) {
@@ -652,49 +578,19 @@ __global__ __launch_bounds__(TP_THREADS) void stats_kernel(RowArgs a, uint32_t* 
         const uint4* xr = (const uint4*)((const char*)a.x + (base + c0) * T::ESIZE);
         const int nvec = (int)((cend - c0) / EPV);  // >= 1
         uint4 r[TP_VPT];
-#pragma unroll
-        for (int i = 0; i < TP_VPT; ++i) {
-            int v = t + i * TP_THREADS;
-            v = v < nvec ? v : nvec - 1;
-            r[i] = xr[v];
-        }
+        load_clamped<false, TP_VPT, TP_THREADS>(r, xr, t, nvec);
         if constexpr (!ASYM) {
-#pragma unroll
-            for (int i = 0; i < TP_VPT; ++i) {
-                acc = T::absmax_acc(acc, r[i].x);
-                acc = T::absmax_acc(acc, r[i].y);
-                acc = T::absmax_acc(acc, r[i].z);
-                acc = T::absmax_acc(acc, r[i].w);
-            }
-            acc = T::absmax_finish(acc);
+            acc = lane_absmax<DT>(r);
         } else {
-            MinMax mm;
-            float f0[T::EPD];
-            T::unpack(r[0].x, f0);
-            mm.mx = mm.mn = f0[0];
-            mm.absacc = 0;
-#pragma unroll
-            for (int i = 0; i < TP_VPT; ++i) {
-                minmax_acc<DT>(mm, r[i].x);
-                minmax_acc<DT>(mm, r[i].y);
-                minmax_acc<DT>(mm, r[i].z);
-                minmax_acc<DT>(mm, r[i].w);
-            }
+            const MinMax mm = lane_minmax<DT>(r);
             acc = T::absmax_finish(mm.absacc);
             mx = mm.mx;
             mn = mm.mn;
         }
     } else {
         mx = mn = T::load1(a.x, base + c0);
-        for (int64_t c = c0 + t; c < cend; c += TP_THREADS) {
-            float v = T::load1(a.x, base + c);
-            uint32_t b = as_u(v) & 0x7FFFFFFFu;
-            acc = acc > b ? acc : b;
-            if constexpr (ASYM) {
-                mx = __builtin_fmaxf(mx, v);
-                mn = __builtin_fminf(mn, v);
-            }
-        }
+        if constexpr (!ASYM) acc = sweep_absmax<DT>(a.x, base, c0 + t, cend, TP_THREADS);
+        else acc = sweep_minmax<DT>(a.x, base, c0 + t, cend, TP_THREADS, mx, mn);
     }
     acc = block_reduce<OpMaxU, TP_THREADS / 64>(acc, red[0]);
     if constexpr (!ASYM) {
@@ -728,7 +624,7 @@ __global__ __launch_bounds__(TP_THREADS) void apply_kernel(RowArgs a, const uint
     if constexpr (!ASYM) {
         const float m = as_f(ws[2 * row]);
         sr = sym_row<DT>(m, a.sym);
-        if (chunk == 0 && t == 0) {
+        if (chunk == 0 && t == 0) {  // (store_bounds() written out, here and in apply_autocast_kernel: through the helper they need more SGPRs)
             if (a.scale) a.scale[row] = sr.s;
             if (a.bounds) {
                 a.bounds[2 * row] = m;
@@ -762,18 +658,13 @@ __global__ __launch_bounds__(TP_THREADS) void apply_kernel(RowArgs a, const uint
         int32_t* idxr = a.idx ? a.idx + base + c0 : nullptr;
         const int nvec = (int)((cend - c0) / EPV);
         uint4 r[TP_VPT];
-#pragma unroll
-        for (int i = 0; i < TP_VPT; ++i) {
-            int v = t + i * TP_THREADS;
-            v = v < nvec ? v : nvec - 1;
-            r[i] = xr[v];
-        }
+        load_clamped<false, TP_VPT, TP_THREADS>(r, xr, t, nvec);
 #pragma unroll
         for (int i = 0; i < TP_VPT; ++i) {
             const int v = t + i * TP_THREADS;
             uint4 o;
             int32_t ib[EPV];
-            if constexpr (!ASYM) {
+            if constexpr (!ASYM) {  // (dword by dword: a whole-vector form of sym_dword / asym_dword frees a VGPR of the fp32 instantiations)
                 o.x = sym_dword<DT, FAST && DT == BF16>(r[i].x, sr, idxr ? ib + 0 * T::EPD : nullptr);
                 o.y = sym_dword<DT, FAST && DT == BF16>(r[i].y, sr, idxr ? ib + 1 * T::EPD : nullptr);
                 o.z = sym_dword<DT, FAST && DT == BF16>(r[i].z, sr, idxr ? ib + 2 * T::EPD : nullptr);
@@ -839,21 +730,12 @@ __global__ __launch_bounds__(STE_THREADS) void ste_vec_kernel(const uint4* __res
                                                               uint4* __restrict__ gx, int64_t nvec, float lo, float hi) {
     const int64_t v0 = (int64_t)blockIdx.x * (STE_THREADS * UNR) + threadIdx.x;
     uint4 rg[UNR], rx[UNR];
-#pragma unroll
-    for (int i = 0; i < UNR; ++i) {
-        int64_t v = v0 + (int64_t)i * STE_THREADS;
-        v = v < nvec ? v : nvec - 1;
-        rg[i] = ld16<NTL>(&g[v]);
-        rx[i] = ld16<NTL>(&x[v]);
-    }
+    load_clamped<NTL, UNR, STE_THREADS>(rg, g, v0, nvec);
+    load_clamped<NTL, UNR, STE_THREADS>(rx, x, v0, nvec);
 #pragma unroll
     for (int i = 0; i < UNR; ++i) {
         const int64_t v = v0 + (int64_t)i * STE_THREADS;
-        uint4 o;
-        o.x = ste_dword<DT>(rg[i].x, rx[i].x, lo, hi);
-        o.y = ste_dword<DT>(rg[i].y, rx[i].y, lo, hi);
-        o.z = ste_dword<DT>(rg[i].z, rx[i].z, lo, hi);
-        o.w = ste_dword<DT>(rg[i].w, rx[i].w, lo, hi);
+        const uint4 o = ste_vec<DT>(rg[i], rx[i], lo, hi);
         if (v < nvec) st16<NTS>(&gx[v], o);
     }
 }
@@ -889,18 +771,10 @@ __global__ __launch_bounds__(STE_THREADS) void ste_rows_kernel(const void* __res
     const int64_t rem = nvec_row - vs;
     const int nvec = (int)(rem < cv ? rem : cv);
     bool safe = false;   // no recorded bounds (pitched tensors in the plain data flow): every row re-reads x
-    if (bounds) {
-        const float ub = bounds[2 * row], lb = bounds[2 * row + 1];
-        safe = (ub < hi) && (lb > lo);  // false when a bound is NaN
-    }
+    if (bounds) safe = cannot_clip(bounds, row, lo, hi);
     const int t = threadIdx.x;
     uint4 rg[VPT];
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        int v = t + i * STE_THREADS;
-        v = v < nvec ? v : nvec - 1;
-        rg[i] = ld16<NTL>(&gr[v]);
-    }
+    load_clamped<NTL, VPT, STE_THREADS>(rg, gr, t, nvec);
     if (safe) {  // block-uniform
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
@@ -909,20 +783,11 @@ __global__ __launch_bounds__(STE_THREADS) void ste_rows_kernel(const void* __res
         }
     } else {
         uint4 rx[VPT];
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            int v = t + i * STE_THREADS;
-            v = v < nvec ? v : nvec - 1;
-            rx[i] = ld16<NTL>(&xr[v]);
-        }
+        load_clamped<NTL, VPT, STE_THREADS>(rx, xr, t, nvec);
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
             const int v = t + i * STE_THREADS;
-            uint4 o;
-            o.x = ste_dword<DT>(rg[i].x, rx[i].x, lo, hi);
-            o.y = ste_dword<DT>(rg[i].y, rx[i].y, lo, hi);
-            o.z = ste_dword<DT>(rg[i].z, rx[i].z, lo, hi);
-            o.w = ste_dword<DT>(rg[i].w, rx[i].w, lo, hi);
+            const uint4 o = ste_vec<DT>(rg[i], rx[i], lo, hi);
             if (v < nvec) st16<NTS>(&or_[v], o);
         }
     }
@@ -1196,19 +1061,11 @@ __device__ __forceinline__ void ste_mask_chunk(const void* g, void* gx, const ui
     const int64_t rem = nvec_row - vs;
     const int nvec = (int)(rem < cv ? rem : cv);
     uint4 rg[VPT];
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        int v = t + i * STE_THREADS;
-        v = v < nvec ? v : nvec - 1;
-        rg[i] = ld16<NTL>(&gr[v]);
-    }
+    load_clamped<NTL, VPT, STE_THREADS>(rg, gr, t, nvec);
     SteMaskHeld<16 / T::ESIZE, VPT> mh;
     mh.load(mrow, vs, mrow_dwords, t);  // unconditionally (a safe row's bitmap is unwritten memory of the same buffer: read, ignored)
     bool safe = false;
-    if (bounds) {
-        const float ub = bounds[2 * row], lb = bounds[2 * row + 1];
-        safe = (ub < hi) && (lb > lo);  // false when a bound is NaN
-    }
+    if (bounds) safe = cannot_clip(bounds, row, lo, hi);
     if (safe) {  // block-uniform
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
@@ -1255,10 +1112,7 @@ __global__ __launch_bounds__(STE_THREADS) void ste_mask_kernel(SteLaunch L, int6
     // in place: which of this block's STE_THREADS rows can clip at all?
     const int64_t r0 = local * STE_THREADS;
     bool unsafe = false;
-    if (r0 + t < sl.rows) {
-        const float ub = sl.bounds[2 * (r0 + t)], lb = sl.bounds[2 * (r0 + t) + 1];
-        unsafe = !((ub < hi) && (lb > lo));
-    }
+    if (r0 + t < sl.rows) unsafe = !cannot_clip(sl.bounds, r0 + t, lo, hi);
     const uint64_t bal = __ballot(unsafe);
     if ((t & 63) == 0) unsafe_rows[t >> 6] = bal;
     __syncthreads();
@@ -1286,7 +1140,6 @@ template <int DT, int HPT, bool NTL = true, bool NTS = true, bool PITCH = false,
 __global__ __launch_bounds__(STE_THREADS) void ste_mask_wide_kernel(SteLaunch L, int64_t nh_row, int ch, int64_t mask_row_words, float lo, float hi) {
     using T = Ty<DT>;
     static_assert(T::ESIZE == 2, "fp32 gradient in, 16-bit gradient out");
-    typedef short s16x2_t __attribute__((ext_vector_type(2)));
     SteSlot sl;   // NS = 1: K's or V's gradient alone (each has its own autograd node): the first slot as it stands, nothing to pick
     if constexpr (NS == 1) sl = L.t[0];
     else sl = ste_pick_slot<PITCH, NS>(L, (int64_t)blockIdx.x);
@@ -1298,16 +1151,10 @@ __global__ __launch_bounds__(STE_THREADS) void ste_mask_wide_kernel(SteLaunch L,
     const int nh = (int)(rem < ch ? rem : ch);
     const int t = threadIdx.x;
     uint4 rg[HPT];
-#pragma unroll
-    for (int i = 0; i < HPT; ++i) {
-        int h = t + i * STE_THREADS;
-        h = h < nh ? h : nh - 1;
-        rg[i] = ld16<NTL>(&gr[h]);
-    }
+    load_clamped<NTL, HPT, STE_THREADS>(rg, gr, t, nh);
     SteMaskHeld<4, HPT> mh;
     mh.load((const uint8_t*)(sl.mask + row * mask_row_words), hs, (int)mask_row_words * 2, t);
-    const float ub = sl.bounds[2 * row], lb = sl.bounds[2 * row + 1];
-    const bool safe = (ub < hi) && (lb > lo);
+    const bool safe = cannot_clip(sl.bounds, row, lo, hi);
     uint32_t mb[HPT];
     if (!safe) mh.bits(t, mb);  // block-uniform
     else {
@@ -1318,11 +1165,8 @@ __global__ __launch_bounds__(STE_THREADS) void ste_mask_wide_kernel(SteLaunch L,
     for (int i = 0; i < HPT; ++i) {
         const int h = t + i * STE_THREADS;
         const float f0[2] = {as_f(rg[i].x), as_f(rg[i].y)}, f1[2] = {as_f(rg[i].z), as_f(rg[i].w)};
-        uint32_t w0 = T::pack(f0), w1 = T::pack(f1);
-        const uint32_t m2 = mb[i] | (mb[i] << 15);
-        w0 &= ~__builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2_t, m2 << 15) >> (short)15);
-        w1 &= ~__builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2_t, m2 << 13) >> (short)15);
-        if (h < nh) st8<NTS>(&or_[h], make_uint2(w0, w1));
+        const uint2 o = ste_mask_apply_half(T::pack(f0), T::pack(f1), mb[i]);
+        if (h < nh) st8<NTS>(&or_[h], o);
     }
 }
 

@@ -3,10 +3,16 @@
 
     python tools/isa_diff.py before.s after.s
 
-Equal means: the same set of demangled kernel names; per kernel the same instruction text (comments and directives stripped, labels
-renumbered in order of appearance within the kernel, because their numbers move with the order of instantiation) and the same
-VGPR / SGPR count, scratch, LDS and kernarg size.  Prints one line per difference and a count; exit status 1 if anything differs.
+Three verdicts per kernel (the two listings must hold the same set of demangled kernel names):
+  identical  the same instruction text (comments and directives stripped, labels renumbered in order of appearance within the kernel,
+             because their numbers move with the order of instantiation) and the same VGPR / SGPR count, accum offset, scratch, LDS
+             and kernarg size;
+  reordered  the same metadata and the same count per opcode (the first token of each instruction; a label counts as one opcode):
+             only register names and the order of instructions moved -- what moving a stage into an inlined helper does;
+  differs    anything else: the line names the metadata that moved and the opcodes whose counts differ.
+Prints one line per kernel that is not identical and the three counts; exit status 1 if a kernel differs or exists on one side only.
 """
+import collections
 import re
 import subprocess
 import sys
@@ -40,25 +46,33 @@ def kernels(path):
     return out
 
 
+def opcodes(ins):
+    return collections.Counter('label:' if i.endswith(':') else i.split()[0] for i in ins)
+
+
 def main():
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
     bad = 0
     for n in sorted(set(a) ^ set(b)):
         bad += 1
         print(('only in %s: ' % sys.argv[1 if n in a else 2]) + n)
-    same = 0
+    same = reordered = 0
     for n in sorted(set(a) & set(b)):
         if a[n] == b[n]:
             same += 1
             continue
-        bad += 1
         (ia, ma), (ib, mb) = a[n], b[n]
+        ca, cb = opcodes(ia), opcodes(ib)
+        if ma == mb and ca == cb:
+            reordered += 1
+            print('reordered: %s' % n)
+            continue
+        bad += 1
         what = [k + ' %s -> %s' % (ma.get(k), mb.get(k)) for k in META if ma.get(k) != mb.get(k)]
-        if ia != ib:
-            first = next((i for i, (x, y) in enumerate(zip(ia, ib)) if x != y), min(len(ia), len(ib)))
-            what.append('instructions %d -> %d, first difference at %d' % (len(ia), len(ib), first))
+        if ca != cb:
+            what.append('instructions %d -> %d: ' % (len(ia), len(ib)) + ', '.join('%s %d -> %d' % (o, ca[o], cb[o]) for o in sorted(set(ca) | set(cb)) if ca[o] != cb[o]))
         print('differs: %s: %s' % (n, '; '.join(what)))
-    print('%d kernels compared, %d identical' % (len(set(a) | set(b)), same))
+    print('%d kernels compared, %d identical, %d reordered, %d other' % (len(set(a) | set(b)), same, reordered, bad))
     sys.exit(1 if bad else 0)
 
 
