@@ -199,7 +199,7 @@ struct FqPairNode : public torch::autograd::Function<FqPairNode> {
 };
 
 // ---- the one-tensor node ---------------------------------------------------------------------------------------------------------------
-// utils_quant._PrecomputedAct in C++: a node over ONE tensor that a launch has already fake-quantized (K and V of the KV-cache hooks,
+// utils_quant._SharedAct over a call's own side-buffer result, in C++: a node over ONE tensor that a launch has already fake-quantized (K and V of the KV-cache hooks,
 // models/modeling_llama_quant.py:320-327, which share a forward launch but never a node).  Forward launches nothing; backward is that
 // tensor's own STE launch -- fq_ste_bwd_mask, or fq_ste_bwd_mask_wide behind the reference's fp32 result under autocast (fp32 gradient in,
 // input-dtype gradient out).  Never in place: these are gradients of tensors a caller can see.

@@ -167,8 +167,9 @@ def _graph_aware(backward):
 
 class _Raw:
     """What one fake-quant forward produced, apart from any autograd node: the result as plain data plus everything a backward needs.
-    `_FakeQuantFunction` makes one and attaches it to its own node; a shared activation (point 1 below) is one `_Raw` that every sibling
-    projection wraps in a node of its OWN (`_SharedAct`), so that no two callers ever share a piece of graph."""
+    The one record for that: `_FakeQuantFunction` makes one and attaches it to its own node; a shared activation (point 1 below) is one
+    `_Raw` that every sibling projection wraps in a node of its OWN (`_SharedAct`), so that no two callers ever share a piece of graph;
+    the weight cache keeps one per layer, and the pending V of a K + V launch is one until the V call asks for it."""
     __slots__ = ("out", "mode", "saved", "clip", "rows_cols", "grad_dtype")
 
     def __init__(self, out, mode, saved=(), clip=None, rows_cols=None, grad_dtype=None):
@@ -179,12 +180,25 @@ class _Raw:
 # bare tuples, unpacked into names where they are read: a _ThreadState.acts entry (_act_store / _act_lookup; its layout is written at
 # _ThreadState.acts) and a _ThreadState.outs record (_note_output / _kv_hook: weakref(output), its version, region, stream).  So does
 # ops.pair_forward's result, unpacked once on arrival.  Constructing a namedtuple is a Python-level call each time, and with all of these
-# named the planned route's host forward left the parent's spread (profiles/pair_route_refactor_host_ab_named_records.txt).
+# named the planned route's host forward left the parent's spread (profiles/pair_route_refactor_host_ab_named_records.txt).  A `_Raw` is
+# written per call too (the remembered activation, K and V): one __slots__ object whose __init__ is a single tuple assignment.
 _Plan = namedtuple("_Plan", "shape in_dtype w_dtype settings eligible launch bits")   # QuantizeLinear._fq_plan, see QuantizeLinear._new_plan
-_VResult = namedtuple("_VResult", "vq side rows cols clip")                 # V as a K + V launch left it, until the V call asks for it
-_KVStash = namedtuple("_KVStash", "ref version v state sig")                # _ThreadState.kv: weakref(V's input), its version, the _VResult, _kv_state, call signature
-_QWeight = namedtuple("_QWeight", "y bounds mask rows_cols")                # a fake-quantized weight as plain data (what _ReuseQuantizedWeight wraps)
-_WCache = namedtuple("_WCache", "key value")                                # QuantizeLinear._fq_wcache: _wcache_key() and the _QWeight made under it
+_KVStash = namedtuple("_KVStash", "ref version v state sig")                # _ThreadState.kv: weakref(V's input), its version, V's _Raw, _kv_state, call signature
+_WCache = namedtuple("_WCache", "key value")                                # QuantizeLinear._fq_wcache: _wcache_key() and the weight's _Raw made under it
+
+
+def _compute_raw(kind, input, clip_val, num_bits, layerwise, narrow, need_grad):
+    """`_compute` for the callers outside a Function.forward (where grad mode is off already): a `_Raw` is plain data, so it is made with
+    grad mode off -- nothing in it carries a graph (a copy path's CloneBackward, the CPU-tensor ops' chain) that whoever remembers the
+    record would pin, intermediates and input included, until the entry is replaced.  (What `with torch.no_grad()` does, without the two
+    context objects it builds: 0.4 us instead of 1.8 us on a call that costs 11 us.)"""
+    if not torch.is_grad_enabled():
+        return _compute(kind, input, clip_val, num_bits, layerwise, narrow, need_grad)
+    torch._C._set_grad_enabled(False)
+    try:
+        return _compute(kind, input, clip_val, num_bits, layerwise, narrow, need_grad)
+    finally:
+        torch._C._set_grad_enabled(True)
 
 
 def _compute(kind, input, clip_val, num_bits, layerwise, narrow, need_grad):
@@ -299,11 +313,13 @@ def _apply_over_raw(kind, input, clip_val, num_bits, layerwise):
         return None
     if type(num_bits) is not int:
         num_bits = ops.bits_arg(num_bits)
-    raw = _compute(kind, input, clip_val, num_bits, layerwise, False, True)
-    if raw.mode in ("mask", "mask_wide"):
+    raw = _compute_raw(kind, input, clip_val, num_bits, layerwise, False, True)
+    if raw.mode == "mask" or raw.mode == "mask_wide":
+        # _node_over_raw's C++ branch written out: everything it tests has been tested above, and with the call in between this path's
+        # host forward left the parent's spread (profiles/raw_node_refactor_host_ab.txt)
         rows, cols = raw.rows_cols
         return _cnode.one_node(input, raw.out, raw.saved[0], rows, cols, raw.clip[0], raw.clip[1], _state().cell)
-    return _SharedAct.apply(input, raw, True)     # (bounds / plain data flows: the Python node over the same result)
+    return _node_over_raw(input, raw, True)     # (bounds / plain data flows: the Python node over the same result)
 
 
 class SymQuantizer(_FakeQuantFunction):
@@ -945,23 +961,37 @@ def _act_store(st, key, x, raw, region, stream):
 
 
 class _SharedAct(torch.autograd.Function):
-    """One sibling's OWN autograd node over an activation some launch has already fake-quantized (a `_Raw`): forward launches nothing,
-    backward is the ordinary STE backward of `_FakeQuantFunction` over the raw's side buffer."""
+    """The Python node over a result some launch has already produced (a `_Raw`): one sibling's OWN node over a shared activation, the
+    weight cache's node over the weight it holds, K's and V's own nodes over the two halves of their launch.  Forward launches nothing;
+    backward is the ordinary STE backward of `_FakeQuantFunction` over what the raw saved -- that function itself, so that the guard
+    of a weight's in-place gradient (`_inplace_ok`) is called from the frame it was calibrated in."""
 
     @staticmethod
-    def forward(ctx, x, raw, own=False):
-        _attach(ctx, raw)
-        if own:               # the raw is this call's alone (_apply_over_raw): its tensor becomes the output as it is
+    def forward(ctx, x, raw, own=False, inplace_grad=False):
+        _attach(ctx, raw, inplace_grad)
+        if own:               # the raw is this call's alone: its tensor becomes the output as it is (in-place ops on it work as in the reference)
             return raw.out
-        return raw.out.view_as(raw.out)   # a tensor of this node's own: the raw stays plain data for the next sibling
+        return raw.out.view_as(raw.out)   # a tensor of this node's own: the raw stays plain data for the next sibling / the next use
 
     backward = _FakeQuantFunction.backward
 
 
-def _wrap_shared(x, raw):
-    if raw.mode == "none" or not (torch.is_grad_enabled() and x.requires_grad):
+def _node_over_raw(x, raw, own=False, inplace_grad=False):
+    """x's fake-quantized value with a node of x's OWN over a `_Raw` -- the bare data where no backward will run.  own: the raw is this
+    call's alone, made with side outputs only if x needs a gradient now (mode "none" otherwise); else it is remembered, and the node gets
+    a tensor of its own over the same memory.  The C++ one-tensor node (csrc/fq_autograd_node.cpp::FqOneNode) serves a CUDA tensor's own
+    side-buffer result; `_SharedAct` everything else (a remembered raw, a weight whose gradient may be masked in place, the bounds /
+    plain / CPU data flows)."""
+    mode = raw.mode
+    if mode == "none":
         return raw.out
-    return _SharedAct.apply(x, raw)
+    if own and _USE_CNODE and (mode == "mask" or mode == "mask_wide") and x.is_cuda and not inplace_grad:
+        rows, cols = raw.rows_cols
+        lo, hi = raw.clip
+        return _cnode.one_node(x, raw.out, raw.saved[0], rows, cols, lo, hi, _state().cell)
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        return raw.out
+    return _SharedAct.apply(x, raw, own, inplace_grad)
 
 
 def _shared_activation(quantizer, x, num_bits, layerwise):
@@ -977,12 +1007,12 @@ def _shared_activation(quantizer, x, num_bits, layerwise):
         _count("act_share_miss")
         if type(num_bits) is not int:
             num_bits = ops.bits_arg(num_bits)
-        raw = _compute("asym" if quantizer is AsymQuantizer else "sym", x, _CLIP, num_bits, layerwise, quantizer is _SymQuantizerOperand,
-                       torch.is_grad_enabled() and x.requires_grad)
+        raw = _compute_raw("asym" if quantizer is AsymQuantizer else "sym", x, _CLIP, num_bits, layerwise, quantizer is _SymQuantizerOperand,
+                           torch.is_grad_enabled() and x.requires_grad)
         _act_store(st, key, x, raw, region, stream)
     else:
         _count("act_share_hit")
-    return _wrap_shared(x, raw)
+    return _node_over_raw(x, raw)
 
 
 # 3. QuantizeLinear needs its weight [out, in] and its input [tokens, in] fake-quantized at the same moment, and both
@@ -1058,6 +1088,18 @@ def _pair_backward_from_cpp(gw, gx, side_w, side_x, rows_w, rows_x, cols, code, 
     return ow, ox
 
 
+def _kv_pair(k, v, num_bits, lo, hi, need_k, need_v):
+    """K and V in ONE forward launch (quantize_kv and the unchanged hooks) -> their two `_Raw`s, each with its own side buffer, or None
+    where the pair is not served.  Under autocast the results are the reference's fp32 ones, whose mask has its own layout."""
+    res = ops.pair_forward(k, v, num_bits, num_bits, lo, hi, need_k, need_v, wide=True)
+    if res is None:
+        return None
+    kq, vq, side_k, side_v, rows_k, rows_v, cols = res
+    mode = "mask" if kq.dtype == k.dtype else "mask_wide"
+    return (_Raw(kq, mode, (side_k,), (lo, hi), (rows_k, cols), k.dtype) if need_k else _Raw(kq, "none"),
+            _Raw(vq, mode, (side_v,), (lo, hi), (rows_v, cols), v.dtype) if need_v else _Raw(vq, "none"))
+
+
 def quantize_kv(key_states, value_states, clip_val_k, clip_val_v, num_bits):
     """The two KV-cache hooks of the attention block (models/modeling_llama_quant.py:320-327),
 
@@ -1080,11 +1122,9 @@ def quantize_kv(key_states, value_states, clip_val_k, clip_val_v, num_bits):
             and k.dim() <= 3 and v.dim() <= 3):
         grad = torch.is_grad_enabled()
         need_k, need_v = grad and k.requires_grad, grad and v.requires_grad
-        res = ops.pair_forward(k, v, num_bits, num_bits, lo, hi, need_k, need_v, wide=True)
-        if res is not None:
-            kq, vq, side_k, side_v, rows_k, rows_v, cols = res
-            return (_precomputed(k, kq, side_k, rows_k, cols, (lo, hi)) if need_k else kq,
-                    _precomputed(v, vq, side_v, rows_v, cols, (lo, hi)) if need_v else vq)
+        raws = _kv_pair(k, v, num_bits, lo, hi, need_k, need_v)
+        if raws is not None:
+            return _node_over_raw(k, raws[0], True), _node_over_raw(v, raws[1], True)
     return (SymQuantizer.apply(k, clip_val_k, num_bits, False), SymQuantizer.apply(v, clip_val_v, num_bits, False))
 
 
@@ -1157,8 +1197,7 @@ def _kv_hook(x, clip_val, num_bits):
         if stash.ref() is x and stash.version == x._version and stash.state == _kv_state(st, clip_val, num_bits, stream):
             st.kv = None
             _count("kv_pair_hit")
-            v = stash.v   # V: quantized together with K a moment ago; its autograd node is built only now
-            return v.vq if v.side is None else _precomputed(x, v.vq, v.side, v.rows, v.cols, v.clip)
+            return _node_over_raw(x, stash.v, True)   # V: quantized together with K a moment ago; its autograd node is built only now
         _kv_discard(st)
     rec = st.outs
     if not rec:
@@ -1184,17 +1223,16 @@ def _kv_hook(x, clip_val, num_bits):
                 return None
             grad = torch.is_grad_enabled()
             need = grad and x.requires_grad
-            res = ops.pair_forward(x, v, num_bits, num_bits, lo, hi, need, need, wide=True)
-            if res is None:
+            raws = _kv_pair(x, v, num_bits, lo, hi, need, need)
+            if raws is None:
                 return None
             _count("kv_pair_launch")
             # One launch forward, but NOT one autograd node: until the V call arrives, V's result is plain data (no graph refers to the
             # tensor V), so a guess that turns out wrong leaves nothing behind -- in particular it cannot make V's producer reachable from
             # a loss that never uses V (a checkpointed producer would be recomputed and hand ZERO gradients to its parameters where the
             # reference leaves None: tests/test_gpu_random_programs.py).  Each of K and V gets its own node over its own side buffer.
-            kq, vq, side_k, side_v, rows_k, rows_v, cols = res
-            st.kv = _KVStash(weakref.ref(v), v._version, _VResult(vq, side_v if need else None, rows_v, cols, (lo, hi)), _kv_state(st, clip_val, num_bits, stream), sig)
-            return _precomputed(x, kq, side_k, rows_k, cols, (lo, hi)) if need else kq
+            st.kv = _KVStash(weakref.ref(v), v._version, raws[1], _kv_state(st, clip_val, num_bits, stream), sig)
+            return _node_over_raw(x, raws[0], True)
     return None
 
 
@@ -1224,60 +1262,6 @@ if os.environ.get("LLMQAT_AMD_CONSERVATIVE", "0") == "1":
     conservative(True)
 
 
-class _ReuseQuantizedWeight(torch.autograd.Function):
-    """Autograd node over an already computed (value, row bounds, STE mask) triple of a weight:
-    forward launches nothing, backward is the ordinary STE backward."""
-
-    @staticmethod
-    def forward(ctx, weight, cached, clip_val):
-        y, bounds, mask, rows_cols = cached
-        ctx.rows_cols = rows_cols
-        ctx.clip = _clip_pair(clip_val)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(weight if mask is None else None, bounds, mask)
-        return y.view_as(y)
-
-    @staticmethod
-    @_graph_aware
-    def backward(ctx, grad_output):
-        if grad_output is None:
-            return None, None, None
-        inplace = _INPLACE_WGRAD and _inplace_ok(grad_output)
-        lo, hi = ctx.clip
-        weight, row_bounds, ste_mask = ctx.saved_tensors
-        if ste_mask is not None:
-            rows, cols = ctx.rows_cols
-            return ops.ste_backward_mask(grad_output, lo, hi, row_bounds, ste_mask, rows, cols, inplace=inplace), None, None
-        bounds = row_bounds if grad_output.is_contiguous() and weight.is_contiguous() else None
-        return ops.ste_backward(grad_output, weight, lo, hi, row_bounds=bounds, rows_cols_hint=ctx.rows_cols), None, None
-
-
-class _PrecomputedAct(torch.autograd.Function):
-    """Autograd node over ONE tensor that a multi-tensor launch has already fake-quantized: forward launches nothing, backward is that
-    tensor's own STE launch.  Used where the tensors of a launch must NOT share a node: with the weight cache on (it saves exactly what
-    _SymQuantizerOperand saves in mask mode, so a checkpointed forward that pairs and its recompute that does not record the same
-    tensors), and for the K / V speculation at the unchanged hooks (point 7: a V result nobody asks for must leave no trace in the graph).
-    y may be the reference's fp32 result under autocast (then fp32 gradients come back: the wide backward)."""
-
-    @staticmethod
-    def forward(ctx, x, res, rows, cols, clip):
-        y, side = res     # (inside a tuple: not inputs of this node -- y is the launch's fresh result and becomes the output as it is, so that
-        ctx.rows_cols, ctx.clip, ctx.dtype, ctx.fq_st = (rows, cols), clip, x.dtype, _state().ref     # in-place ops on it work as in the reference)
-        ctx.wide = y.dtype != x.dtype
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(side)
-        return y
-
-    @staticmethod
-    @_graph_aware
-    def backward(ctx, grad_output):
-        if grad_output is None:
-            return None, None, None, None, None
-        _backward_started(ctx.fq_st)
-        (side,) = ctx.saved_tensors
-        return _one_backward(grad_output, side, *ctx.rows_cols, *ctx.clip, ctx.dtype, ctx.wide), None, None, None, None
-
-
 def _one_backward(g, side, rows, cols, lo, hi, dtype, wide):
     """-> the masked gradient of one tensor over its side buffer (wide: the fp32 gradient of the reference's fp32 result under autocast)"""
     if wide:
@@ -1297,13 +1281,6 @@ def _one_backward_from_cpp(g, side, rows, cols, lo, hi, code, wide):
 def _explicit_else(explicit, default, applies):
     """QuantizeLinear's rule for a setting it was not given: the explicit argument, else the process default where it applies to the layer"""
     return explicit if explicit is not None else (default if applies else None)
-
-
-def _precomputed(x, y, side, rows, cols, clip):
-    """a node of x's own over a result some launch has already produced: the C++ one (csrc/fq_autograd_node.cpp::FqOneNode) or _PrecomputedAct"""
-    if _USE_CNODE and x.is_cuda:
-        return _cnode.one_node(x, y, side, rows, cols, clip[0], clip[1], _state().cell)
-    return _PrecomputedAct.apply(x, (y, side), rows, cols, clip)
 
 
 def _node_over(weight, input_, res, code, view_x, need, cell):
@@ -1419,39 +1396,22 @@ class QuantizeLinear(nn.Linear):
         ac = ops.autocast_active(w)
         if not _WEIGHT_CACHE or not w.is_cuda or w.is_inference() or (ac and not ops.autocast_narrow_ok(w)):
             # (an fp16 weight inside autocast(bf16), or the reverse, gets the reference's fp32 result and an fp32 gradient:
-            # the plain node handles both dtypes; the cache's node works in the weight's dtype only)
+            # the cache keeps the operand-dtype result only)
             return _SymQuantizerWeight.apply(w, _CLIP, self.w_bits, self.weight_layerwise)
         key = self._wcache_key()
         ent = self._fq_wcache
         if ent is not None and ent.key == key:
-            cached = ent.value
+            raw = ent.value
             _count("wcache_hit")
             if not _WEIGHT_CACHE_PERSISTENT:
                 self._fq_wcache = None  # second use within the step (the checkpoint recompute): done with it
         else:
-            rc = ops.rows_cols(tuple(w.shape), self.weight_layerwise)
-            bounds = mask = None
-            if ac:  # autocast arithmetic, result rounded once to the weight dtype (see _SymQuantizerOperand)
-                y, side, rows, _, got = ops.sym_forward_autocast(w, self.w_bits, self.weight_layerwise, wide=False,
-                                                                 train=None if _BACKWARD_MODE == "plain" else _BACKWARD_MODE)
-                if got == "mask":
-                    bounds, mask = ops.split_side(side, rows)
-                elif got == "bounds":
-                    bounds = side
-            else:
-                res = ops.quantize_train("sym", w, self.w_bits, self.weight_layerwise, -2.0, 2.0) if _BACKWARD_MODE == "mask" else None
-                if res is not None:
-                    y, bounds, mask = res
-                elif _BACKWARD_MODE == "plain":
-                    y = ops.sym_quantize(w, self.w_bits, self.weight_layerwise)
-                else:
-                    y, bounds = ops.sym_quantize(w, self.w_bits, self.weight_layerwise, want_bounds=True)
-            cached = _QWeight(y, bounds, mask, rc)
-            self._fq_wcache = _WCache(key, cached)
+            # what _SymQuantizerWeight would compute, as plain data; the side outputs are recorded even without grad (need_grad=True):
+            # the first pass of a reentrant checkpoint runs under no_grad, and the recompute pass's backward needs them
+            raw = _compute_raw("sym", w, _CLIP, ops.bits_arg(self.w_bits), self.weight_layerwise, True, True)
+            self._fq_wcache = _WCache(key, raw)
             _count("wcache_fill")
-        if torch.is_grad_enabled() and w.requires_grad:
-            return _ReuseQuantizedWeight.apply(w, cached, _CLIP)  # launches nothing; backward = the ordinary STE
-        return cached.y
+        return _node_over_raw(w, raw, False, True)  # launches nothing; backward = the ordinary STE, the gradient masked where it stands
 
     def _new_plan(self, input_, settings):
         """What depends only on shapes / dtypes / device and the module's settings, decided once per module and input shape: whether the
@@ -1553,14 +1513,14 @@ class QuantizeLinear(nn.Linear):
         if built_in_cpp:
             return wq, xq
         if wkey is not None:
-            # bounds + mask are recorded even without grad (the recompute pass's backward needs them), and the results are
-            # wrapped in the SAME nodes the recompute pass will build (_ReuseQuantizedWeight for the weight, a side-buffer
-            # node for the input), so non-reentrant checkpointing sees identical saved tensors in both passes
-            cached = _QWeight(wq, *ops.split_side(side_w, rows_w), ops.rows_cols(tuple(weight.shape), False))
-            self._fq_wcache = _WCache(wkey, cached)
+            # the side buffer is recorded even without grad (the recompute pass's backward needs it), and the results are wrapped in
+            # the SAME nodes the recompute pass will build (the cache's node over the weight's record, one over a side buffer for
+            # the input), so non-reentrant checkpointing sees identical saved tensors in both passes
+            raw_w = _Raw(wq, "mask", (side_w,), (-2.0, 2.0), (rows_w, cols))
+            self._fq_wcache = _WCache(wkey, raw_w)
             _count("wcache_fill")
-            return (_ReuseQuantizedWeight.apply(weight, cached, _CLIP) if need_w else wq,
-                    _precomputed(input_, xq, side_x, rows_x, cols, (-2.0, 2.0)) if need_x else xq)
+            raw_x = _Raw(xq, "mask", (side_x,), (-2.0, 2.0), (rows_x, cols), input_.dtype) if need_x else _Raw(xq, "none")
+            return _node_over_raw(weight, raw_w, False, True), _node_over_raw(input_, raw_x, True)
         # (on the general route with sharing the remembered xq stays plain data: the node gets a tensor of its own over the same memory)
         return _node_over(weight, input_, res, ops._DTYPES[weight.dtype], share and not planned, need_w or need_x, None)
 

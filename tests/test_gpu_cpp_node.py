@@ -276,7 +276,7 @@ def test_gradient_accumulation_over_steps(pkg):
 @pytest.mark.parametrize("autocast", [False, True])
 def test_kv_hooks_through_the_one_tensor_node(pkg, autocast):
     """k_proj, v_proj and the two unchanged KV hooks (modeling_llama_quant.py:317-327): one forward launch for K and V, one node EACH -- the
-    C++ one-tensor node (fp32 gradients in under autocast: the wide backward) or _PrecomputedAct -- == the eager chain; incl. a backward that
+    C++ one-tensor node (fp32 gradients in under autocast: the wide backward) or _SharedAct --== the eager chain; incl. a backward that
     is itself recorded (handed back to the Python node's code)"""
     from llm_qat_amd import utils_quant as U
     res = {}

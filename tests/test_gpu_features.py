@@ -1309,7 +1309,7 @@ def _inplace_guard_body(pkg, U, QuantizeLinear, node):
     del alias
     assert U._inplace_ok(g)
     # the guarded path engages for EVERY weight node, not only the pair node: _SymQuantizerWeight (operands quantized separately)
-    # and _ReuseQuantizedWeight (weight cache), and llm_qat_amd.stats() counts it
+    # and the weight cache's _SharedAct, and llm_qat_amd.stats() counts it
     for setup, teardown in (((lambda: pkg.pair_operands(False)), (lambda: pkg.pair_operands(True))),
                             ((lambda: pkg.enable_weight_quant_cache(True)), (lambda: pkg.enable_weight_quant_cache(False)))):
         setup()

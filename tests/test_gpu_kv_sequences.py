@@ -16,7 +16,7 @@ import tiny_llama as TL  # noqa: E402
 
 @pytest.fixture(autouse=True, params=["c++", "python"])
 def node(request):
-    """every test of this file with either kind of autograd node behind K and V (csrc/fq_autograd_node.cpp::FqOneNode / _PrecomputedAct)"""
+    """every test of this file with either kind of autograd node behind K and V (csrc/fq_autograd_node.cpp::FqOneNode / _SharedAct)"""
     import llm_qat_amd
     assert llm_qat_amd.cpp_node(request.param == "c++") == (request.param == "c++"), llm_qat_amd.host_node()
     yield request.param

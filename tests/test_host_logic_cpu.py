@@ -161,3 +161,68 @@ def test_a_backward_lets_go_of_what_its_forward_thread_remembered(UQ):
     del a, b
     gc.collect()
     assert all(r() is None for r in held), "the shared activation outlived its forward pass"
+
+
+def _siblings_step(Q):
+    """two sibling QuantizeLinear(64, 32) over one [3, 64] input that needs a gradient -> (outputs, gradients)"""
+    ms = []
+    for seed in (0, 1):
+        m = Q.QuantizeLinear(64, 32, w_bits=4, a_bits=8)
+        with torch.no_grad():
+            m.weight.copy_(torch.randn(32, 64, generator=torch.Generator().manual_seed(80 + seed)) * 0.4)
+        ms.append(m)
+    x = (torch.randn(3, 64, generator=torch.Generator().manual_seed(11)) * 1.5).requires_grad_(True)
+    return ms, x
+
+
+def test_remembered_records_are_plain_data(UQ):
+    """a `_Raw` is made with grad mode off: what `_ThreadState.acts` keeps carries no graph (it pinned the op chain's intermediates and the
+    input until the entry was replaced), a sibling still finds it, and everything equals the conservative run bit for bit"""
+    import llm_qat_amd
+    llm_qat_amd.conservative(True)
+    ms, x = _siblings_step(UQ)
+    outs = [m(x) for m in ms]
+    (outs[0].sum() + 2 * outs[1].sum()).backward()
+    want = [o.detach() for o in outs] + [x.grad] + [m.weight.grad for m in ms]
+    llm_qat_amd.conservative(False)
+    llm_qat_amd.reset_learned_state()
+    llm_qat_amd.stats(reset=True)
+    ms, x = _siblings_step(UQ)
+    a = ms[0](x)
+    acts = UQ._state().acts
+    assert acts, "nothing was remembered"
+    for ent in acts.values():
+        assert ent[3].out.grad_fn is None and ent[3].out.requires_grad is False, ent[3].out
+    b = ms[1](x)
+    st = llm_qat_amd.stats()
+    assert st.get("act_share_miss") == 1 and st.get("act_share_hit") == 1, st
+    for ent in UQ._state().acts.values():
+        assert ent[3].out.grad_fn is None and ent[3].out.requires_grad is False, ent[3].out
+    (a.sum() + 2 * b.sum()).backward()
+    assert same(want, [a.detach(), b.detach(), x.grad] + [m.weight.grad for m in ms])
+
+
+@pytest.mark.parametrize("kind", ["sym", "asym"])
+def test_a_quantizers_record_is_plain_data(UQ, kind):
+    """the same for SymQuantizer.apply / AsymQuantizer.apply on a [3, 64] tensor: the record made outside a Function.forward has no graph,
+    nothing with one is remembered, and result and gradient equal the conservative run bit for bit"""
+    import llm_qat_amd
+    quantizer = UQ.SymQuantizer if kind == "sym" else UQ.AsymQuantizer
+    clip = torch.tensor([-2.0, 2.0])
+
+    def run():
+        x = (torch.randn(3, 64, generator=torch.Generator().manual_seed(12)) * 1.5).requires_grad_(True)
+        y = quantizer.apply(x, clip, 8, False)
+        (y * torch.arange(64.0)).sum().backward()
+        return [y.detach(), x.grad]
+
+    llm_qat_amd.conservative(True)
+    want = run()
+    llm_qat_amd.conservative(False)
+    llm_qat_amd.reset_learned_state()
+    x = (torch.randn(3, 64, generator=torch.Generator().manual_seed(12)) * 1.5).requires_grad_(True)
+    raw = UQ._compute_raw(kind, x, clip, 8, False, False, True)
+    assert raw.out.grad_fn is None and raw.out.requires_grad is False
+    assert same(want, run())
+    for ent in UQ._state().acts.values():
+        assert ent[3].out.grad_fn is None and ent[3].out.requires_grad is False
