@@ -30,6 +30,8 @@ EXPORTS = (
     "fq_mx_fwd_rot", "fq_mx_export_rot", "fq_block_rotate",
     "fq_mx_fwd_ex", "fq_mx_export_ex", "fq_mx_ste_bwd",
 )
+# every symbol include/llmqat_fakequant_train.h declares (the fqt_ family: the training-side entry points, outside the recorded set above)
+TRAIN_EXPORTS = ("fqt_mx_fwd_cols",)
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -151,6 +153,8 @@ def _bind(L):
     L.fq_mx_ste_bwd.restype = i32
     L.fq_mx_gemm.argtypes = [vp, vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp]
     L.fq_mx_gemm.restype = i32
+    L.fqt_mx_fwd_cols.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp]
+    L.fqt_mx_fwd_cols.restype = i32
     return L
 
 

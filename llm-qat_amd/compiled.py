@@ -197,6 +197,22 @@ def _mx_rule_setup(ctx, inputs, output):
 mx_fake_quant_rule_op.register_autograd(lambda ctx, g: (mx_block_rotate_op(g) if ctx.rotate else g, None, None, None), setup_context=_mx_rule_setup)
 
 
+# ops.mx_quantize_axis(axis=-2): the blocks run down the columns; identity gradient, nothing saved
+@torch.library.custom_op("llmqat_amd::mx_fake_quant_cols", mutates_args=(), device_types="cuda")
+def mx_fake_quant_cols_op(x: torch.Tensor, fmt: str, scale_rule: str) -> torch.Tensor:
+    return ops.mx_quantize_axis(x, fmt, scale_rule=scale_rule, axis=-2)
+
+
+@mx_fake_quant_cols_op.register_fake
+def _(x, fmt, scale_rule):
+    ops.check_mx_cols(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule)
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+mx_fake_quant_cols_op.register_autograd(lambda ctx, g: (g, None, None))
+
+
 # ops.mx_ste_backward: the gradient under the saturation bitmap (rotate: times R, same launch)
 @torch.library.custom_op("llmqat_amd::mx_ste_backward", mutates_args=(), device_types="cuda")
 def mx_ste_backward_op(g: torch.Tensor, mask: torch.Tensor, rotate: bool) -> torch.Tensor:

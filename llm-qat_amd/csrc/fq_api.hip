@@ -1,6 +1,7 @@
 // fq_api.hip -- host side of the C ABI declared in include/llmqat_fakequant.h:
 // argument validation, kernel selection, launches.  No allocation, no synchronisation.
 #include "../../include/llmqat_fakequant.h"
+#include "../../include/llmqat_fakequant_train.h"
 
 #include <hip/hip_runtime.h>
 
@@ -536,6 +537,29 @@ FQ_API int fq_mx_ste_bwd(const void* g, const void* mask, void* gx, int64_t rows
     const MxSteArgs a{g, (const uint32_t*)mask, gx, nvec, nvec * 16 >= NT_LOAD_MIN_BYTES ? 1 : 0};
     hipStream_t st = (hipStream_t)stream;
     return by_dtype(dtype, [&](auto dt) { return launch_mx_ste<decltype(dt)::value>(rot, a, st); });
+}
+
+// include/llmqat_fakequant_train.h.  The checks are mx_checks' in mx_checks' order, with the block along the rows: rows % 32 in place of
+// cols % 32, whole 16-byte strips per row, and the grid counted in tiles.  Every check comes before any HIP call.
+FQ_API int fqt_mx_fwd_cols(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, int flags, void* stream) {
+    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
+    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
+    if (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
+    if (flags & ~FQ_MX_FLAG_CEIL) return fail(FQ_ERR_ARG, "flag bits 0x%x: the column axis takes FQ_MX_FLAG_CEIL only", (unsigned)(flags & ~FQ_MX_FLAG_CEIL));
+    if (rows < 0 || cols < 0) return fail(FQ_ERR_SHAPE, "negative shape rows=%lld cols=%lld", (long long)rows, (long long)cols);
+    if (rows % 32 != 0) return fail(FQ_ERR_SHAPE, "rows=%lld is not a multiple of the 32-element MX block", (long long)rows);
+    if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
+    if (rows == 0 || cols == 0) return ok();
+    if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
+    if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+    if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+    const int64_t row_bytes = cols * esize_of(dtype);
+    if (row_bytes % 16 != 0) return fail(FQ_ERR_UNSUPPORTED, "cols=%lld: a row must be whole 16-byte vectors", (long long)cols);
+    const int64_t ncs = row_bytes / 16, nct = (ncs + MXC_TILE_STRIPS - 1) / MXC_TILE_STRIPS, row_tiles = rows / MXC_TILE_ROWS;
+    if (row_tiles > 0x7FFFFFFF / nct) return fail(FQ_ERR_UNSUPPORTED, "%lld x %lld tiles exceed one launch's grid", (long long)row_tiles, (long long)nct);
+    const MxColsArgs a{x, y, ncs, (uint32_t)nct, rows * row_bytes >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    hipStream_t st = (hipStream_t)stream;
+    return by_dtype(dtype, [&](auto dt) { return launch_mx_cols<decltype(dt)::value>((flags & FQ_MX_FLAG_CEIL) != 0, a, kMxFmts[fmt], row_tiles, st); });
 }
 
 // Every check comes before any HIP call.

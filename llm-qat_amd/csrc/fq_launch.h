@@ -230,6 +230,15 @@ template <int DT> FQ_HIDDEN int launch_mx_ste(bool rot, MxSteArgs a, hipStream_t
 // kind MX_ROT (with rot): y = x R alone (f, ceil and mask unused).  All four are template parameters of mx_kernel, so every entry point
 // runs the instantiation it always ran.
 template <int DT> FQ_HIDDEN int launch_mx(int kind, bool rot, bool ceil, bool mask, MxArgs a, MxFmt f, hipStream_t st);
+// MX forward with the blocks running down the columns (fq_mx_cols.h / fq_mx_cols.hip): x, y contiguous [rows, cols], rows a multiple of 32
+struct MxColsArgs {
+    const void* x;
+    void* y;
+    int64_t ncs;     // 16-byte column strips of a row: cols * esize / 16
+    uint32_t nct;    // column tiles: ncs in units of MXC_TILE_STRIPS, rounded up
+    int ntl;         // non-temporal loads, as MxArgs
+};
+template <int DT> FQ_HIDDEN int launch_mx_cols(bool ceil, MxColsArgs a, MxFmt f, int64_t row_tiles, hipStream_t st);
 // MX block-scaled GEMM (fq_mx_gemm.h / fq_mx_gemm.hip): out[m, n] = sum_k A[m, k] * W[n, k] over two MX exports
 struct MxGemmArgs {
     const uint8_t* we;   // W: [N, K] element codes, E8M0 scales [N, K / 32]

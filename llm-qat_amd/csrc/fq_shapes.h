@@ -60,4 +60,13 @@ template <class F> inline void by_group_shape(int64_t nvec, F&& f) {
     else f(Const<1024>{}, Const<8>{});
 }
 
+
+// Tile of the column-block MX kernel (fq_mx_cols.h): a workgroup covers MXC_TILE_ROWS rows (one MX block down every column) by
+// MXC_TILE_STRIPS 16-byte column strips (16 / esize columns each); a wave holds MXC_WAVE_STRIPS of the strips, its MXC_ROW_GROUPS
+// quarter-waves MXC_TILE_ROWS / MXC_ROW_GROUPS rows each.  tests/test_gpu_mx_cols.py reads these four lines.
+constexpr int MXC_TILE_ROWS = 32;
+constexpr int MXC_TILE_STRIPS = 64;
+constexpr int MXC_WAVE_STRIPS = 16;
+constexpr int MXC_ROW_GROUPS = 4;
+
 }  // namespace fq

@@ -1012,7 +1012,7 @@ MX_ROTATE = 64
 # element, bit i & 7 of byte i >> 3 for flat element i, 0 where saturation changed the rounded value; mx_ste_backward applies it.
 MX_SCALE_RULES = ("floor", "ceil")
 mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm_launch": 0, "mx_gemm_skinny": 0, "mx_gemm_tiled": 0,
-             "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0}
+             "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0, "mx_cols_launch": 0}
 
 
 def check_mx(shape, fmt):
@@ -1067,6 +1067,66 @@ def mx_rotate(x):
         _lib.check(_launch(x, _lib.lib().fq_block_rotate, x.data_ptr(), y.data_ptr(), rows, cols, dt), "mx_rotate")
         mx_counts["mx_rotate_launch"] += 1
     return y
+
+
+def check_mx_axis(ndim, axis, what="mx_quantize"):
+    """-> -1 or -2, the axis the MX blocks run along; ValueError for anything but the last two axes (negative or not) of the tensor"""
+    if isinstance(axis, int) and not isinstance(axis, bool):
+        if axis in (-1, ndim - 1):
+            return -1
+        if axis in (-2, ndim - 2) and ndim >= 2:
+            return -2
+        if axis == -2:
+            raise ValueError(f"{what}: axis=-2 needs a tensor with at least two dimensions, got {ndim}")
+    raise ValueError(f"{what}: axis={axis!r}: MX blocks run along the last axis (-1) or the one before it (-2)")
+
+
+def check_mx_cols(shape, fmt, what="mx_quantize"):
+    """-> the format's C code after the argument checks of the column axis: at least two dimensions, shape[-2] a multiple of 32 (the last
+    dimension is free)"""
+    code = MX_FORMATS.get(fmt) if isinstance(fmt, str) else None
+    if code is None:
+        raise ValueError(f"unknown MX format {fmt!r}: one of {', '.join(MX_FORMATS)}")
+    if len(shape) < 2:
+        raise ValueError(f"{what}: axis=-2 needs a tensor with at least two dimensions, got {len(shape)}")
+    if shape[-2] % MX_BLOCK:
+        raise ValueError(f"{what}: axis=-2 needs a second-to-last dimension that is a multiple of {MX_BLOCK}, got {shape[-2]}")
+    return code
+
+
+def _mx_quantize_cols(x, fmt, scale_rule):
+    """mx_quantize_axis along axis -2: one launch of the column kernel on a contiguous, 16-byte aligned tensor whose rows
+    are whole 16-byte vectors; anything else goes through the row kernel on the transposed copy (same values; mx_copy_route)."""
+    flags = check_mx_scale_rule(scale_rule)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
+    code = check_mx_cols(tuple(x.shape), fmt)
+    dt = _prep(x, "mx_quantize")
+    if dt == _lib.DTYPE_F64:
+        raise NotImplementedError("mx_quantize: float64 is not served by the MX formats (float32, bfloat16, float16 are)")
+    cols = x.shape[-1]
+    if not x.is_contiguous() or x.data_ptr() & 15 or (cols * x.element_size()) % 16:
+        mx_counts["mx_copy_route"] += 1
+        return mx_quantize(x.transpose(-1, -2).contiguous(), fmt, scale_rule=scale_rule).transpose(-1, -2).contiguous()
+    y = torch.empty_like(x)
+    if x.numel():
+        rc = _launch(x, _lib.lib().fqt_mx_fwd_cols, x.data_ptr(), y.data_ptr(), x.numel() // cols, cols, code, dt, flags)
+        _lib.check(rc, "mx_quantize")
+        mx_counts["mx_cols_launch"] += 1
+    return y
+
+
+def mx_quantize_axis(x, fmt, rotate=False, scale_rule="floor", return_mask=False, axis=-1):
+    """mx_quantize with a choice of the axis the blocks run along: -1 (or ndim - 1) is mx_quantize itself; -2 (or ndim - 2): the blocks run
+    down the columns -- 32 consecutive elements of the second-to-last dimension (a multiple of 32; the last one is free) share a scale;
+    the result is contiguous and equals the last-axis result of the transposed tensor, transposed back, bit for bit.  One launch of its
+    own kernel; the rotation and the mask are not served there (ValueError).  (A function of its own: mx_quantize's parameter list is
+    pinned by tests/test_mx_rules_cpu.py.)"""
+    if isinstance(x, torch.Tensor) and check_mx_axis(x.dim(), axis) == -2:
+        if rotate or return_mask:
+            raise ValueError(f"mx_quantize: the column axis (axis=-2) does not serve {'rotate' if rotate else 'return_mask'}=True yet")
+        return _mx_quantize_cols(x, fmt, scale_rule)
+    return mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, return_mask=return_mask)
 
 
 def mx_quantize(x, fmt, rotate=False, scale_rule="floor", return_mask=False):

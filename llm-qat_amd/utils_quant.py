@@ -115,6 +115,8 @@ def stats(reset=False):
                                          MX quantizer); the fused rotated forms count as mx_launch / mx_export_launch
       mx_mask_launch / mx_ste_launch     MX forwards that also wrote the saturation bitmap (ops.mx_quantize(return_mask=True), mx_ste="clip"; each
                                          is an mx_launch too) and masked straight-through backwards launched (ops.mx_ste_backward)
+      mx_cols_launch                     MX forwards along axis -2 served by the column kernel (ops.mx_quantize_axis(axis=-2), the backward of
+                                         mx_backward_format); an input it does not take goes through the row kernel: mx_copy_route + mx_launch
       mx_gemm_launch / mx_gemm_skinny / mx_gemm_tiled
                                          MX block-scaled GEMMs (ops.mx_matmul, MXLinear) launched, and which kernel served them (M <= 32: skinny)
       cpp_pair_forward / cpp_weight_forward / cpp_pair_backward / cpp_one_backward / cpp_slow_backward
@@ -443,7 +445,7 @@ def group_quantize(x, clip_val, num_bits, group_size, symmetric=True):
 
 # what the QuantizeLinears constructed from now on take for the settings they are not given explicitly (the default_* setters below):
 # (weight, activation) group sizes, (weight, activation) MX formats, and the MX operands' rotation, scale rule and gradient
-_DEFAULTS = {"groups": (None, None), "mx": (None, None), "mx_rotate": False, "mx_scale_rule": "floor", "mx_ste": "identity"}
+_DEFAULTS = {"groups": (None, None), "mx": (None, None), "mx_rotate": False, "mx_scale_rule": "floor", "mx_ste": "identity", "mx_backward": None}
 
 
 def _set_default(name, value):
@@ -505,6 +507,20 @@ class _MXQuantizer(torch.autograd.Function):
         return ops.mx_ste_backward(grad_output, mask, ctx.rotate), None, None, None, None
 
 
+class _MXColsQuantizer(torch.autograd.Function):
+    """MX fake quantization with the blocks running down the columns (ops.mx_quantize_axis(axis=-2)), straight-through:
+    nothing is saved and the gradient is the incoming tensor itself."""
+
+    @staticmethod
+    def forward(ctx, x, fmt, scale_rule):
+        ctx.set_materialize_grads(False)
+        return ops.mx_quantize_axis(x, fmt, scale_rule=scale_rule, axis=-2)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return grad_output, None, None
+
+
 MX_STE_MODES = ("identity", "clip")
 
 
@@ -550,6 +566,26 @@ def mx_quantize(x, fmt, rotate=False, scale_rule="floor", ste="identity"):
     return _mx_apply(x, fmt, bool(rotate), scale_rule, ste)
 
 
+def mx_quantize_axis(x, fmt, rotate=False, scale_rule="floor", ste="identity", axis=-1):
+    """mx_quantize with a choice of the axis the blocks run along: -1 (or ndim - 1) is mx_quantize itself.  -2 (or ndim - 2): the blocks
+    run down the columns -- 32 consecutive elements of the second-to-last dimension (a multiple of 32; the last one is free) share a
+    scale, which is what a product that contracts over that axis needs (the backward GEMMs of a linear layer).  One launch, a contiguous
+    result, the identity gradient; the rotation and ste="clip" are not served along that axis (ValueError).  (A function of its own:
+    mx_quantize's parameter list is pinned by tests/test_mx_rules_cpu.py.)"""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
+    if ops.check_mx_axis(x.dim(), axis) == -1:
+        return mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, ste=ste)
+    ops.check_mx_cols(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule)
+    _check_mx_ste(ste)
+    if rotate or ste == "clip":
+        raise ValueError(f"mx_quantize: the column axis (axis=-2) does not serve {'rotate=True' if rotate else 'ste=clip'} yet")
+    if torch.compiler.is_compiling():
+        return compiled.mx_fake_quant_cols_op(x, fmt, scale_rule)
+    return _MXColsQuantizer.apply(x, fmt, scale_rule)
+
+
 def default_mx_formats(weight=None, act=None):
     """MX formats the QuantizeLinears constructed from now on take for the operands they quantize (w_bits < 32 / a_bits < 32, not
     layerwise, no explicit group size) when their own weight_format / act_format are not given (None: the integer quantizers).  Lets
@@ -579,6 +615,66 @@ def default_mx_ste(mode):
     is not given.  Layers without an MX operand are not affected.  -> the previous mode."""
     _check_mx_ste(mode, "default_mx_ste")
     return _set_default("mx_ste", mode)
+
+
+def default_mx_backward_format(fmt):
+    """The MX format the QuantizeLinears constructed from now on run their backward GEMMs in (mx_backward_format) when their own is not
+    given; None: the backward GEMMs stay in the tensors' dtype.  Applies only to layers that qualify: both operands in an MX format, no
+    rotation, the identity gradient, out_features a multiple of 32.  -> the previous format."""
+    if fmt is not None and fmt not in ops.MX_FORMATS:
+        raise ValueError(f"unknown MX format {fmt!r}: one of {', '.join(ops.MX_FORMATS)}")
+    return _set_default("mx_backward", fmt)
+
+
+def _mx_backward_refusal(layer):
+    """why `layer` cannot run its backward GEMMs on MX operands, or None"""
+    if layer.weight_format is None or layer.act_format is None:
+        return "it needs both operands in an MX format (weight_format and act_format)"
+    if layer.mx_rotate:
+        return "the column axis does not serve the rotation yet (mx_rotate must be False)"
+    if layer.mx_ste != "identity":
+        return 'the column axis does not serve the clip gradient yet (mx_ste must be "identity")'
+    if layer.out_features % ops.MX_BLOCK:
+        return f"dX = dY W contracts over out_features, which must be a multiple of {ops.MX_BLOCK}, got {layer.out_features}"
+    return None
+
+
+class _MXLinearBackward(torch.autograd.Function):
+    """F.linear(Qr(x), Qr(W)) whose two backward GEMMs run on MX-quantized operands, each blocked along its contraction axis (DESIGN.md
+    section 17; Qr / Qc: ops.mx_quantize / ops.mx_quantize_axis(axis=-2), format fb, the layer's scale rule):
+        dX = Qr(g) Qc(W)         both blocked along `out`
+        dW = Qc(g)^T Qc(x)       both blocked along the tokens (zero rows pad them to a multiple of 32: no amax and no sum changes)
+    The operands quantized backward are the ORIGINAL x and W cast to the output's dtype, as the microscaling emulation libraries do, so x
+    and W themselves are what is saved.  An operand of a gradient nobody needs is not quantized."""
+
+    @staticmethod
+    def forward(ctx, x, w, weight_format, act_format, scale_rule, fb):
+        ctx.cfg = (fb, scale_rule)
+        ctx.save_for_backward(x, w)
+        wq = ops.mx_quantize(w, weight_format, scale_rule=scale_rule)
+        return nn.functional.linear(ops.mx_quantize(x, act_format, scale_rule=scale_rule), wq)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        fb, rule = ctx.cfg
+        need_x, need_w = ctx.needs_input_grad[:2]
+        gx = gw = None
+        with torch.autocast("cuda", enabled=False):   # every operand is cast to d explicitly
+            d = g.dtype
+            g2 = g.reshape(-1, w.shape[0]).contiguous()
+            if need_x:
+                gx2 = torch.matmul(ops.mx_quantize(g2, fb, scale_rule=rule), ops.mx_quantize_axis(w.to(d), fb, scale_rule=rule, axis=-2))
+                gx = gx2.reshape(x.shape).to(x.dtype)
+            if need_w:
+                x2 = x.reshape(-1, w.shape[1]).to(d)
+                pad = -g2.shape[0] % ops.MX_BLOCK
+                if pad:
+                    ops.mx_counts["mx_copy_route"] += 1
+                    g2, x2 = nn.functional.pad(g2, (0, 0, 0, pad)), nn.functional.pad(x2, (0, 0, 0, pad))
+                gw = torch.matmul(ops.mx_quantize_axis(g2, fb, scale_rule=rule, axis=-2).t(), ops.mx_quantize_axis(x2, fb, scale_rule=rule, axis=-2)).to(w.dtype)
+        return gx, gw, None, None, None, None
 
 
 class _LowBitWeight(torch.autograd.Function):
@@ -1305,10 +1401,11 @@ class QuantizeLinear(nn.Linear):
     mx_rotate = False          # both operands are rotated along K before they are quantized: F.linear(Q(x R), Q(W R)) (a plain attribute)
     mx_scale_rule = "floor"    # shared-exponent rule of the MX operands ("ceil": nothing saturates) and their gradient ("clip": zero where
     mx_ste = "identity"        # saturation changed the element); plain attributes
+    mx_backward_format = None  # an MX format: the two backward GEMMs run on operands quantized along their contraction axes (a plain attribute)
 
     def __init__(self, *kargs, symmetric=True, bias=False, w_bits=32, a_bits=32, act_layerwise=False,
                  weight_layerwise=False, weight_group_size=None, act_group_size=None, weight_format=None, act_format=None, mx_rotate=None,
-                 mx_scale_rule=None, mx_ste=None):
+                 mx_scale_rule=None, mx_ste=None, mx_backward_format=None):
         super().__init__(*kargs, bias=False)  # `bias` is accepted and ignored, as in the reference (:176)
         self.w_bits = w_bits
         self.a_bits = a_bits
@@ -1349,6 +1446,17 @@ class QuantizeLinear(nn.Linear):
                     raise ValueError(f"{name} applies to MX operands: this layer has neither weight_format nor act_format")
             if any_mx:
                 setattr(self, name, _explicit_else(given, _DEFAULTS[name], True))
+        # the backward GEMMs in an MX format: an explicit format needs a layer that qualifies (_mx_backward_refusal); the process default
+        # (default_mx_backward_format) applies to the layers that do
+        why = _mx_backward_refusal(self)
+        if mx_backward_format is not None:
+            if mx_backward_format not in ops.MX_FORMATS:
+                raise ValueError(f"unknown MX format {mx_backward_format!r}: one of {', '.join(ops.MX_FORMATS)}")
+            if why is not None:
+                raise ValueError(f"mx_backward_format: {why}")
+            self.mx_backward_format = mx_backward_format
+        elif _DEFAULTS["mx_backward"] is not None and why is None:
+            self.mx_backward_format = _DEFAULTS["mx_backward"]
         # group sizes: an explicit argument is checked and kept; the process default (default_group_sizes) applies where it means something
         # (an operand without an MX format, of a bit width the group quantizer serves, not layerwise)
         dw, da = _DEFAULTS["groups"]
@@ -1568,6 +1676,9 @@ class QuantizeLinear(nn.Linear):
 
     def _forward_compiled(self, input_):
         """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
+        if self.mx_backward_format is not None:
+            raise NotImplementedError("QuantizeLinear: mx_backward_format is not served while torch.compile traces (the compiled module path "
+                                      "keeps the backward GEMMs in the tensors' dtype): run this layer eagerly or leave mx_backward_format unset")
         route, weight = self._weight_route(), self.weight
         if route == "mx":   # llmqat_amd::mx_fake_quant (identity gradient) / mx_fake_quant_rot (Q(W R), gradient g R), or the section 16 ops
             weight = _mx_apply(weight, self.weight_format, self.mx_rotate, self.mx_scale_rule, self.mx_ste)
@@ -1591,7 +1702,16 @@ class QuantizeLinear(nn.Linear):
         node, weight cache or activation sharing; an operand without a format keeps its integer quantizer (uncached, unshared).
         mx_rotate (both operands have a format: the constructor's check): F.linear(Q(x R), Q(W R)), still one launch per operand forward,
         and one rotate launch per operand gradient.
-        mx_ste="clip": each MX operand's forward launch also writes its saturation bitmap, and its gradient is one masked launch."""
+        mx_ste="clip": each MX operand's forward launch also writes its saturation bitmap, and its gradient is one masked launch.
+        mx_backward_format: the same two forward launches inside one node whose backward GEMMs run on MX operands (_MXLinearBackward)."""
+        if self.mx_backward_format is not None:
+            why = _mx_backward_refusal(self)   # (the settings are plain attributes: one may have been assigned since the constructor)
+            if why is not None:
+                raise ValueError(f"mx_backward_format: {why}")
+            out = _MXLinearBackward.apply(input_, self.weight, self.weight_format, self.act_format, self.mx_scale_rule, self.mx_backward_format)
+            if self.bias is not None:
+                out += self.bias.view(1, -1).expand_as(out)
+            return out
         route, weight = self._weight_route(), self.weight
         if route == "low" and self.weight_group_size is not None:
             route = "group"    # (a group size ASSIGNED to a 1-/2-bit layer -- the constructor refuses one: this path alone has always honoured it)
