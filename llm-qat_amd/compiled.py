@@ -78,51 +78,28 @@ def fake_quant(kind, x, clip_val, num_bits, layerwise, narrow=False):
     return fake_quant_op(x, clip_val, _KINDS[kind], int(num_bits), bool(layerwise), mode)
 
 
-# MX block-scaled fake quantization (ops.mx_quantize): the straight-through identity gradient, nothing saved
-@torch.library.custom_op("llmqat_amd::mx_fake_quant", mutates_args=(), device_types="cuda")
-def mx_fake_quant_op(x: torch.Tensor, fmt: str) -> torch.Tensor:
-    return ops.mx_quantize(x, fmt)
+# ---- MX block-scaled fake quantization (DESIGN.md sections 13, 15, 16, 17).  One op per combination of options (the names a traced graph
+# holds); behind them one fake implementation, one straight-through gradient and one dispatcher (mx_fake_quant) -------------------------
+def _mx_quant_fake(x, fmt, rotate=False, scale_rule="floor", mask=False, axis=-1):
+    """the quantizer ops' fake implementation: ops.mx_quantize_axis's checks on shapes alone -> y (, the numel / 8 bytes of the bitmap)"""
+    if axis == -2:
+        ops.check_mx_cols(tuple(x.shape), fmt)
+    else:
+        ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule)
+    if rotate:
+        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    return (y, x.new_empty((x.numel() // 8,), dtype=torch.uint8)) if mask else y
 
 
-@mx_fake_quant_op.register_fake
-def _(x, fmt):
-    ops.check_mx(tuple(x.shape), fmt)
-    return torch.empty_like(x, memory_format=torch.contiguous_format)
+def _mx_straight_through(op, rotate=None):
+    """the gradient of a quantizer op without a bitmap: the incoming one itself, times R (one rotate launch) where the op rotates -- a
+    constant, or None: its `rotate` input says; nothing saved"""
+    def setup(ctx, inputs, output):
+        ctx.rotate, ctx.rest = (inputs[2] if rotate is None else rotate), (None,) * (len(inputs) - 1)
 
-
-mx_fake_quant_op.register_autograd(lambda ctx, g: (g, None))
-
-
-
-# MX block-scaled GEMM (ops.mx_matmul) on the tensors of the two exports; inference only: no autograd formula is registered, so asking
-# for a gradient through it raises
-@torch.library.custom_op("llmqat_amd::mx_matmul", mutates_args=(), device_types="cuda")
-def mx_matmul_op(a_elems: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, w_elems: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
-                 a_shape: List[int], out_dtype: torch.dtype) -> torch.Tensor:
-    return ops.mx_matmul_tensors(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, tuple(a_shape), out_dtype)
-
-
-@mx_matmul_op.register_fake
-def _(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, a_shape, out_dtype):
-    _, N, _ = ops.check_mx_matmul(tuple(a_shape), a_fmt, (w_scales.shape[0], w_scales.shape[1] * ops.MX_BLOCK), w_fmt, out_dtype)
-    return a_elems.new_empty(tuple(a_shape[:-1]) + (N,), dtype=out_dtype)
-
-
-# ops.mx_export as an op: (elements, scales) of x in `fmt` (mxfp4 / mxfp8_*)
-@torch.library.custom_op("llmqat_amd::mx_export", mutates_args=(), device_types="cuda")
-def mx_export_op(x: torch.Tensor, fmt: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    e = ops.mx_export(x, fmt)
-    return e.elements, e.scales
-
-
-@mx_export_op.register_fake
-def _(x, fmt):
-    ops.check_mx(tuple(x.shape), fmt)
-    if fmt not in ops.MX_GEMM_FORMATS:
-        raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
-    lead, cols = tuple(x.shape[:-1]), x.shape[-1]
-    return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
-            x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))
+    op.register_autograd(lambda ctx, g: (mx_block_rotate_op(g) if ctx.rotate else g,) + ctx.rest, setup_context=setup)
 
 
 # The block-Hadamard rotation (ops.mx_rotate): R is symmetric and its own inverse, so the gradient is the same op on the gradient
@@ -140,77 +117,45 @@ def _(x):
 mx_block_rotate_op.register_autograd(lambda ctx, g: mx_block_rotate_op(g))
 
 
-# MX fake quantization of x R in one launch (ops.mx_quantize(rotate=True)); straight-through: grad_x = grad_y R, nothing saved
+# ops.mx_quantize(x, fmt): the identity gradient
+@torch.library.custom_op("llmqat_amd::mx_fake_quant", mutates_args=(), device_types="cuda")
+def mx_fake_quant_op(x: torch.Tensor, fmt: str) -> torch.Tensor:
+    return ops.mx_quantize(x, fmt)
+
+
+# ... of x R in one launch (rotate=True): grad_x = grad_y R
 @torch.library.custom_op("llmqat_amd::mx_fake_quant_rot", mutates_args=(), device_types="cuda")
 def mx_fake_quant_rot_op(x: torch.Tensor, fmt: str) -> torch.Tensor:
     return ops.mx_quantize(x, fmt, rotate=True)
 
 
-@mx_fake_quant_rot_op.register_fake
-def _(x, fmt):
-    ops.check_mx(tuple(x.shape), fmt)
-    ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
-    return torch.empty_like(x, memory_format=torch.contiguous_format)
-
-
-mx_fake_quant_rot_op.register_autograd(lambda ctx, g: (mx_block_rotate_op(g), None))
-
-
-# ops.mx_export(rotate=True) as an op: (elements, scales) of x R
-@torch.library.custom_op("llmqat_amd::mx_export_rot", mutates_args=(), device_types="cuda")
-def mx_export_rot_op(x: torch.Tensor, fmt: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    e = ops.mx_export(x, fmt, rotate=True)
-    return e.elements, e.scales
-
-
-@mx_export_rot_op.register_fake
-def _(x, fmt):
-    ops.check_mx(tuple(x.shape), fmt)
-    ops.check_mx_rotate(tuple(x.shape), "mx_export")
-    if fmt not in ops.MX_GEMM_FORMATS:
-        raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
-    lead, cols = tuple(x.shape[:-1]), x.shape[-1]
-    return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
-            x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))
-
-
-# ---- scale rule and saturation-masked gradient of the MX quantizer: the combinations the ops above do not cover ----
-# ops.mx_quantize under a non-default scale rule with the identity gradient (rotate: grad_x = grad_y R); nothing saved
+# ... under a non-default scale rule
 @torch.library.custom_op("llmqat_amd::mx_fake_quant_rule", mutates_args=(), device_types="cuda")
 def mx_fake_quant_rule_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> torch.Tensor:
     return ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule)
 
 
-@mx_fake_quant_rule_op.register_fake
-def _(x, fmt, rotate, scale_rule):
-    ops.check_mx(tuple(x.shape), fmt)
-    ops.check_mx_scale_rule(scale_rule)
-    if rotate:
-        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
-    return torch.empty_like(x, memory_format=torch.contiguous_format)
-
-
-def _mx_rule_setup(ctx, inputs, output):
-    ctx.rotate = inputs[2]
-
-
-mx_fake_quant_rule_op.register_autograd(lambda ctx, g: (mx_block_rotate_op(g) if ctx.rotate else g, None, None, None), setup_context=_mx_rule_setup)
-
-
-# ops.mx_quantize_axis(axis=-2): the blocks run down the columns; identity gradient, nothing saved
+# ... along axis -2, the blocks running down the columns (ops.mx_quantize_axis)
 @torch.library.custom_op("llmqat_amd::mx_fake_quant_cols", mutates_args=(), device_types="cuda")
 def mx_fake_quant_cols_op(x: torch.Tensor, fmt: str, scale_rule: str) -> torch.Tensor:
     return ops.mx_quantize_axis(x, fmt, scale_rule=scale_rule, axis=-2)
 
 
-@mx_fake_quant_cols_op.register_fake
-def _(x, fmt, scale_rule):
-    ops.check_mx_cols(tuple(x.shape), fmt)
-    ops.check_mx_scale_rule(scale_rule)
-    return torch.empty_like(x, memory_format=torch.contiguous_format)
+# ... with return_mask=True: (y, bitmap); the bitmap is all the backward keeps, and the backward is one launch
+@torch.library.custom_op("llmqat_amd::mx_fake_quant_clip", mutates_args=(), device_types="cuda")
+def mx_fake_quant_clip_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, return_mask=True)
 
 
-mx_fake_quant_cols_op.register_autograd(lambda ctx, g: (g, None, None))
+mx_fake_quant_op.register_fake(_mx_quant_fake)
+mx_fake_quant_rot_op.register_fake(lambda x, fmt: _mx_quant_fake(x, fmt, True))
+mx_fake_quant_rule_op.register_fake(_mx_quant_fake)
+mx_fake_quant_cols_op.register_fake(lambda x, fmt, scale_rule: _mx_quant_fake(x, fmt, False, scale_rule, False, -2))
+mx_fake_quant_clip_op.register_fake(lambda x, fmt, rotate, scale_rule: _mx_quant_fake(x, fmt, rotate, scale_rule, True))
+_mx_straight_through(mx_fake_quant_op, False)
+_mx_straight_through(mx_fake_quant_rot_op, True)
+_mx_straight_through(mx_fake_quant_rule_op)
+_mx_straight_through(mx_fake_quant_cols_op, False)
 
 
 # ops.mx_ste_backward: the gradient under the saturation bitmap (rotate: times R, same launch)
@@ -225,21 +170,6 @@ def _(g, mask, rotate):
     return torch.empty_like(g, memory_format=torch.contiguous_format)
 
 
-# ops.mx_quantize(return_mask=True): (y, bitmap); the bitmap is all the backward keeps, and the backward is one launch
-@torch.library.custom_op("llmqat_amd::mx_fake_quant_clip", mutates_args=(), device_types="cuda")
-def mx_fake_quant_clip_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    return ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, return_mask=True)
-
-
-@mx_fake_quant_clip_op.register_fake
-def _(x, fmt, rotate, scale_rule):
-    ops.check_mx(tuple(x.shape), fmt)
-    ops.check_mx_scale_rule(scale_rule)
-    if rotate:
-        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
-    return torch.empty_like(x, memory_format=torch.contiguous_format), x.new_empty((x.numel() // 8,), dtype=torch.uint8)
-
-
 def _mx_clip_setup(ctx, inputs, output):
     ctx.rotate = inputs[2]
     ctx.save_for_backward(output[1])
@@ -252,8 +182,12 @@ def _mx_clip_backward(ctx, grad_y, grad_mask):
 mx_fake_quant_clip_op.register_autograd(_mx_clip_backward, setup_context=_mx_clip_setup)
 
 
-def mx_fake_quant(x, fmt, rotate, scale_rule, clip):
-    """utils_quant's MX quantizer while compiling: the op that serves (rotate, scale_rule, clip)."""
+def mx_fake_quant(x, fmt, rotate, scale_rule, clip, axis=-1):
+    """utils_quant's MX quantizer while compiling: the op that serves (rotate, scale_rule, clip, axis)."""
+    if axis == -2:
+        if rotate or clip:
+            raise ValueError("mx_fake_quant: the column axis (axis=-2) serves neither the rotation nor the clip gradient yet")
+        return mx_fake_quant_cols_op(x, fmt, scale_rule)
     if clip:
         return mx_fake_quant_clip_op(x, fmt, rotate, scale_rule)[0]
     if scale_rule != "floor":
@@ -261,15 +195,8 @@ def mx_fake_quant(x, fmt, rotate, scale_rule, clip):
     return mx_fake_quant_rot_op(x, fmt) if rotate else mx_fake_quant_op(x, fmt)
 
 
-# ops.mx_export under a scale rule as an op: (elements, scales) of x (rotate: of x R)
-@torch.library.custom_op("llmqat_amd::mx_export_rule", mutates_args=(), device_types="cuda")
-def mx_export_rule_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    e = ops.mx_export(x, fmt, rotate=rotate, scale_rule=scale_rule)
-    return e.elements, e.scales
-
-
-@mx_export_rule_op.register_fake
-def _(x, fmt, rotate, scale_rule):
+# ---- ops.mx_export as ops: (elements, scales) of x in `fmt` (mxfp4 / mxfp8_*); of x R under rotate; under a scale rule ------------------
+def _mx_export_fake(x, fmt, rotate=False, scale_rule="floor"):
     ops.check_mx(tuple(x.shape), fmt)
     ops.check_mx_scale_rule(scale_rule, "mx_export")
     if rotate:
@@ -279,3 +206,47 @@ def _(x, fmt, rotate, scale_rule):
     lead, cols = tuple(x.shape[:-1]), x.shape[-1]
     return (x.new_empty(lead + (cols // 2 if fmt == "mxfp4" else cols,), dtype=torch.uint8),
             x.new_empty(lead + (cols // ops.MX_BLOCK,), dtype=torch.uint8))
+
+
+@torch.library.custom_op("llmqat_amd::mx_export", mutates_args=(), device_types="cuda")
+def mx_export_op(x: torch.Tensor, fmt: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    e = ops.mx_export(x, fmt)
+    return e.elements, e.scales
+
+
+@torch.library.custom_op("llmqat_amd::mx_export_rot", mutates_args=(), device_types="cuda")
+def mx_export_rot_op(x: torch.Tensor, fmt: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    e = ops.mx_export(x, fmt, rotate=True)
+    return e.elements, e.scales
+
+
+@torch.library.custom_op("llmqat_amd::mx_export_rule", mutates_args=(), device_types="cuda")
+def mx_export_rule_op(x: torch.Tensor, fmt: str, rotate: bool, scale_rule: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    e = ops.mx_export(x, fmt, rotate=rotate, scale_rule=scale_rule)
+    return e.elements, e.scales
+
+
+mx_export_op.register_fake(_mx_export_fake)
+mx_export_rot_op.register_fake(lambda x, fmt: _mx_export_fake(x, fmt, True))
+mx_export_rule_op.register_fake(_mx_export_fake)
+
+
+def mx_export(x, fmt, rotate, scale_rule):
+    """MXLinear's activation export while compiling: the op that serves (rotate, scale_rule) -> (elements, scales)."""
+    if scale_rule != "floor":
+        return mx_export_rule_op(x, fmt, rotate, scale_rule)
+    return mx_export_rot_op(x, fmt) if rotate else mx_export_op(x, fmt)
+
+
+# MX block-scaled GEMM (ops.mx_matmul) on the tensors of the two exports; inference only: no autograd formula is registered, so asking
+# for a gradient through it raises
+@torch.library.custom_op("llmqat_amd::mx_matmul", mutates_args=(), device_types="cuda")
+def mx_matmul_op(a_elems: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, w_elems: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
+                 a_shape: List[int], out_dtype: torch.dtype) -> torch.Tensor:
+    return ops.mx_matmul_tensors(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, tuple(a_shape), out_dtype)
+
+
+@mx_matmul_op.register_fake
+def _(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, a_shape, out_dtype):
+    _, N, _ = ops.check_mx_matmul(tuple(a_shape), a_fmt, (w_scales.shape[0], w_scales.shape[1] * ops.MX_BLOCK), w_fmt, out_dtype)
+    return a_elems.new_empty(tuple(a_shape[:-1]) + (N,), dtype=out_dtype)

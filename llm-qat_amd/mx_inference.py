@@ -77,11 +77,8 @@ class MXLinear(nn.Module):
     def forward(self, x):
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("MXLinear is an inference module and is not differentiable: call it under torch.no_grad() or on a detached input")
-        if torch.compiler.is_compiling() and self.scale_rule != "floor":
-            ae, asc = compiled.mx_export_rule_op(x, self.act_format, self.rotate, self.scale_rule)
-            y = compiled.mx_matmul_op(ae, asc, self.act_format, self.weight_elements, self.weight_scales, self.weight_format, list(x.shape), x.dtype)
-        elif torch.compiler.is_compiling():
-            ae, asc = (compiled.mx_export_rot_op if self.rotate else compiled.mx_export_op)(x, self.act_format)
+        if torch.compiler.is_compiling():
+            ae, asc = compiled.mx_export(x, self.act_format, self.rotate, self.scale_rule)
             y = compiled.mx_matmul_op(ae, asc, self.act_format, self.weight_elements, self.weight_scales, self.weight_format, list(x.shape), x.dtype)
         else:
             a = ops.mx_export(x, self.act_format, rotate=self.rotate, scale_rule=self.scale_rule)

@@ -1015,12 +1015,18 @@ mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm
              "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0, "mx_cols_launch": 0}
 
 
-def check_mx(shape, fmt):
-    """-> the format's C code after the argument checks of the MX API (ValueError for an unknown format or a last dimension that is not a
-    multiple of 32)"""
+def _mx_format(fmt):
+    """-> the C code of an MX format name; ValueError for anything else"""
     code = MX_FORMATS.get(fmt) if isinstance(fmt, str) else None
     if code is None:
         raise ValueError(f"unknown MX format {fmt!r}: one of {', '.join(MX_FORMATS)}")
+    return code
+
+
+def check_mx(shape, fmt):
+    """-> the format's C code after the argument checks of the MX API (ValueError for an unknown format or a last dimension that is not a
+    multiple of 32)"""
+    code = _mx_format(fmt)
     if len(shape) == 0:
         raise ValueError("MX formats take tensors with at least one dimension")
     if shape[-1] % MX_BLOCK:
@@ -1043,32 +1049,6 @@ def check_mx_scale_rule(scale_rule, what="mx_quantize"):
     return _lib.MX_FLAG_CEIL if scale_rule == "ceil" else 0
 
 
-def _mx_input(x, fmt, what, rotate=False):
-    code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) and fmt is not None else None
-    if rotate and isinstance(x, torch.Tensor):
-        check_mx_rotate(tuple(x.shape), what)
-    dt = _prep(x, what)
-    if dt == _lib.DTYPE_F64:
-        raise NotImplementedError(f"{what}: float64 is not served by the MX formats (float32, bfloat16, float16 are)")
-    if not x.is_contiguous() or x.data_ptr() & 15:
-        mx_counts["mx_copy_route"] += 1
-        x = x.contiguous() if not x.is_contiguous() else x.clone()   # (a fresh allocation is 16-byte aligned)
-    return x, code, dt
-
-
-def mx_rotate(x):
-    """x R (same shape and dtype): every run of 64 elements along the last dimension times H64 / 8, in fp32, rounded once to x's dtype.
-    R is its own inverse and its own transpose, so this is also the backward of itself.  One launch (fq_block_rotate)."""
-    x, _, dt = _mx_input(x, None, "mx_rotate", True)
-    y = torch.empty_like(x, memory_format=torch.contiguous_format)
-    if x.numel():
-        cols = x.shape[-1]
-        rows = x.numel() // cols
-        _lib.check(_launch(x, _lib.lib().fq_block_rotate, x.data_ptr(), y.data_ptr(), rows, cols, dt), "mx_rotate")
-        mx_counts["mx_rotate_launch"] += 1
-    return y
-
-
 def check_mx_axis(ndim, axis, what="mx_quantize"):
     """-> -1 or -2, the axis the MX blocks run along; ValueError for anything but the last two axes (negative or not) of the tensor"""
     if isinstance(axis, int) and not isinstance(axis, bool):
@@ -1084,9 +1064,7 @@ def check_mx_axis(ndim, axis, what="mx_quantize"):
 def check_mx_cols(shape, fmt, what="mx_quantize"):
     """-> the format's C code after the argument checks of the column axis: at least two dimensions, shape[-2] a multiple of 32 (the last
     dimension is free)"""
-    code = MX_FORMATS.get(fmt) if isinstance(fmt, str) else None
-    if code is None:
-        raise ValueError(f"unknown MX format {fmt!r}: one of {', '.join(MX_FORMATS)}")
+    code = _mx_format(fmt)
     if len(shape) < 2:
         raise ValueError(f"{what}: axis=-2 needs a tensor with at least two dimensions, got {len(shape)}")
     if shape[-2] % MX_BLOCK:
@@ -1094,39 +1072,86 @@ def check_mx_cols(shape, fmt, what="mx_quantize"):
     return code
 
 
-def _mx_quantize_cols(x, fmt, scale_rule):
-    """mx_quantize_axis along axis -2: one launch of the column kernel on a contiguous, 16-byte aligned tensor whose rows
-    are whole 16-byte vectors; anything else goes through the row kernel on the transposed copy (same values; mx_copy_route)."""
-    flags = check_mx_scale_rule(scale_rule)
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
-    code = check_mx_cols(tuple(x.shape), fmt)
-    dt = _prep(x, "mx_quantize")
-    if dt == _lib.DTYPE_F64:
-        raise NotImplementedError("mx_quantize: float64 is not served by the MX formats (float32, bfloat16, float16 are)")
-    cols = x.shape[-1]
-    if not x.is_contiguous() or x.data_ptr() & 15 or (cols * x.element_size()) % 16:
+def _mx_aligned(t, count):
+    """t where it is contiguous and 16-byte aligned, else one fresh copy (aligned as every allocation); count: as an mx_copy_route"""
+    if t.is_contiguous() and not t.data_ptr() & 15:
+        return t
+    if count:
         mx_counts["mx_copy_route"] += 1
-        return mx_quantize(x.transpose(-1, -2).contiguous(), fmt, scale_rule=scale_rule).transpose(-1, -2).contiguous()
-    y = torch.empty_like(x)
-    if x.numel():
-        rc = _launch(x, _lib.lib().fqt_mx_fwd_cols, x.data_ptr(), y.data_ptr(), x.numel() // cols, cols, code, dt, flags)
-        _lib.check(rc, "mx_quantize")
-        mx_counts["mx_cols_launch"] += 1
+    return t.clone() if t.is_contiguous() else t.contiguous()
+
+
+def _mx_input(x, fmt, what, rotate=False, axis=-1):
+    """The input checks of every MX launch, in their order: format (None: the call has none) and shape for `axis`, the rotation's shape,
+    type / device / dtype, then the copy route -> (tensor to launch on, format code, dtype code, the axis its blocks run along).  The
+    column kernel takes a contiguous, aligned tensor of whole 16-byte rows: any other comes back transposed, for the row kernel (-1)."""
+    code = None
+    if isinstance(x, torch.Tensor):
+        if axis == -2:
+            code = check_mx_cols(tuple(x.shape), fmt, what)
+        elif fmt is not None:
+            code = check_mx(tuple(x.shape), fmt)
+        if rotate:
+            check_mx_rotate(tuple(x.shape), what)
+    dt = _prep(x, what)
+    if dt == _lib.DTYPE_F64:
+        raise NotImplementedError(f"{what}: float64 is not served by the MX formats (float32, bfloat16, float16 are)")
+    if axis == -2 and (not x.is_contiguous() or x.data_ptr() & 15 or (x.shape[-1] * x.element_size()) % 16):
+        mx_counts["mx_copy_route"] += 1
+        x, axis = x.transpose(-1, -2).contiguous(), -1
+    return _mx_aligned(x, True), code, dt, axis
+
+
+def _mx_launch(what, entry, counter, t, head, *tail, dims=None):
+    """The tail of every MX launch: lib.<entry>(*head, *dims, *tail, stream) on t's device, the status checked under the caller's name,
+    mx_counts[counter] bumped; dims None: t's (rows, cols).  A dimension of 0: nothing is launched or counted.  -> whether it launched."""
+    if dims is None:
+        cols = t.shape[-1]
+        dims = (t.numel() // cols if cols else 0, cols)
+    if 0 in dims:
+        return False
+    _lib.check(_launch(t, getattr(_lib.lib(), entry), *head, *dims, *tail), what)
+    mx_counts[counter] += 1
+    return True
+
+
+def mx_rotate(x):
+    """x R (same shape and dtype): every run of 64 elements along the last dimension times H64 / 8, in fp32, rounded once to x's dtype.
+    R is its own inverse and its own transpose, so this is also the backward of itself.  One launch (fq_block_rotate)."""
+    x, _, dt, _ = _mx_input(x, None, "mx_rotate", True)
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    _mx_launch("mx_rotate", "fq_block_rotate", "mx_rotate_launch", x, (x.data_ptr(), y.data_ptr()), dt)
     return y
+
+
+def _mx_quantize(x, fmt, rotate, scale_rule, return_mask, axis):
+    """mx_quantize / mx_quantize_axis: one launch of the row kernel (fq_mx_fwd_ex), or along axis -2 one of the
+    column kernel (fqt_mx_fwd_cols) where it takes the input, else the row kernel on the transposed copy, transposed back."""
+    down = axis != -1 and isinstance(x, torch.Tensor) and check_mx_axis(x.dim(), axis) == -2
+    if down and (rotate or return_mask):
+        raise ValueError(f"mx_quantize: the column axis (axis=-2) does not serve {'rotate' if rotate else 'return_mask'}=True yet")
+    flags = check_mx_scale_rule(scale_rule) | (_lib.MX_FLAG_ROTATE if rotate else 0)
+    x, code, dt, axis = _mx_input(x, fmt, "mx_quantize", rotate, -2 if down else -1)
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    if axis == -2:
+        _mx_launch("mx_quantize", "fqt_mx_fwd_cols", "mx_cols_launch", x, (x.data_ptr(), y.data_ptr()), code, dt, flags)
+        return y
+    mask = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device) if return_mask else None
+    head = (x.data_ptr(), y.data_ptr(), mask.data_ptr() if return_mask else None)
+    if _mx_launch("mx_quantize", "fq_mx_fwd_ex", "mx_launch", x, head, code, dt, flags) and return_mask:
+        mx_counts["mx_mask_launch"] += 1
+    if down:
+        return y.transpose(-1, -2).contiguous()
+    return (y, mask) if return_mask else y
 
 
 def mx_quantize_axis(x, fmt, rotate=False, scale_rule="floor", return_mask=False, axis=-1):
     """mx_quantize with a choice of the axis the blocks run along: -1 (or ndim - 1) is mx_quantize itself; -2 (or ndim - 2): the blocks run
     down the columns -- 32 consecutive elements of the second-to-last dimension (a multiple of 32; the last one is free) share a scale;
     the result is contiguous and equals the last-axis result of the transposed tensor, transposed back, bit for bit.  One launch of its
-    own kernel; the rotation and the mask are not served there (ValueError).  (A function of its own: mx_quantize's parameter list is
-    pinned by tests/test_mx_rules_cpu.py.)"""
-    if isinstance(x, torch.Tensor) and check_mx_axis(x.dim(), axis) == -2:
-        if rotate or return_mask:
-            raise ValueError(f"mx_quantize: the column axis (axis=-2) does not serve {'rotate' if rotate else 'return_mask'}=True yet")
-        return _mx_quantize_cols(x, fmt, scale_rule)
-    return mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, return_mask=return_mask)
+    own kernel; the rotation and the mask are not served there (ValueError).  (mx_quantize's body, _mx_quantize, under a name that takes
+    the axis: mx_quantize's own parameter list is pinned by tests/test_mx_rules_cpu.py.)"""
+    return _mx_quantize(x, fmt, rotate, scale_rule, return_mask, axis)
 
 
 def mx_quantize(x, fmt, rotate=False, scale_rule="floor", return_mask=False):
@@ -1135,19 +1160,7 @@ def mx_quantize(x, fmt, rotate=False, scale_rule="floor", return_mask=False):
     fp32 values of x R (mx_rotate) instead, in the same single launch; the result is in the rotated basis.
     scale_rule="ceil": the shared exponent under which no element of a finite block saturates.  return_mask=True -> (y, mask): mask is a
     uint8 tensor of numel / 8 bytes written by the same launch, a 0 bit where saturation changed the element (of x R under rotate)."""
-    flags = check_mx_scale_rule(scale_rule) | (_lib.MX_FLAG_ROTATE if rotate else 0)
-    x, code, dt = _mx_input(x, fmt, "mx_quantize", rotate)
-    y = torch.empty_like(x, memory_format=torch.contiguous_format)
-    mask = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device) if return_mask else None
-    if x.numel():
-        cols = x.shape[-1]
-        rows = x.numel() // cols
-        rc = _launch(x, _lib.lib().fq_mx_fwd_ex, x.data_ptr(), y.data_ptr(), mask.data_ptr() if return_mask else None, rows, cols, code, dt, flags)
-        _lib.check(rc, "mx_quantize")
-        mx_counts["mx_launch"] += 1
-        if return_mask:
-            mx_counts["mx_mask_launch"] += 1
-    return (y, mask) if return_mask else y
+    return _mx_quantize(x, fmt, rotate, scale_rule, return_mask, -1)
 
 
 def check_mx_ste(g_shape, mask_shape, mask_dtype, rotate):
@@ -1176,19 +1189,13 @@ def mx_ste_backward(g, mask, rotate=False):
         raise TypeError(f"mx_ste_backward: expected a torch.Tensor mask, got {type(mask).__name__}")
     if isinstance(g, torch.Tensor):
         check_mx_ste(tuple(g.shape), tuple(mask.shape), mask.dtype, rotate)
-    g, _, dt = _mx_input(g, None, "mx_ste_backward", False)
+    g, _, dt, _ = _mx_input(g, None, "mx_ste_backward")
     if mask.device != g.device:
         raise RuntimeError(f"mx_ste_backward: the mask is on '{mask.device}', the gradient on '{g.device}'")
-    if not mask.is_contiguous() or mask.data_ptr() & 15:
-        mx_counts["mx_copy_route"] += 1
-        mask = mask.contiguous() if not mask.is_contiguous() else mask.clone()
+    mask = _mx_aligned(mask, True)
     gx = torch.empty_like(g, memory_format=torch.contiguous_format)
-    if g.numel():
-        cols = g.shape[-1]
-        rows = g.numel() // cols
-        rc = _launch(g, _lib.lib().fq_mx_ste_bwd, g.data_ptr(), mask.data_ptr(), gx.data_ptr(), rows, cols, dt, _lib.MX_FLAG_ROTATE if rotate else 0)
-        _lib.check(rc, "mx_ste_backward")
-        mx_counts["mx_ste_launch"] += 1
+    flags = _lib.MX_FLAG_ROTATE if rotate else 0
+    _mx_launch("mx_ste_backward", "fq_mx_ste_bwd", "mx_ste_launch", g, (g.data_ptr(), mask.data_ptr(), gx.data_ptr()), dt, flags)
     return gx
 
 
@@ -1238,15 +1245,12 @@ def mx_export(x, fmt, rotate=False, scale_rule="floor"):
     code = check_mx(tuple(x.shape), fmt) if isinstance(x, torch.Tensor) else None
     if code in (_lib.MX_FP6_E2M3, _lib.MX_FP6_E3M2):
         raise ValueError(f"{fmt!r}: FP6 formats have no export packing")
-    x, code, dt = _mx_input(x, fmt, "mx_export", rotate)
+    x, _, dt, _ = _mx_input(x, None, "mx_export", rotate)   # (the format is checked: the FP6 refusal comes before the rotation's and the device's)
     cols = x.shape[-1]
     lead = tuple(x.shape[:-1])
     elems = torch.empty(lead + (cols // 2 if code == _lib.MX_FP4_E2M1 else cols,), dtype=torch.uint8, device=x.device)
     scales = torch.empty(lead + (cols // MX_BLOCK,), dtype=torch.uint8, device=x.device)
-    if x.numel():
-        rows = x.numel() // cols
-        _lib.check(_launch(x, _lib.lib().fq_mx_export_ex, x.data_ptr(), elems.data_ptr(), scales.data_ptr(), rows, cols, code, dt, flags), "mx_export")
-        mx_counts["mx_export_launch"] += 1
+    _mx_launch("mx_export", "fq_mx_export_ex", "mx_export_launch", x, (x.data_ptr(), elems.data_ptr(), scales.data_ptr()), code, dt, flags)
     return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype, rotate)
 
 
@@ -1295,14 +1299,10 @@ def mx_matmul_tensors(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, a_shap
             raise ValueError(f"mx_matmul: {what} holds {t.numel()} bytes, not those of a [{rows}, {K}] {fmt} export")
     if a_scales.numel() != M * (K // MX_BLOCK) or w_scales.numel() != N * (K // MX_BLOCK):
         raise ValueError("mx_matmul: a scales tensor does not hold one byte per 32-element block")
-    fix = lambda t: t if (t.is_contiguous() and not t.data_ptr() & 15) else t.contiguous().clone()
-    a_elems, a_scales, w_elems, w_scales = fix(a_elems), fix(a_scales), fix(w_elems), fix(w_scales)
+    a_elems, a_scales, w_elems, w_scales = (_mx_aligned(t, False) for t in ts)
     out = torch.empty(tuple(a_shape[:-1]) + (N,), dtype=out_dtype, device=a_elems.device)
-    if M and N:
-        rc = _launch(a_elems, _lib.lib().fq_mx_gemm, a_elems.data_ptr(), a_scales.data_ptr(), MX_FORMATS[a_fmt], w_elems.data_ptr(), w_scales.data_ptr(),
-                     MX_FORMATS[w_fmt], out.data_ptr(), M, N, K, _OUT_DTYPES[out_dtype])
-        _lib.check(rc, "mx_matmul")
-        mx_counts["mx_gemm_launch"] += 1
+    head = (a_elems.data_ptr(), a_scales.data_ptr(), MX_FORMATS[a_fmt], w_elems.data_ptr(), w_scales.data_ptr(), MX_FORMATS[w_fmt], out.data_ptr())
+    if _mx_launch("mx_matmul", "fq_mx_gemm", "mx_gemm_launch", a_elems, head, _OUT_DTYPES[out_dtype], dims=(M, N, K)):
         mx_counts["mx_gemm_skinny" if M <= MX_GEMM_SKINNY_M else "mx_gemm_tiled"] += 1
     return out
 

@@ -476,18 +476,18 @@ class _BlockRotate(torch.autograd.Function):
 
 
 class _MXQuantizer(torch.autograd.Function):
-    """MX block-scaled fake quantization (ops.mx_quantize; DESIGN.md sections 13, 15, 16), straight-through over the quantizer only.
+    """MX block-scaled fake quantization (ops.mx_quantize_axis; DESIGN.md sections 13, 15, 16, 17), straight-through over the quantizer only.
     Without clip nothing is saved and the gradient is the incoming one itself (as the 1-/2-bit weight branches, _LowBitWeight; the saturated
     elements are not masked), times R under rotate -- the rotation is a linear map with its own gradient: one rotate launch.  clip: the
     forward launch also writes the saturation bitmap, the only tensor saved, and the backward is one launch: grad_x = grad_y where the bit
-    is 1, +0.0 elsewhere (times R under rotate, in that launch)."""
+    is 1, +0.0 elsewhere (times R under rotate, in that launch).  axis -2 (the blocks run down the columns) serves neither rotate nor clip."""
 
     @staticmethod
-    def forward(ctx, x, fmt, rotate, scale_rule, clip):
+    def forward(ctx, x, fmt, rotate, scale_rule, clip, axis):
         ctx.set_materialize_grads(False)
         ctx.rotate, ctx.clip = rotate, clip
         if not clip:
-            return ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule)
+            return ops.mx_quantize_axis(x, fmt, rotate, scale_rule, False, axis)
         y, mask = ops.mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, return_mask=True)
         ctx.save_for_backward(mask)
         return y
@@ -495,30 +495,16 @@ class _MXQuantizer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         if grad_output is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         if not ctx.clip:
-            return (_BlockRotate.apply(grad_output) if ctx.rotate else grad_output), None, None, None, None
+            return (_BlockRotate.apply(grad_output) if ctx.rotate else grad_output), None, None, None, None, None
         mask, = ctx.saved_tensors
         if torch.is_grad_enabled():   # create_graph: the mask does not depend on the gradient (as _graph_aware) -- learn it on ones
             with torch.no_grad():
                 keep = ops.mx_ste_backward(torch.ones_like(grad_output), mask)
             g = torch.where(keep != 0, grad_output, torch.zeros((), dtype=grad_output.dtype, device=grad_output.device))
-            return (_BlockRotate.apply(g) if ctx.rotate else g), None, None, None, None
-        return ops.mx_ste_backward(grad_output, mask, ctx.rotate), None, None, None, None
-
-
-class _MXColsQuantizer(torch.autograd.Function):
-    """MX fake quantization with the blocks running down the columns (ops.mx_quantize_axis(axis=-2)), straight-through:
-    nothing is saved and the gradient is the incoming tensor itself."""
-
-    @staticmethod
-    def forward(ctx, x, fmt, scale_rule):
-        ctx.set_materialize_grads(False)
-        return ops.mx_quantize_axis(x, fmt, scale_rule=scale_rule, axis=-2)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        return grad_output, None, None
+            return (_BlockRotate.apply(g) if ctx.rotate else g), None, None, None, None, None
+        return ops.mx_ste_backward(grad_output, mask, ctx.rotate), None, None, None, None, None
 
 
 MX_STE_MODES = ("identity", "clip")
@@ -530,12 +516,37 @@ def _check_mx_ste(ste, what="mx_quantize"):
     return ste
 
 
-def _mx_apply(x, fmt, rotate, scale_rule, ste):
-    """the MX quantizer of (rotate, scale_rule, ste) on x, eager or while compiling; the arguments are checked by the callers"""
+def _check_mx_format(fmt):
+    """a setting that holds an MX format name or None"""
+    if fmt is not None and fmt not in ops.MX_FORMATS:
+        raise ValueError(f"unknown MX format {fmt!r}: one of {', '.join(ops.MX_FORMATS)}")
+
+
+def _mx_check(x, fmt, rotate, scale_rule, ste, axis):
+    """The argument checks of mx_quantize / mx_quantize_axis, in their order: tensor, axis, format, shape, rule, ste, what the column axis
+    does not serve, the rotation's shape -> -1 | -2.  (Dynamo traces this: plain branches and lookups.)"""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
+    axis = ops.check_mx_axis(x.dim(), axis)
+    if axis == -2:
+        ops.check_mx_cols(tuple(x.shape), fmt)
+    else:
+        ops.check_mx(tuple(x.shape), fmt)
+    ops.check_mx_scale_rule(scale_rule)
+    _check_mx_ste(ste)
+    if axis == -2 and (rotate or ste == "clip"):
+        raise ValueError(f"mx_quantize: the column axis (axis=-2) does not serve {'rotate=True' if rotate else 'ste=clip'} yet")
+    if rotate:
+        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
+    return axis
+
+
+def _mx_apply(x, fmt, rotate, scale_rule, ste, axis=-1):
+    """the MX quantizer of (rotate, scale_rule, ste, axis) on x, eager or while compiling; the arguments are checked by the callers"""
     clip = ste == "clip" and torch.is_grad_enabled() and x.requires_grad   # no backward will come: no bitmap is written
     if torch.compiler.is_compiling():
-        return compiled.mx_fake_quant(x, fmt, rotate, scale_rule, clip)
-    return _MXQuantizer.apply(x, fmt, rotate, scale_rule, clip)
+        return compiled.mx_fake_quant(x, fmt, rotate, scale_rule, clip, axis)
+    return _MXQuantizer.apply(x, fmt, rotate, scale_rule, clip, axis)
 
 
 def block_rotate(x):
@@ -556,43 +567,24 @@ def mx_quantize(x, fmt, rotate=False, scale_rule="floor", ste="identity"):
     scale_rule="ceil" takes the shared exponent under which no element saturates ("floor": OCP's round-down rule, under which the top
     binade of a block may).  ste="clip" zeroes the gradient of the elements that saturation changed: the forward launch also writes a
     bitmap (numel / 8 bytes, all that is saved) and the backward is one launch, with or without the rotation."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
-    ops.check_mx(tuple(x.shape), fmt)
-    ops.check_mx_scale_rule(scale_rule)
-    _check_mx_ste(ste)
-    if rotate:
-        ops.check_mx_rotate(tuple(x.shape), "mx_quantize")
-    return _mx_apply(x, fmt, bool(rotate), scale_rule, ste)
+    return _mx_apply(x, fmt, bool(rotate), scale_rule, ste, _mx_check(x, fmt, rotate, scale_rule, ste, -1))
 
 
 def mx_quantize_axis(x, fmt, rotate=False, scale_rule="floor", ste="identity", axis=-1):
     """mx_quantize with a choice of the axis the blocks run along: -1 (or ndim - 1) is mx_quantize itself.  -2 (or ndim - 2): the blocks
     run down the columns -- 32 consecutive elements of the second-to-last dimension (a multiple of 32; the last one is free) share a
     scale, which is what a product that contracts over that axis needs (the backward GEMMs of a linear layer).  One launch, a contiguous
-    result, the identity gradient; the rotation and ste="clip" are not served along that axis (ValueError).  (A function of its own:
-    mx_quantize's parameter list is pinned by tests/test_mx_rules_cpu.py.)"""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"mx_quantize: expected a torch.Tensor, got {type(x).__name__}")
-    if ops.check_mx_axis(x.dim(), axis) == -1:
-        return mx_quantize(x, fmt, rotate=rotate, scale_rule=scale_rule, ste=ste)
-    ops.check_mx_cols(tuple(x.shape), fmt)
-    ops.check_mx_scale_rule(scale_rule)
-    _check_mx_ste(ste)
-    if rotate or ste == "clip":
-        raise ValueError(f"mx_quantize: the column axis (axis=-2) does not serve {'rotate=True' if rotate else 'ste=clip'} yet")
-    if torch.compiler.is_compiling():
-        return compiled.mx_fake_quant_cols_op(x, fmt, scale_rule)
-    return _MXColsQuantizer.apply(x, fmt, scale_rule)
+    result, the identity gradient; the rotation and ste="clip" are not served along that axis (ValueError).  (The same checks and
+    quantizer as mx_quantize, whose own parameter list is pinned by tests/test_mx_rules_cpu.py.)"""
+    return _mx_apply(x, fmt, bool(rotate), scale_rule, ste, _mx_check(x, fmt, rotate, scale_rule, ste, axis))
 
 
 def default_mx_formats(weight=None, act=None):
     """MX formats the QuantizeLinears constructed from now on take for the operands they quantize (w_bits < 32 / a_bits < 32, not
     layerwise, no explicit group size) when their own weight_format / act_format are not given (None: the integer quantizers).  Lets
     unchanged model code (LLM-QAT's train.py) train for MXFP4.  -> the previous pair."""
-    for f in (weight, act):
-        if f is not None and f not in ops.MX_FORMATS:
-            raise ValueError(f"unknown MX format {f!r}: one of {', '.join(ops.MX_FORMATS)}")
+    _check_mx_format(weight)
+    _check_mx_format(act)
     return _set_default("mx", (weight, act))
 
 
@@ -621,8 +613,7 @@ def default_mx_backward_format(fmt):
     """The MX format the QuantizeLinears constructed from now on run their backward GEMMs in (mx_backward_format) when their own is not
     given; None: the backward GEMMs stay in the tensors' dtype.  Applies only to layers that qualify: both operands in an MX format, no
     rotation, the identity gradient, out_features a multiple of 32.  -> the previous format."""
-    if fmt is not None and fmt not in ops.MX_FORMATS:
-        raise ValueError(f"unknown MX format {fmt!r}: one of {', '.join(ops.MX_FORMATS)}")
+    _check_mx_format(fmt)
     return _set_default("mx_backward", fmt)
 
 
@@ -1450,8 +1441,7 @@ class QuantizeLinear(nn.Linear):
         # (default_mx_backward_format) applies to the layers that do
         why = _mx_backward_refusal(self)
         if mx_backward_format is not None:
-            if mx_backward_format not in ops.MX_FORMATS:
-                raise ValueError(f"unknown MX format {mx_backward_format!r}: one of {', '.join(ops.MX_FORMATS)}")
+            _check_mx_format(mx_backward_format)
             if why is not None:
                 raise ValueError(f"mx_backward_format: {why}")
             self.mx_backward_format = mx_backward_format
@@ -1668,11 +1658,13 @@ class QuantizeLinear(nn.Linear):
     def _group_act(self, input_):
         return _GroupQuantizer.apply(input_, _CLIP, self.a_bits, self.act_group_size, self._act_kind, True, False)
 
-    def _finish(self, input_, weight):
-        out = nn.functional.linear(input_, weight)
+    def _add_bias(self, out):
         if self.bias is not None:
             out += self.bias.view(1, -1).expand_as(out)
         return out
+
+    def _finish(self, input_, weight):
+        return self._add_bias(nn.functional.linear(input_, weight))
 
     def _forward_compiled(self, input_):
         """forward while torch.compile traces: the same kernels as custom ops, no Python-side caches (compiled.py)"""
@@ -1708,10 +1700,7 @@ class QuantizeLinear(nn.Linear):
             why = _mx_backward_refusal(self)   # (the settings are plain attributes: one may have been assigned since the constructor)
             if why is not None:
                 raise ValueError(f"mx_backward_format: {why}")
-            out = _MXLinearBackward.apply(input_, self.weight, self.weight_format, self.act_format, self.mx_scale_rule, self.mx_backward_format)
-            if self.bias is not None:
-                out += self.bias.view(1, -1).expand_as(out)
-            return out
+            return self._add_bias(_MXLinearBackward.apply(input_, self.weight, self.weight_format, self.act_format, self.mx_scale_rule, self.mx_backward_format))
         route, weight = self._weight_route(), self.weight
         if route == "low" and self.weight_group_size is not None:
             route = "group"    # (a group size ASSIGNED to a 1-/2-bit layer -- the constructor refuses one: this path alone has always honoured it)
