@@ -22,7 +22,8 @@ import group_cases as C
 from conftest import ROOT
 from export_cases import EPV, RUNGS
 from group_ntl_worker import DEV, DTS, from_dev, to_dev
-from test_gpu_row_launch_shapes import row_bits, unpack_mask
+from row_ntl_worker import unpack_mask
+from row_view_cases import row_bits
 
 pytestmark = pytest.mark.gpu
 DTYPES = ["bf16", "fp16", "fp32"]

@@ -8,9 +8,11 @@ import pytest
 import torch
 
 import group_cases as C
+import row_ntl_worker as W
 from group_ntl_worker import from_dev, report, to_dev
 from mx_reference import encode
-from test_gpu_row_launch_shapes import BITS, HI, LO, ROWS, grad_and_masked, memo, none_failed, row_bits
+from row_view_cases import BITS, ROWS, memo, row_bits
+from row_ntl_worker import none_failed
 
 pytestmark = pytest.mark.gpu
 
@@ -24,45 +26,20 @@ def _semantics():
     llm_qat_amd.set_semantics(prev)
 
 
-def dev_bounds(bits, dt, asym=False):
-    return torch.from_numpy(C.row_bounds(bits, dt, asym)).to("cuda")
-
-
-# ---- the x-reading backward --------------------------------------------------------------------------------------------------------------
-
-# rows of 256 v - 1 vectors: v vectors per thread (launch_ste_rows), the last lane slot a clamped duplicate; 2049 vectors: two chunks of
-# 1025 and 1024 vectors at 5 vectors per thread, the second one short
-ROW_NVECS = [256 * v - 1 for v in range(1, 9)] + [2049]
-
+# ---- the x-reading backward (the loops live in row_ntl_worker.py, which runs them once more with non-temporal loads) --------------------
 
 @pytest.mark.parametrize("dt", ["bf16", "fp32"])
 def test_rows_backward_at_every_vector_count_and_a_short_chunk(dt):
     """5 rows: rows 0 / 2 / 4 can clip (row 2 holds a NaN: its bounds are NaN, its NaN passes the gradient), rows 1 / 3 are copied
     without their x being read"""
-    from llm_qat_amd import ops
-    failures = []
-    for nvec in ROW_NVECS:
-        cols = nvec * C.EPV[dt]
-        b = row_bits(dt, cols)
-        bounds = C.row_bounds(b, dt, False)
-        safe = (bounds[:, 0] < HI) & (bounds[:, 1] > LO)
-        assert safe.any() and (~safe).any() and np.isnan(bounds[2]).all()
-        g, want = grad_and_masked(dt, cols)
-        got = ops.ste_backward(to_dev(g, dt), to_dev(b, dt), LO, HI, row_bounds=dev_bounds(b, dt), rows_cols_hint=(ROWS, cols))
-        failures.append(report(from_dev(got, dt), want, dt, f"{dt} nvec {nvec} rows backward"))
-    none_failed(failures)
+    none_failed(W.rows_backward(dt))
 
 
 @pytest.mark.parametrize("nvec", [257, 1])
 @pytest.mark.parametrize("dt", ["bf16", "fp32"])
 def test_flat_backward(dt, nvec):
     """fq_ste_bwd on n = 257 vectors (two blocks, the second holds one vector) and on a single vector"""
-    from llm_qat_amd import ops
-    cols = nvec * C.EPV[dt]
-    g, want = grad_and_masked(dt, cols, 1)
-    assert want.any() and (want != g).any()
-    got = ops.ste_backward(to_dev(g, dt), to_dev(row_bits(dt, cols, 1), dt), LO, HI)
-    assert report(from_dev(got, dt), want, dt, f"{dt} {nvec} vectors flat backward") is None
+    none_failed(W.flat_backward(dt, nvec))
 
 
 # ---- the two-pass path -------------------------------------------------------------------------------------------------------------------
