@@ -281,6 +281,27 @@ def _aligned(g):
     return g.clone() if g.data_ptr() & 15 else g
 
 
+def _mask_slot(g, side, rows, inplace=False, out_dtype=None):
+    """One tensor of a masked STE backward launch -> (g, gx, (g, gx, rows, bounds, mask) as the C ABI takes them): the gradient contiguous
+    and 16-byte aligned, and fp32 behind a wide forward (out_dtype given); the result in place, fresh, or fresh in out_dtype; the side
+    buffer's two pointers.  What train_backward, train_backward_wide, pair_backward, pair_backward_wide and multi_backward do per tensor."""
+    if out_dtype is not None and g.dtype != torch.float32:
+        g = g.float()
+    g = g.contiguous()
+    gp = g.data_ptr()
+    if gp & 15:   # (a contiguous gradient can still be an offset view into a larger buffer)
+        g = g.clone()
+        gp = g.data_ptr()
+    if inplace:
+        gx = g
+    elif out_dtype is None:
+        gx = torch.empty_like(g)
+    else:
+        gx = torch.empty(g.shape, dtype=out_dtype, device=g.device)
+    bp = side.data_ptr()
+    return g, gx, (gp, gx.data_ptr(), rows, bp, bp + rows * SIDE_ROW_BYTES)
+
+
 def train_forward(kind, x, num_bits, layerwise, lo, hi):
     """-> (y, side, rows, cols) or None.  `side` is one uint8 buffer: float[rows][2] bounds followed by the mask."""
     if x.device.type != "cuda":
@@ -355,10 +376,8 @@ def train_backward(grad_output, side, rows, cols, lo, hi, inplace=False):
         res = _mask_backward_v([grad_output], [side], [rows], cols, lo, hi, code, False, [inplace])
         if res is not None:
             return res[0]
-    g = _aligned(grad_output)
-    gx = g if inplace else torch.empty_like(g)
-    bp, mp = _side_ptrs(side, rows)
-    rc = _launch(g, _lib.lib().fq_ste_bwd_mask, g.data_ptr(), gx.data_ptr(), rows, cols, lo, hi, bp, mp, side.numel() - (mp - bp), code)   # (mp - bp: the bounds' bytes)
+    g, gx, (gp, gxp, _, bp, mp) = _mask_slot(grad_output, side, rows, inplace)
+    rc = _launch(g, _lib.lib().fq_ste_bwd_mask, gp, gxp, rows, cols, lo, hi, bp, mp, side.numel() - (mp - bp), code)   # (mp - bp: the bounds' bytes)
     if rc:
         _lib.check(rc, "ste_backward_mask")
     return gx
@@ -374,10 +393,8 @@ def train_backward_wide(grad_output, side, rows, cols, lo, hi, out_dtype):
         res = _mask_backward_v([grad_output], [side], [rows], cols, lo, hi, code, True, None, out_dtype)
         if res is not None:
             return res[0]
-    g = _aligned(grad_output if grad_output.dtype == torch.float32 else grad_output.float())
-    gx = torch.empty(g.shape, dtype=out_dtype, device=g.device)
-    rc = _launch(g, _lib.lib().fq_ste_bwd_mask_wide, g.data_ptr(), gx.data_ptr(), rows, *_side_ptrs(side, rows), None, None, 0, None, None,
-                 cols, float(lo), float(hi), code)
+    g, gx, slot = _mask_slot(grad_output, side, rows, False, out_dtype)
+    rc = _launch(g, _lib.lib().fq_ste_bwd_mask_wide, *slot, None, None, 0, None, None, cols, float(lo), float(hi), code)
     _lib.check(rc, "ste_backward_mask_wide")
     return gx
 
@@ -548,10 +565,9 @@ def pair_backward(gw, gx, side_w, side_x, rows_w, rows_x, cols, lo, hi, inplace_
         res = _mask_backward_v([gw, gx], [side_w, side_x], [rows_w, rows_x], cols, lo, hi, code, False, [inplace_w, False])
         if res is not None:
             return res[0], res[1]
-    gw, gx = _aligned(gw), _aligned(gx)
-    ow, ox = (gw if inplace_w else torch.empty_like(gw)), torch.empty_like(gx)
-    rc = _launch(gw, _lib.lib().fq_ste_bwd_mask_pair, gw.data_ptr(), ow.data_ptr(), rows_w, *_side_ptrs(side_w, rows_w),
-                 gx.data_ptr(), ox.data_ptr(), rows_x, *_side_ptrs(side_x, rows_x), cols, lo, hi, code)
+    gw, ow, slot_w = _mask_slot(gw, side_w, rows_w, inplace_w)
+    gx, ox, slot_x = _mask_slot(gx, side_x, rows_x)
+    rc = _launch(gw, _lib.lib().fq_ste_bwd_mask_pair, *slot_w, *slot_x, cols, lo, hi, code)
     if not _served(rc, "quantize_linear_pair_backward"):
         return train_backward(gw, side_w, rows_w, cols, lo, hi, inplace=inplace_w), train_backward(gx, side_x, rows_x, cols, lo, hi)
     return ow, ox
@@ -564,11 +580,9 @@ def pair_backward_wide(gw, gx, side_w, side_x, rows_w, rows_x, cols, lo, hi, out
             return train_backward_wide(gw, side_w, rows_w, cols, lo, hi, out_dtype), None
         return None, train_backward_wide(gx, side_x, rows_x, cols, lo, hi, out_dtype)
     code = _DTYPES.get(out_dtype)
-    gw = _aligned(gw if gw.dtype == torch.float32 else gw.float())
-    gx = _aligned(gx if gx.dtype == torch.float32 else gx.float())
-    ow, ox = torch.empty(gw.shape, dtype=out_dtype, device=gw.device), torch.empty(gx.shape, dtype=out_dtype, device=gx.device)
-    rc = _launch(gw, _lib.lib().fq_ste_bwd_mask_wide, gw.data_ptr(), ow.data_ptr(), rows_w, *_side_ptrs(side_w, rows_w),
-                 gx.data_ptr(), ox.data_ptr(), rows_x, *_side_ptrs(side_x, rows_x), cols, float(lo), float(hi), code)
+    gw, ow, slot_w = _mask_slot(gw, side_w, rows_w, False, out_dtype)
+    gx, ox, slot_x = _mask_slot(gx, side_x, rows_x, False, out_dtype)
+    rc = _launch(gw, _lib.lib().fq_ste_bwd_mask_wide, *slot_w, *slot_x, cols, float(lo), float(hi), code)
     _lib.check(rc, "quantize_pair_backward_wide")
     return ow, ox
 
@@ -625,11 +639,11 @@ def multi_backward(grads, sides, rows, cols, lo, hi, inplace=None):
         out[i] = train_backward(grads[i], sides[i], rows[i], cols, lo, hi, inplace=inplace[i])
         return out
     code = _DTYPES.get(grads[live[0]].dtype)
-    gs = {i: _aligned(grads[i]) for i in live}
+    gs = {}
     arr = (_lib.BwdTensor * len(live))()
     for j, i in enumerate(live):
-        out[i] = gs[i] if inplace[i] else torch.empty_like(gs[i])
-        arr[j] = _lib.BwdTensor(gs[i].data_ptr(), out[i].data_ptr(), rows[i], *_side_ptrs(sides[i], rows[i]))
+        gs[i], out[i], slot = _mask_slot(grads[i], sides[i], rows[i], inplace[i])
+        arr[j] = _lib.BwdTensor(*slot)
     rc = _launch(gs[live[0]], _lib.lib().fq_ste_bwd_mask_multi, len(live), arr, cols, float(lo), float(hi), code, 0)
     if not _served(rc, "quantize_multi_backward"):
         for i in live:
