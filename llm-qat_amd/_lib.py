@@ -32,6 +32,8 @@ EXPORTS = (
 )
 # every symbol include/llmqat_fakequant_train.h declares (the fqt_ family: the training-side entry points, outside the recorded set above)
 TRAIN_EXPORTS = ("fqt_mx_fwd_cols",)
+# every symbol include/llmqat_fakequant_sr.h declares (the fqs_ family: MX fake quantization with stochastic rounding)
+SR_EXPORTS = ("fqs_mx_fwd", "fqs_mx_fwd_cols", "fqs_mx_noise")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -155,6 +157,13 @@ def _bind(L):
     L.fq_mx_gemm.restype = i32
     L.fqt_mx_fwd_cols.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp]
     L.fqt_mx_fwd_cols.restype = i32
+    u64 = ctypes.c_uint64
+    for name in ("fqs_mx_fwd", "fqs_mx_fwd_cols"):
+        f = getattr(L, name)
+        f.argtypes = [vp, vp, i64, i64, i32, i32, i32, u64, u64, vp]
+        f.restype = i32
+    L.fqs_mx_noise.argtypes = [u64, u64, i64, i64, i32, vp]
+    L.fqs_mx_noise.restype = i32
     return L
 
 

@@ -5,7 +5,7 @@ from ._lib import FakeQuantLibraryError
 from .ops import get_semantics, set_semantics
 from .mx_inference import MXLinear, convert_to_mx_inference
 from .utils_quant import (AsymQuantizer, QuantizeLinear, SymQuantizer, conservative, cpp_node, default_group_sizes, default_mx_formats, default_mx_rotate, default_mx_scale_rule, default_mx_ste, default_mx_backward_format, enable_weight_quant_cache, fuse_low_bit_mean,
-                          get_backward_mode, block_rotate, group_quantize, host_node, mx_quantize, mx_quantize_axis,
+                          get_backward_mode, block_rotate, group_quantize, host_node, mx_quantize, mx_quantize_axis, mx_quantize_sr, mx_sr_seed, default_mx_backward_rounding,
                           inplace_weight_grad, pair_kv_hooks, pair_operands, quantize_kv, reset_learned_state, set_backward_mode, share_activation_quant, stats)
 
 __version__ = "0.5.0"
@@ -13,5 +13,5 @@ __all__ = ["SymQuantizer", "AsymQuantizer", "QuantizeLinear", "ops", "set_semant
            "share_activation_quant", "enable_weight_quant_cache", "pair_operands", "quantize_kv", "fuse_low_bit_mean", "inplace_weight_grad", "pair_kv_hooks",
            "conservative", "cpp_node", "host_node", "stats", "reset_learned_state", "allow_cpu_tensors", "FakeQuantLibraryError",
            "group_quantize", "default_group_sizes", "mx_quantize", "default_mx_formats", "block_rotate", "default_mx_rotate", "default_mx_scale_rule", "default_mx_ste",
-           "default_mx_backward_format", "mx_quantize_axis",
+           "default_mx_backward_format", "mx_quantize_axis", "mx_quantize_sr", "mx_sr_seed", "default_mx_backward_rounding",
            "MXLinear", "convert_to_mx_inference"]

@@ -2,6 +2,7 @@
 // argument validation, kernel selection, launches.  No allocation, no synchronisation.
 #include "../../include/llmqat_fakequant.h"
 #include "../../include/llmqat_fakequant_train.h"
+#include "../../include/llmqat_fakequant_sr.h"
 
 #include <hip/hip_runtime.h>
 
@@ -539,9 +540,11 @@ FQ_API int fq_mx_ste_bwd(const void* g, const void* mask, void* gx, int64_t rows
     return by_dtype(dtype, [&](auto dt) { return launch_mx_ste<decltype(dt)::value>(rot, a, st); });
 }
 
-// include/llmqat_fakequant_train.h.  The checks are mx_checks' in mx_checks' order, with the block along the rows: rows % 32 in place of
-// cols % 32, whole 16-byte strips per row, and the grid counted in tiles.  Every check comes before any HIP call.
-FQ_API int fqt_mx_fwd_cols(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, int flags, void* stream) {
+namespace {
+// The checks of the column-axis entry points (fqt_mx_fwd_cols, fqs_mx_fwd_cols): mx_checks' in mx_checks' order, with the block along the
+// rows: rows % 32 in place of cols % 32, whole 16-byte strips per row, and the grid counted in tiles.  CONTINUE with a and row_tiles set,
+// or the entry point's result.  Every check comes before any HIP call.
+int mx_cols_checks(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, int flags, MxColsArgs& a, int64_t& row_tiles) {
     if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
     if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
     if (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
@@ -555,11 +558,70 @@ FQ_API int fqt_mx_fwd_cols(const void* x, void* y, int64_t rows, int64_t cols, i
     if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
     const int64_t row_bytes = cols * esize_of(dtype);
     if (row_bytes % 16 != 0) return fail(FQ_ERR_UNSUPPORTED, "cols=%lld: a row must be whole 16-byte vectors", (long long)cols);
-    const int64_t ncs = row_bytes / 16, nct = (ncs + MXC_TILE_STRIPS - 1) / MXC_TILE_STRIPS, row_tiles = rows / MXC_TILE_ROWS;
+    const int64_t ncs = row_bytes / 16, nct = (ncs + MXC_TILE_STRIPS - 1) / MXC_TILE_STRIPS;
+    row_tiles = rows / MXC_TILE_ROWS;
     if (row_tiles > 0x7FFFFFFF / nct) return fail(FQ_ERR_UNSUPPORTED, "%lld x %lld tiles exceed one launch's grid", (long long)row_tiles, (long long)nct);
-    const MxColsArgs a{x, y, ncs, (uint32_t)nct, rows * row_bytes >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    a = MxColsArgs{x, y, ncs, (uint32_t)nct, rows * row_bytes >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    return CONTINUE;
+}
+MxSrKey sr_key(uint64_t seed, uint64_t stream_id) {
+    return MxSrKey{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
+}
+}  // namespace
+
+// include/llmqat_fakequant_train.h
+FQ_API int fqt_mx_fwd_cols(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, int flags, void* stream) {
+    MxColsArgs a;
+    int64_t row_tiles = 0;
+    if (const int rc = mx_cols_checks(x, y, rows, cols, fmt, dtype, flags, a, row_tiles); rc != CONTINUE) return rc;
     hipStream_t st = (hipStream_t)stream;
     return by_dtype(dtype, [&](auto dt) { return launch_mx_cols<decltype(dt)::value>((flags & FQ_MX_FLAG_CEIL) != 0, a, kMxFmts[fmt], row_tiles, st); });
+}
+
+// include/llmqat_fakequant_sr.h: the two forwards with stochastic rounding.  The checks are the nearest entry points' (mx_checks with the
+// format and the flag bits first; mx_cols_checks), every one before any HIP call; any seed and stream id are valid.
+FQ_API int fqs_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, int flags, uint64_t seed, uint64_t stream_id,
+                      void* stream) {
+    auto first = [&] {
+        if (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
+        if (flags & ~FQ_MX_FLAG_CEIL) return fail(FQ_ERR_ARG, "flag bits 0x%x: stochastic rounding takes FQ_MX_FLAG_CEIL only", (unsigned)(flags & ~FQ_MX_FLAG_CEIL));
+        return 0;
+    };
+    auto pointers = [&] {
+        if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
+        if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+        if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+        return 0;
+    };
+    int64_t nvec = 0;
+    if (const int rc = mx_checks(dtype, rows, cols, false, nvec, first, pointers); rc != CONTINUE) return rc;
+    const MxArgs a{x, y, nullptr, nullptr, nvec, nvec * 16 >= NT_LOAD_MIN_BYTES ? 1 : 0};
+    hipStream_t st = (hipStream_t)stream;
+    return by_dtype(dtype, [&](auto dt) { return launch_mx_sr<decltype(dt)::value>((flags & FQ_MX_FLAG_CEIL) != 0, a, kMxFmts[fmt], sr_key(seed, stream_id), st); });
+}
+
+FQ_API int fqs_mx_fwd_cols(const void* x, void* y, int64_t rows, int64_t cols, int fmt, int dtype, int flags, uint64_t seed, uint64_t stream_id,
+                           void* stream) {
+    MxColsArgs a;
+    int64_t row_tiles = 0;
+    if (const int rc = mx_cols_checks(x, y, rows, cols, fmt, dtype, flags, a, row_tiles); rc != CONTINUE) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return by_dtype(dtype, [&](auto dt) {
+        return launch_mx_sr_cols<decltype(dt)::value>((flags & FQ_MX_FLAG_CEIL) != 0, a, kMxFmts[fmt], sr_key(seed, stream_id), row_tiles, st);
+    });
+}
+
+// host only: no HIP call at all
+FQ_API int fqs_mx_noise(uint64_t seed, uint64_t stream_id, int64_t first, int64_t n, int dtype, uint16_t* out) {
+    if (dtype < 0 || dtype > FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "unknown dtype code %d", dtype);
+    if (dtype == FQ_DTYPE_F64) return fail(FQ_ERR_DTYPE, "float64 is not served by the MX entry points");
+    if (first < 0 || n < 0) return fail(FQ_ERR_SHAPE, "negative range first=%lld n=%lld", (long long)first, (long long)n);
+    if (n > (int64_t)1 << 24) return fail(FQ_ERR_SHAPE, "n=%lld: at most 2^24 elements per call", (long long)n);
+    if (first > INT64_MAX - n) return fail(FQ_ERR_SHAPE, "first + n overflows");
+    if (n == 0) return ok();
+    if (!out) return fail(FQ_ERR_NULL, "out must not be NULL");
+    mx_sr_host_noise(sr_key(seed, stream_id), first, n, 16 / esize_of(dtype), out);
+    return ok();
 }
 
 // Every check comes before any HIP call.

@@ -239,6 +239,15 @@ struct MxColsArgs {
     int ntl;         // non-temporal loads, as MxArgs
 };
 template <int DT> FQ_HIDDEN int launch_mx_cols(bool ceil, MxColsArgs a, MxFmt f, int64_t row_tiles, hipStream_t st);
+// the two MX forwards with stochastic rounding (fq_mx_sr.h / fq_mx_sr.hip): key and stream of the Philox4x32-10 counter, whose counter
+// is the flat element index >> 3
+struct MxSrKey {
+    uint32_t k0, k1;   // seed: low, high word
+    uint32_t s0, s1;   // stream id: low, high word
+};
+template <int DT> FQ_HIDDEN int launch_mx_sr(bool ceil, MxArgs a, MxFmt f, MxSrKey k, hipStream_t st);
+template <int DT> FQ_HIDDEN int launch_mx_sr_cols(bool ceil, MxColsArgs a, MxFmt f, MxSrKey k, int64_t row_tiles, hipStream_t st);
+FQ_HIDDEN void mx_sr_host_noise(MxSrKey k, int64_t first, int64_t n, int epv, uint16_t* out);   // host only: the kernels' noise, restated
 // MX block-scaled GEMM (fq_mx_gemm.h / fq_mx_gemm.hip): out[m, n] = sum_k A[m, k] * W[n, k] over two MX exports
 struct MxGemmArgs {
     const uint8_t* we;   // W: [N, K] element codes, E8M0 scales [N, K / 32]

@@ -1025,8 +1025,11 @@ MX_ROTATE = 64
 # "ceil" is the smallest E with amax * 2^-E <= max-normal, under which nothing does.  The saturation mask (return_mask) has one bit per
 # element, bit i & 7 of byte i >> 3 for flat element i, 0 where saturation changed the rounded value; mx_ste_backward applies it.
 MX_SCALE_RULES = ("floor", "ceil")
+# mx_quantize_sr: the same two launches with stochastic rounding onto the element grid -- each element goes to one of its
+# two grid neighbours with the probabilities that make the result unbiased -- for the gradient operand of the backward GEMMs.  The noise is
+# Philox4x32-10 on (seed, stream, flat element index), computed inside the kernels (fqs_mx_fwd / fqs_mx_fwd_cols of the third header).
 mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm_launch": 0, "mx_gemm_skinny": 0, "mx_gemm_tiled": 0,
-             "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0, "mx_cols_launch": 0}
+             "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0, "mx_cols_launch": 0, "mx_sr_launch": 0, "mx_sr_cols_launch": 0}
 
 
 def _mx_format(fmt):
@@ -1095,14 +1098,19 @@ def _mx_aligned(t, count):
     return t.clone() if t.is_contiguous() else t.contiguous()
 
 
-def _mx_input(x, fmt, what, rotate=False, axis=-1):
+def _mx_input(x, fmt, what, rotate=False, axis=-1, as_given=False):
     """The input checks of every MX launch, in their order: format (None: the call has none) and shape for `axis`, the rotation's shape,
     type / device / dtype, then the copy route -> (tensor to launch on, format code, dtype code, the axis its blocks run along).  The
-    column kernel takes a contiguous, aligned tensor of whole 16-byte rows: any other comes back transposed, for the row kernel (-1)."""
+    column kernel takes a contiguous, aligned tensor of whole 16-byte rows: any other comes back transposed, for the row kernel (-1).
+    as_given (the stochastic forms, whose noise is indexed on the tensor as it is given): nothing is transposed -- along -2 a last dimension
+    that is not whole 16-byte vectors is refused, and a non-contiguous or misaligned input takes the one copy of the last axis."""
     code = None
     if isinstance(x, torch.Tensor):
         if axis == -2:
             code = check_mx_cols(tuple(x.shape), fmt, what)
+            if as_given and (x.shape[-1] * x.element_size()) % 16:
+                raise ValueError(f"{what}: axis=-2 needs a last dimension of whole 16-byte vectors ({16 // x.element_size()} elements of {x.dtype}), "
+                                 f"got {x.shape[-1]}: the noise is indexed on the tensor as given, so the transposed route does not serve it")
         elif fmt is not None:
             code = check_mx(tuple(x.shape), fmt)
         if rotate:
@@ -1110,7 +1118,7 @@ def _mx_input(x, fmt, what, rotate=False, axis=-1):
     dt = _prep(x, what)
     if dt == _lib.DTYPE_F64:
         raise NotImplementedError(f"{what}: float64 is not served by the MX formats (float32, bfloat16, float16 are)")
-    if axis == -2 and (not x.is_contiguous() or x.data_ptr() & 15 or (x.shape[-1] * x.element_size()) % 16):
+    if axis == -2 and not as_given and (not x.is_contiguous() or x.data_ptr() & 15 or (x.shape[-1] * x.element_size()) % 16):
         mx_counts["mx_copy_route"] += 1
         x, axis = x.transpose(-1, -2).contiguous(), -1
     return _mx_aligned(x, True), code, dt, axis
@@ -1175,6 +1183,33 @@ def mx_quantize(x, fmt, rotate=False, scale_rule="floor", return_mask=False):
     scale_rule="ceil": the shared exponent under which no element of a finite block saturates.  return_mask=True -> (y, mask): mask is a
     uint8 tensor of numel / 8 bytes written by the same launch, a 0 bit where saturation changed the element (of x R under rotate)."""
     return _mx_quantize(x, fmt, rotate, scale_rule, return_mask, -1)
+
+
+def check_mx_sr_word(value, name, what="mx_quantize_sr"):
+    """-> value, a Python int in [0, 2^64) (a seed or a stream id of the stochastic forms); ValueError for anything else, bools included"""
+    if not isinstance(value, int) or isinstance(value, bool) or not 0 <= value < 1 << 64:
+        raise ValueError(f"{what}: {name} must be a Python int in [0, 2**64), got {value!r}")
+    return value
+
+
+def mx_quantize_sr(x, fmt, seed, stream=0, scale_rule="floor", axis=-1):
+    """mx_quantize_axis with STOCHASTIC rounding onto the element grid: every element becomes one of its two grid
+    neighbours, the upper one with probability (distance to the lower) / (their distance) in steps of 2^-16, so E[y] = x where nearest
+    rounding sends every element below half a quantum to zero -- the rule for a gradient.  Values on the grid are unchanged.  Under
+    scale_rule="ceil" nothing saturates and the whole block is unbiased; under "floor" the top binade of a block still clips.
+    The noise is Philox4x32-10 on (seed, stream, flat index of the element in the contiguous tensor): Python ints in [0, 2^64), the same
+    pair gives the same bits.  A non-contiguous or misaligned input is copied once (mx_copy_route) and gives the bits of its contiguous
+    equal; along axis=-2 the last dimension must be whole 16-byte vectors (ValueError).  One launch (mx_sr_launch / mx_sr_cols_launch);
+    no rotation, no mask.  -> a new contiguous tensor of x's shape and dtype."""
+    what = "mx_quantize_sr"
+    down = isinstance(x, torch.Tensor) and check_mx_axis(x.dim(), axis, what) == -2
+    flags = check_mx_scale_rule(scale_rule, what)
+    seed, stream = check_mx_sr_word(seed, "seed"), check_mx_sr_word(stream, "stream")
+    x, code, dt, _ = _mx_input(x, fmt, what, False, -2 if down else -1, True)
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    entry, counter = ("fqs_mx_fwd_cols", "mx_sr_cols_launch") if down else ("fqs_mx_fwd", "mx_sr_launch")
+    _mx_launch(what, entry, counter, x, (x.data_ptr(), y.data_ptr()), code, dt, flags, seed, stream)
+    return y
 
 
 def check_mx_ste(g_shape, mask_shape, mask_dtype, rotate):

@@ -445,7 +445,8 @@ def group_quantize(x, clip_val, num_bits, group_size, symmetric=True):
 
 # what the QuantizeLinears constructed from now on take for the settings they are not given explicitly (the default_* setters below):
 # (weight, activation) group sizes, (weight, activation) MX formats, and the MX operands' rotation, scale rule and gradient
-_DEFAULTS = {"groups": (None, None), "mx": (None, None), "mx_rotate": False, "mx_scale_rule": "floor", "mx_ste": "identity", "mx_backward": None}
+_DEFAULTS = {"groups": (None, None), "mx": (None, None), "mx_rotate": False, "mx_scale_rule": "floor", "mx_ste": "identity", "mx_backward": None,
+             "mx_backward_rounding": None}
 
 
 def _set_default(name, value):
@@ -579,6 +580,76 @@ def mx_quantize_axis(x, fmt, rotate=False, scale_rule="floor", ste="identity", a
     return _mx_apply(x, fmt, bool(rotate), scale_rule, ste, _mx_check(x, fmt, rotate, scale_rule, ste, axis))
 
 
+class _MXQuantizerSR(torch.autograd.Function):
+    """ops.mx_quantize_sr, straight-through: nothing is saved and the gradient is the incoming one itself (no launch backward)."""
+
+    @staticmethod
+    def forward(ctx, x, fmt, seed, stream, scale_rule, axis):
+        ctx.set_materialize_grads(False)
+        return ops.mx_quantize_sr(x, fmt, seed, stream, scale_rule, axis)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return grad_output, None, None, None, None, None
+
+
+def mx_quantize_sr(x, fmt, seed, stream=0, scale_rule="floor", axis=-1):
+    """MX fake quantization with stochastic rounding: as mx_quantize_axis, but every element goes to one of its two
+    grid neighbours with the probabilities that make the result unbiased (E[y] = x; exactly so under scale_rule="ceil", under "floor" the
+    top binade of a block still clips) -- the rounding for a gradient operand.  The noise is Philox4x32-10 on (seed, stream, flat element
+    index): Python ints in [0, 2^64); the same pair reproduces the result bit for bit.  Same shape and dtype as x, contiguous; the gradient
+    is the identity and costs no launch.  Along axis=-2 the last dimension must be whole 16-byte vectors.  Not served while torch.compile
+    traces (NotImplementedError).  A launch captured into a hipGraph carries its seed and stream, so every replay repeats its noise."""
+    if torch.compiler.is_compiling():
+        raise NotImplementedError("mx_quantize_sr is not served while torch.compile traces (seed and stream would be baked into the graph): "
+                                  "call it eagerly")
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"mx_quantize_sr: expected a torch.Tensor, got {type(x).__name__}")
+    return _MXQuantizerSR.apply(x, fmt, seed, stream, scale_rule, axis)
+
+
+# The noise of the module path (QuantizeLinear(mx_backward_rounding="stochastic")): one process seed and one process-wide stream counter.
+# Every stochastic launch of a module backward takes the counter's next value under the lock, Qr(g) before Qc(g) within a backward, so a
+# fixed program with a fixed seed reproduces bit for bit.  Data-parallel ranks should be given different seeds by the caller.
+_sr_lock = threading.Lock()
+_sr_state = {"seed": None, "next": 0}
+
+
+def mx_sr_seed(seed):
+    """Set the seed of the stochastic backward roundings of this process and reset their stream counter to 0.  -> the previous seed (None
+    if none was set; then the first stochastic backward would have taken torch.initial_seed() & (2^64 - 1))."""
+    ops.check_mx_sr_word(seed, "seed", "mx_sr_seed")
+    with _sr_lock:
+        prev, _sr_state["seed"], _sr_state["next"] = _sr_state["seed"], seed, 0
+    return prev
+
+
+def _sr_next():
+    """-> (seed, stream id) of the next stochastic launch of a module backward"""
+    with _sr_lock:
+        if _sr_state["seed"] is None:
+            _sr_state["seed"] = torch.initial_seed() & ((1 << 64) - 1)
+        stream = _sr_state["next"]
+        _sr_state["next"] = (stream + 1) & ((1 << 64) - 1)
+        return _sr_state["seed"], stream
+
+
+MX_BACKWARD_ROUNDINGS = ("nearest", "stochastic")
+
+
+def _check_mx_backward_rounding(mode, what="mx_backward_rounding"):
+    if mode is not None and (not isinstance(mode, str) or mode not in MX_BACKWARD_ROUNDINGS):
+        raise ValueError(f"{what}: unknown rounding {mode!r}: one of {', '.join(MX_BACKWARD_ROUNDINGS)} (or None)")
+
+
+def default_mx_backward_rounding(mode):
+    """The rounding ("nearest" / "stochastic", None: nearest) the QuantizeLinears constructed from now on take for the gradient operand of
+    their MX backward GEMMs when their own mx_backward_rounding is not given.  Applies only to layers that have a backward format
+    (mx_backward_format or its process default).  -> the previous mode."""
+    _check_mx_backward_rounding(mode, "default_mx_backward_rounding")
+    return _set_default("mx_backward_rounding", mode)
+
+
 def default_mx_formats(weight=None, act=None):
     """MX formats the QuantizeLinears constructed from now on take for the operands they quantize (w_bits < 32 / a_bits < 32, not
     layerwise, no explicit group size) when their own weight_format / act_format are not given (None: the integer quantizers).  Lets
@@ -636,11 +707,15 @@ class _MXLinearBackward(torch.autograd.Function):
         dX = Qr(g) Qc(W)         both blocked along `out`
         dW = Qc(g)^T Qc(x)       both blocked along the tokens (zero rows pad them to a multiple of 32: no amax and no sum changes)
     The operands quantized backward are the ORIGINAL x and W cast to the output's dtype, as the microscaling emulation libraries do, so x
-    and W themselves are what is saved.  An operand of a gradient nobody needs is not quantized."""
+    and W themselves are what is saved.  An operand of a gradient nobody needs is not quantized.
+    stochastic: the two quantizations of the gradient operand, Qr(g) and then Qc(g) (after the zero-row padding),
+    round stochastically (ops.mx_quantize_sr), each on the process seed and the next stream id (_sr_next); Qc(W) and Qc(x) stay nearest.
+    The launches stay one row-kernel and three column-kernel launches and two GEMMs."""
 
     @staticmethod
-    def forward(ctx, x, w, weight_format, act_format, scale_rule, fb):
+    def forward(ctx, x, w, weight_format, act_format, scale_rule, fb, stochastic):
         ctx.cfg = (fb, scale_rule)
+        ctx.stochastic = stochastic
         ctx.save_for_backward(x, w)
         wq = ops.mx_quantize(w, weight_format, scale_rule=scale_rule)
         return nn.functional.linear(ops.mx_quantize(x, act_format, scale_rule=scale_rule), wq)
@@ -655,8 +730,14 @@ class _MXLinearBackward(torch.autograd.Function):
         with torch.autocast("cuda", enabled=False):   # every operand is cast to d explicitly
             d = g.dtype
             g2 = g.reshape(-1, w.shape[0]).contiguous()
+            if ctx.stochastic:
+                def qg(t, axis):
+                    return ops.mx_quantize_sr(t, fb, *_sr_next(), scale_rule=rule, axis=axis)
+            else:
+                def qg(t, axis):
+                    return ops.mx_quantize_axis(t, fb, scale_rule=rule, axis=axis)
             if need_x:
-                gx2 = torch.matmul(ops.mx_quantize(g2, fb, scale_rule=rule), ops.mx_quantize_axis(w.to(d), fb, scale_rule=rule, axis=-2))
+                gx2 = torch.matmul(qg(g2, -1), ops.mx_quantize_axis(w.to(d), fb, scale_rule=rule, axis=-2))
                 gx = gx2.reshape(x.shape).to(x.dtype)
             if need_w:
                 x2 = x.reshape(-1, w.shape[1]).to(d)
@@ -664,8 +745,8 @@ class _MXLinearBackward(torch.autograd.Function):
                 if pad:
                     ops.mx_counts["mx_copy_route"] += 1
                     g2, x2 = nn.functional.pad(g2, (0, 0, 0, pad)), nn.functional.pad(x2, (0, 0, 0, pad))
-                gw = torch.matmul(ops.mx_quantize_axis(g2, fb, scale_rule=rule, axis=-2).t(), ops.mx_quantize_axis(x2, fb, scale_rule=rule, axis=-2)).to(w.dtype)
-        return gx, gw, None, None, None, None
+                gw = torch.matmul(qg(g2, -2).t(), ops.mx_quantize_axis(x2, fb, scale_rule=rule, axis=-2)).to(w.dtype)
+        return gx, gw, None, None, None, None, None
 
 
 class _LowBitWeight(torch.autograd.Function):
@@ -1393,10 +1474,11 @@ class QuantizeLinear(nn.Linear):
     mx_scale_rule = "floor"    # shared-exponent rule of the MX operands ("ceil": nothing saturates) and their gradient ("clip": zero where
     mx_ste = "identity"        # saturation changed the element); plain attributes
     mx_backward_format = None  # an MX format: the two backward GEMMs run on operands quantized along their contraction axes (a plain attribute)
+    mx_backward_rounding = None   # "nearest" (None) / "stochastic": the rounding of the gradient operand of those GEMMs (a plain attribute)
 
     def __init__(self, *kargs, symmetric=True, bias=False, w_bits=32, a_bits=32, act_layerwise=False,
                  weight_layerwise=False, weight_group_size=None, act_group_size=None, weight_format=None, act_format=None, mx_rotate=None,
-                 mx_scale_rule=None, mx_ste=None, mx_backward_format=None):
+                 mx_scale_rule=None, mx_ste=None, mx_backward_format=None, mx_backward_rounding=None):
         super().__init__(*kargs, bias=False)  # `bias` is accepted and ignored, as in the reference (:176)
         self.w_bits = w_bits
         self.a_bits = a_bits
@@ -1447,6 +1529,14 @@ class QuantizeLinear(nn.Linear):
             self.mx_backward_format = mx_backward_format
         elif _DEFAULTS["mx_backward"] is not None and why is None:
             self.mx_backward_format = _DEFAULTS["mx_backward"]
+        # the rounding of the gradient operand: an explicit value needs a backward format in force; the process default
+        # (default_mx_backward_rounding) applies to the layers that have one
+        _check_mx_backward_rounding(mx_backward_rounding)
+        if mx_backward_rounding is not None and self.mx_backward_format is None:
+            raise ValueError("mx_backward_rounding applies to the MX backward GEMMs: this layer has no mx_backward_format in force")
+        mode = _explicit_else(mx_backward_rounding, _DEFAULTS["mx_backward_rounding"], self.mx_backward_format is not None)
+        if mode is not None:
+            self.mx_backward_rounding = mode
         # group sizes: an explicit argument is checked and kept; the process default (default_group_sizes) applies where it means something
         # (an operand without an MX format, of a bit width the group quantizer serves, not layerwise)
         dw, da = _DEFAULTS["groups"]
@@ -1700,7 +1790,8 @@ class QuantizeLinear(nn.Linear):
             why = _mx_backward_refusal(self)   # (the settings are plain attributes: one may have been assigned since the constructor)
             if why is not None:
                 raise ValueError(f"mx_backward_format: {why}")
-            return self._add_bias(_MXLinearBackward.apply(input_, self.weight, self.weight_format, self.act_format, self.mx_scale_rule, self.mx_backward_format))
+            return self._add_bias(_MXLinearBackward.apply(input_, self.weight, self.weight_format, self.act_format, self.mx_scale_rule, self.mx_backward_format,
+                                                          self.mx_backward_rounding == "stochastic"))
         route, weight = self._weight_route(), self.weight
         if route == "low" and self.weight_group_size is not None:
             route = "group"    # (a group size ASSIGNED to a 1-/2-bit layer -- the constructor refuses one: this path alone has always honoured it)
