@@ -91,6 +91,14 @@ int mx_checks(int dtype, int64_t rows, int64_t cols, bool rot, int64_t& nvec, Fi
     return CONTINUE;
 }
 
+// the `pointers` of an MX entry point that reads x and writes y: 0 or the refusal
+int mx_xy_pointers(const void* x, const void* y) {
+    if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
+    if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
+    if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+    return 0;
+}
+
 template <bool ASYM>
 int rowwise(const void* x, void* y, int32_t* idx, float* scale, float* bounds, int64_t rows, int64_t cols, int bits, int dtype,
             int sem, void* ws, size_t wsb, void* stream, const MaskArgs* mk = nullptr, const fq_rows_view* xv = nullptr,
@@ -553,9 +561,7 @@ int mx_cols_checks(const void* x, void* y, int64_t rows, int64_t cols, int fmt, 
     if (rows % 32 != 0) return fail(FQ_ERR_SHAPE, "rows=%lld is not a multiple of the 32-element MX block", (long long)rows);
     if (cols > 0 && rows > INT64_MAX / 4 / cols) return fail(FQ_ERR_SHAPE, "rows * cols overflows");
     if (rows == 0 || cols == 0) return ok();
-    if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
-    if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
-    if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
+    if (const int rc = mx_xy_pointers(x, y)) return rc;
     const int64_t row_bytes = cols * esize_of(dtype);
     if (row_bytes % 16 != 0) return fail(FQ_ERR_UNSUPPORTED, "cols=%lld: a row must be whole 16-byte vectors", (long long)cols);
     const int64_t ncs = row_bytes / 16, nct = (ncs + MXC_TILE_STRIPS - 1) / MXC_TILE_STRIPS;
@@ -587,14 +593,8 @@ FQ_API int fqs_mx_fwd(const void* x, void* y, int64_t rows, int64_t cols, int fm
         if (flags & ~FQ_MX_FLAG_CEIL) return fail(FQ_ERR_ARG, "flag bits 0x%x: stochastic rounding takes FQ_MX_FLAG_CEIL only", (unsigned)(flags & ~FQ_MX_FLAG_CEIL));
         return 0;
     };
-    auto pointers = [&] {
-        if (!x || !y) return fail(FQ_ERR_NULL, "x / y must not be NULL");
-        if (x == y) return fail(FQ_ERR_ARG, "in-place (y == x) is not supported");
-        if (!aligned16(x) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "pointers must be 16-byte aligned");
-        return 0;
-    };
     int64_t nvec = 0;
-    if (const int rc = mx_checks(dtype, rows, cols, false, nvec, first, pointers); rc != CONTINUE) return rc;
+    if (const int rc = mx_checks(dtype, rows, cols, false, nvec, first, [&] { return mx_xy_pointers(x, y); }); rc != CONTINUE) return rc;
     const MxArgs a{x, y, nullptr, nullptr, nvec, nvec * 16 >= NT_LOAD_MIN_BYTES ? 1 : 0};
     hipStream_t st = (hipStream_t)stream;
     return by_dtype(dtype, [&](auto dt) { return launch_mx_sr<decltype(dt)::value>((flags & FQ_MX_FLAG_CEIL) != 0, a, kMxFmts[fmt], sr_key(seed, stream_id), st); });

@@ -60,15 +60,26 @@ __device__ __forceinline__ int mx_shared_exp_ceil(uint32_t ab, int emax, float m
     return e < -127 ? -127 : (e > 127 ? 127 : e);
 }
 
-// one element of a finite block, step 1: t = v * 2^-E (nE = -E; exact: t only underflows far below the grid) in units of its quantum,
-// rounded to nearest-even (v_rndne_f32).  bmin = emin + 127, the biased exponent of the smallest normal binade; sb <- the biased exponent
-// of t's binade, at least bmin (the subnormals share the smallest normal binade's quantum).
-__device__ __forceinline__ float mx_rint(float v, int nE, int bmin, int mbits, int& sb) {
+// what the element chain needs of a block, from the fp32 bits of its amax (NaN sorts above Inf): bad = a NaN or Inf in the block,
+// nE = -E, yk = E - 127 - mbits, maxx = max-normal * 2^E (exact)
+template <bool CEIL> __device__ __forceinline__ void mx_block_consts(uint32_t ab, const MxFmt& f, bool& bad, int& nE, int& yk, float& maxx) {
+    bad = ab >= 0x7F800000u;
+    const int E = CEIL ? mx_shared_exp_ceil(ab, f.emax, f.maxnorm) : mx_shared_exp(ab, f.emax);
+    nE = -E, yk = E - 127 - f.mbits;
+    maxx = __builtin_amdgcn_ldexpf(f.maxnorm, E);
+}
+
+// one element of a finite block, step 1, shared by both rounding rules: -> t = v * 2^-E (nE = -E; exact: t only underflows far below
+// the grid) in units of its quantum.  bmin = emin + 127, the biased exponent of the smallest normal binade; sb <- the biased exponent of
+// t's binade, at least bmin (the subnormals share the smallest normal binade's quantum).
+__device__ __forceinline__ float mx_quanta(float v, int nE, int bmin, int mbits, int& sb) {
     const float t = __builtin_amdgcn_ldexpf(v, nE);
     const int e = (int)((as_u(t) >> 23) & 0xFFu);                          // 0 for a subnormal t
     sb = e > bmin ? e : bmin;
-    return __builtin_rintf(__builtin_amdgcn_ldexpf(t, 127 + mbits - sb));
+    return __builtin_amdgcn_ldexpf(t, 127 + mbits - sb);
 }
+// ... rounded to nearest-even (v_rndne_f32); the stochastic rule is mx_rint_sr (fq_mx_sr.h)
+__device__ __forceinline__ float mx_rint(float v, int nE, int bmin, int mbits, int& sb) { return __builtin_rintf(mx_quanta(v, nE, bmin, mbits, sb)); }
 
 // step 2 (forward): y = q * 2^E from r (yk = E - 127 - mbits), saturated at maxx = max-normal * 2^E (exact), with the input's sign
 __device__ __forceinline__ float mx_value(float v, float r, int sb, int yk, float maxx) {
@@ -127,6 +138,15 @@ template <int EPV> __device__ __forceinline__ void mx_rotate(float (&v)[EPV], ui
     for (int e = 0; e < EPV; ++e) v[e] = v[e] * 0.125f;
 }
 
+// fp32 bits of max|x| over the elements of one loaded vector
+template <int DT> __device__ __forceinline__ uint32_t mx_vec_absmax(const uint4& r) {
+    using T = Ty<DT>;
+    return T::absmax_finish(T::absmax_acc(T::absmax_acc(T::absmax_acc(T::absmax_acc(0u, r.x), r.y), r.z), r.w));
+}
+
+// workgroups of a launch of the row kernels: MX_VPT vectors per lane
+inline unsigned mx_rows_grid(int64_t nvec) { return (unsigned)((nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT)); }
+
 template <int DT, int KIND, int VPT, bool ROT, bool MASK, bool CEIL>
 __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
     using T = Ty<DT>;
@@ -175,17 +195,12 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
 #pragma unroll
             for (int e = 0; e < EPV; ++e) acc = Ty<F32>::absmax_acc(acc, as_u(xr[e]));
         } else {
-            acc = T::absmax_acc(acc, r[i].x);
-            acc = T::absmax_acc(acc, r[i].y);
-            acc = T::absmax_acc(acc, r[i].z);
-            acc = T::absmax_acc(acc, r[i].w);
-            acc = T::absmax_finish(acc);
+            acc = mx_vec_absmax<DT>(r[i]);
         }
-        const uint32_t ab = group_reduce<OpMaxU>(acc, BV);   // fp32 bits of the block's amax (NaN sorts above Inf)
-        const bool bad = ab >= 0x7F800000u;                   // a NaN or Inf in the block
-        const int E = CEIL ? mx_shared_exp_ceil(ab, f.emax, f.maxnorm) : mx_shared_exp(ab, f.emax);
-        const int nE = -E, yk = E - 127 - f.mbits;
-        const float maxx = __builtin_amdgcn_ldexpf(f.maxnorm, E);
+        bool bad;
+        int nE, yk;
+        float maxx;
+        mx_block_consts<CEIL>(group_reduce<OpMaxU>(acc, BV), f, bad, nE, yk, maxx);   // the block's amax: a DPP max over its BV lanes
         if constexpr (KIND == MX_FWD) {
             uint32_t o[4];
             uint32_t keep = 0;   // MASK: bit e set = the lane's element e was not changed by the saturation
@@ -255,40 +270,37 @@ __global__ __launch_bounds__(MX_TPB) void mx_kernel(MxArgs a, MxFmt f) {
                     if constexpr (EPV == 8) __builtin_nontemporal_store(b, (uint32_t*)(a.elems + v * 4));
                     else __builtin_nontemporal_store((uint16_t)b, (uint16_t*)(a.elems + v * 2));
                 }
-                if ((threadIdx.x & (BV - 1)) == 0) a.scales[v / BV] = bad ? (uint8_t)0xFF : (uint8_t)(E + 127);
+                if ((threadIdx.x & (BV - 1)) == 0) a.scales[v / BV] = bad ? (uint8_t)0xFF : (uint8_t)(127 - nE);
             }
         }
     }
 }
 
+// mx_ste_kernel's loads: the lane's VPT vectors of g, clamped as load_clamped clamps, and in the low bits of m[i] the EPV mask bits of
+// vector i -- bits (v % BV) * EPV .. of mask word v / BV
+template <bool NT, int DT, int VPT> __device__ __forceinline__ void mx_ste_load(const MxSteArgs& a, int64_t base, uint4 (&r)[VPT], uint32_t (&m)[VPT]) {
+    constexpr int EPV = 16 / Ty<DT>::ESIZE, BV = 32 / EPV;
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const int64_t v = base + i * MX_TPB, c = v < a.nvec ? v : a.nvec - 1;
+        r[i] = ld16<NT>(&((const uint4*)a.g)[c]);
+        m[i] = a.mask[c / BV] >> ((uint32_t)(c & (BV - 1)) * EPV);
+    }
+}
+
 // gx = g where the mask bit is 1, else +0.0 (a select on the bit patterns: a NaN g at a masked position gives +0.0); ROT: the masked
-// values times R, rounded once.  Loads, slots and stores as mx_kernel; a lane's EPV bits are bits (v % BV) * EPV .. of mask word v / BV.
+// values times R, rounded once.  Slots and stores as mx_kernel.
 template <int DT, int VPT, bool ROT>
 __global__ __launch_bounds__(MX_TPB) void mx_ste_kernel(MxSteArgs a) {
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE;
-    constexpr int BV = 32 / EPV;
     const uint32_t slot = ROT ? mx_rot_slot<EPV>(threadIdx.x) : threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * (MX_TPB * VPT) + slot;
-    const uint4* gv = (const uint4*)a.g;
 
     uint4 r[VPT];
     uint32_t m[VPT];
-    if (a.ntl) {
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int64_t v = base + i * MX_TPB, c = v < a.nvec ? v : a.nvec - 1;
-            r[i] = ld16<true>(&gv[c]);
-            m[i] = a.mask[c / BV] >> ((uint32_t)(c & (BV - 1)) * EPV);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int64_t v = base + i * MX_TPB, c = v < a.nvec ? v : a.nvec - 1;
-            r[i] = ld16<false>(&gv[c]);
-            m[i] = a.mask[c / BV] >> ((uint32_t)(c & (BV - 1)) * EPV);
-        }
-    }
+    if (a.ntl) mx_ste_load<true, DT>(a, base, r, m);
+    else mx_ste_load<false, DT>(a, base, r, m);
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
         const int64_t v = base + i * MX_TPB;
@@ -325,8 +337,7 @@ __global__ __launch_bounds__(MX_TPB) void mx_ste_kernel(MxSteArgs a) {
 
 template <int DT, int KIND, bool ROT = false, bool MASK = false, bool CEIL = false>
 static void launch_mx_kind(const MxArgs& a, const MxFmt& f, hipStream_t st) {
-    const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
-    launch(mx_kernel<DT, KIND, MX_VPT, ROT, MASK, CEIL>, dim3((unsigned)grid), dim3(MX_TPB), st, a, f);
+    launch(mx_kernel<DT, KIND, MX_VPT, ROT, MASK, CEIL>, dim3(mx_rows_grid(a.nvec)), dim3(MX_TPB), st, a, f);
 }
 template <int DT, bool ROT, bool CEIL> static void launch_mx_rule(int kind, bool mask, const MxArgs& a, const MxFmt& f, hipStream_t st) {
     if (kind == MX_FWD && mask) launch_mx_kind<DT, MX_FWD, ROT, true, CEIL>(a, f, st);
@@ -349,9 +360,9 @@ template <int DT> int launch_mx(int kind, bool rot, bool ceil, bool mask, MxArgs
 // a validated by fq_mx_ste_bwd (nvec > 0, grid within limits; rot: whole runs)
 template <int DT> int launch_mx_ste(bool rot, MxSteArgs a, hipStream_t st) {
     begin_launches();
-    const int64_t grid = (a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT);
-    if (rot) launch(mx_ste_kernel<DT, MX_VPT, true>, dim3((unsigned)grid), dim3(MX_TPB), st, a);
-    else launch(mx_ste_kernel<DT, MX_VPT, false>, dim3((unsigned)grid), dim3(MX_TPB), st, a);
+    const dim3 grid(mx_rows_grid(a.nvec));
+    if (rot) launch(mx_ste_kernel<DT, MX_VPT, true>, grid, dim3(MX_TPB), st, a);
+    else launch(mx_ste_kernel<DT, MX_VPT, false>, grid, dim3(MX_TPB), st, a);
     return launch_result();
 }
 

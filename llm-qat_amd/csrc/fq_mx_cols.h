@@ -1,17 +1,22 @@
 // fq_mx_cols.h -- MX block-scaled fake quantization with the blocks running down the columns: the block of a
 // contiguous [rows, cols] tensor is the 32 elements (32k .. 32k + 31, c) of one column, which is what a GEMM that contracts over axis 0
 // needs (dX = dY W over `out`, dW = dY^T X over the tokens).  Per block the arithmetic is mx_kernel's, through the same helpers of
-// fq_mx.h (mx_shared_exp / mx_shared_exp_ceil, mx_rint, mx_value): the result is the row kernel's on the transposed tensor, bit for bit.
+// fq_mx.h (mx_block_consts, mx_rint, mx_value): the result is the row kernel's on the transposed tensor, bit for bit.
 //
-//   mx_cols_kernel   one pass, no LDS, no barrier.  A workgroup covers MXC_TILE_ROWS = 32 rows (one block of every column) by
-//                    MXC_TILE_STRIPS = 64 column strips of 16 bytes; each of its four waves holds 16 neighbouring strips.  Lane l of a wave owns
-//                    strip l & 15 and the 8 rows (l >> 4) * 8 .. + 7: 8 vectors in flight, and every row segment a wave touches is 256
-//                    contiguous bytes (1 KiB for the workgroup).  A vector holds 16 / esize columns, so a lane carries that many
-//                    independent blocks; their absmaxes stay packed as in the row kernels (two 16-bit patterns per dword), are folded
-//                    over the lane's 8 rows in registers and over the four row groups -- lanes l, l ^ 16, l ^ 32, l ^ 48 -- with
-//                    v_permlane16_swap and v_permlane32_swap.  The amax never leaves the registers.
-// Strips past the last one re-load the last strip (the tile's rows are always whole: rows is a multiple of 32); such a lane's partners hold
-// the same strip, so it only ever meets lanes that are not stored either.  Only stores are predicated.
+// The column tile, in stages that the nearest kernel here and the stochastic one (mx_sr_cols_kernel, fq_mx_sr.h) both call (DESIGN.md
+// section 20); each kernel keeps its own loop nest over the loaded tile:
+//   mx_cols_load     A workgroup covers MXC_TILE_ROWS = 32 rows (one block of every column) by MXC_TILE_STRIPS = 64 column strips of
+//                    16 bytes; each of its four waves holds 16 neighbouring strips.  Lane l of a wave owns strip l & 15 and the 8 rows
+//                    (l >> 4) * 8 .. + 7: 8 vectors in flight, and every row segment a wave touches is 256 contiguous bytes (1 KiB for
+//                    the workgroup).  A vector holds 16 / esize columns, so a lane carries that many independent blocks; their
+//                    absmaxes stay packed as in the row kernels (two 16-bit patterns per dword) and are folded over the lane's 8 rows
+//                    in registers.  Strips past the last one re-load the last strip (the tile's rows are always whole: rows is a
+//                    multiple of 32); such a lane's partners hold the same strip, so it only ever meets lanes that are not stored
+//                    either.  Only stores are predicated (`live`).
+//   mx_cols_consts   one dword of the strip: the fold over the four row groups -- lanes l, l ^ 16, l ^ 32, l ^ 48 -- with
+//                    v_permlane16_swap and v_permlane32_swap (mx_cols_group_max), then the constants of its one or two columns'
+//                    blocks.  The amax never leaves the registers.
+//   mx_cols_kernel   one pass, no LDS, no barrier: dword by dword, the constants and then the lane's 8 rows in place.
 #pragma once
 #include "fq_mx.h"
 
@@ -31,15 +36,18 @@ template <int DT> __device__ __forceinline__ uint32_t mx_cols_group_max(uint32_t
     return T::absmax_acc(q[0], q[1]);
 }
 
-template <int DT, bool CEIL>
-__global__ __launch_bounds__(MX_TPB) void mx_cols_kernel(MxColsArgs a, MxFmt f) {
+// The lane's place in the tile and its loads.  -> first: the lane's vector of its first row; row i of its RPL rows is first + i * a.ncs.
+// A row is ncs whole vectors, so that is also the flat vector index in the contiguous tensor, which the stochastic kernel takes as its
+// noise index: the tile geometry may change here and nowhere else.  live <- the lane's strip exists (its rows are stored); w <- the
+// lane's RPL vectors as dwords; acc[d] <- the packed absmax of dword d over the lane's rows.
+template <int DT, int RPL> __device__ __forceinline__ int64_t mx_cols_load(const MxColsArgs& a, uint32_t (&w)[RPL][4], uint32_t (&acc)[4], bool& live) {
     using T = Ty<DT>;
-    constexpr int RPL = MXC_TILE_ROWS / MXC_ROW_GROUPS;   // rows per lane
+    static_assert(RPL * MXC_ROW_GROUPS == MXC_TILE_ROWS, "the wave's row groups share the tile's rows");
     const uint32_t rt = blockIdx.x / a.nct, ct = blockIdx.x - rt * a.nct;   // column tiles of one row tile follow one another
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const int64_t strip = (int64_t)ct * MXC_TILE_STRIPS + wave * MXC_WAVE_STRIPS + (lane & (MXC_WAVE_STRIPS - 1));
     const int64_t row = (int64_t)rt * MXC_TILE_ROWS + (lane / MXC_WAVE_STRIPS) * RPL;
-    const bool live = strip < a.ncs;
+    live = strip < a.ncs;
     const int64_t first = row * a.ncs + (live ? strip : a.ncs - 1);
     const uint4* __restrict__ xv = (const uint4*)a.x;
 
@@ -51,30 +59,42 @@ __global__ __launch_bounds__(MX_TPB) void mx_cols_kernel(MxColsArgs a, MxFmt f) 
 #pragma unroll
         for (int i = 0; i < RPL; ++i) r[i] = ld16<false>(&xv[first + i * a.ncs]);
     }
-
-    uint32_t w[RPL][4], acc[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) acc[d] = 0u;
 #pragma unroll
     for (int i = 0; i < RPL; ++i) {
         w[i][0] = r[i].x, w[i][1] = r[i].y, w[i][2] = r[i].z, w[i][3] = r[i].w;
 #pragma unroll
         for (int d = 0; d < 4; ++d) acc[d] = T::absmax_acc(acc[d], w[i][d]);
     }
+    return first;
+}
+
+// accd: mx_cols_load's acc of one dword of the strip -> mx_block_consts of its EPD columns' blocks
+template <int DT, bool CEIL>
+__device__ __forceinline__ void mx_cols_consts(uint32_t accd, const MxFmt& f, bool* bad, int* nE, int* yk, float* maxx) {
+    using T = Ty<DT>;
+    const uint32_t m = mx_cols_group_max<DT>(accd);   // the patterns of the columns' amax
+#pragma unroll
+    for (int k = 0; k < T::EPD; ++k)
+        mx_block_consts<CEIL>(T::EPD == 1 ? m : T::absmax_finish(k ? m >> 16 : m & 0xFFFFu), f, bad[k], nE[k], yk[k], maxx[k]);
+}
+
+template <int DT, bool CEIL>
+__global__ __launch_bounds__(MX_TPB) void mx_cols_kernel(MxColsArgs a, MxFmt f) {
+    using T = Ty<DT>;
+    constexpr int RPL = MXC_TILE_ROWS / MXC_ROW_GROUPS;   // rows per lane
+    uint32_t w[RPL][4], acc[4];
+    bool live;
+    const int64_t first = mx_cols_load<DT, RPL>(a, w, acc, live);
 
     const int bmin = f.emin + 127;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-        const uint32_t m = mx_cols_group_max<DT>(acc[d]);   // dword d of the strip: the patterns of its EPD columns' amax
+        bool bad[T::EPD];
         int nE[T::EPD], yk[T::EPD];
         float maxx[T::EPD];
-        bool bad[T::EPD];
-#pragma unroll
-        for (int k = 0; k < T::EPD; ++k) {
-            const uint32_t ab = T::EPD == 1 ? m : T::absmax_finish(k ? m >> 16 : m & 0xFFFFu);   // fp32 bits of the block's amax
-            bad[k] = ab >= 0x7F800000u;                                                          // a NaN or Inf in the block
-            const int E = CEIL ? mx_shared_exp_ceil(ab, f.emax, f.maxnorm) : mx_shared_exp(ab, f.emax);
-            nE[k] = -E, yk[k] = E - 127 - f.mbits;
-            maxx[k] = __builtin_amdgcn_ldexpf(f.maxnorm, E);
-        }
+        mx_cols_consts<DT, CEIL>(acc[d], f, bad, nE, yk, maxx);
 #pragma unroll
         for (int i = 0; i < RPL; ++i) {
             float fd[T::EPD];

@@ -2,9 +2,10 @@
 // for a gradient, whose backward GEMMs sum thousands of quantized elements -- under nearest rounding every element below half a quantum
 // rounds to zero on every step (a bias); here E[y] = v.
 //
-//   mx_sr_kernel        the row axis: loads, slots, DPP absmax and stores of mx_kernel<DT, MX_FWD, ...> (fq_mx.h)
-//   mx_sr_cols_kernel   the column axis: tile, loads, permlane absmax and stores of mx_cols_kernel<DT, CEIL> (fq_mx_cols.h)
-// No rotation, no saturation bitmap, no export; no LDS, no barrier.
+//   mx_sr_kernel        the row axis: mx_kernel<DT, MX_FWD, ...>'s slots, load_clamped and mx_vec_absmax + DPP absmax (fq_mx.h)
+//   mx_sr_cols_kernel   the column axis: the tile of fq_mx_cols.h through its stages mx_cols_load and mx_cols_consts; its own part is
+//                       the constants of all four dwords up front and the row-outer loop (one Philox call per row of the strip)
+// Both round through mx_rint_sr and mx_sr_dword below.  No rotation, no saturation bitmap, no export; no LDS, no barrier.
 //
 // Per block nothing changes up to the shared exponent (amax from the bit patterns, NaN / Inf -> a NaN block, E by the floor or ceil rule,
 // t = v * 2^-E, the binade sb of |t| clamped at the smallest normal one).  a = |t| / quantum is the exact fp32 value mx_rint feeds to
@@ -53,10 +54,7 @@ template <int EPV> __host__ __device__ __forceinline__ void mx_sr_words(int64_t 
 
 // mx_rint with the stochastic rule: r16 is the element's random number in [0, 65535]; -> r >= 0 (mx_value takes the sign from v)
 __device__ __forceinline__ float mx_rint_sr(float v, int nE, int bmin, int mbits, uint32_t r16, int& sb) {
-    const float t = __builtin_amdgcn_ldexpf(v, nE);
-    const int e = (int)((as_u(t) >> 23) & 0xFFu);                          // 0 for a subnormal t
-    sb = e > bmin ? e : bmin;
-    const float a = __builtin_fabsf(__builtin_amdgcn_ldexpf(t, 127 + mbits - sb));
+    const float a = __builtin_fabsf(mx_quanta(v, nE, bmin, mbits, sb));
     const float n = __builtin_floorf(a), f = a - n;
     return n + ((float)r16 < f * 65536.0f ? 1.0f : 0.0f);   // (a select and an add: `? n + 1 : n` compiles to a branch per element)
 }
@@ -98,16 +96,12 @@ __global__ __launch_bounds__(MX_TPB) void mx_sr_kernel(MxArgs a, MxFmt f, MxSrKe
     for (int i = 0; i < VPT; ++i) {
         const int64_t v = base + i * MX_TPB;
         const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
-        uint32_t acc = 0;
-        acc = T::absmax_acc(acc, r[i].x);
-        acc = T::absmax_acc(acc, r[i].y);
-        acc = T::absmax_acc(acc, r[i].z);
-        acc = T::absmax_acc(acc, r[i].w);
-        acc = T::absmax_finish(acc);
-        const uint32_t ab = group_reduce<OpMaxU>(acc, BV);   // fp32 bits of the block's amax (NaN sorts above Inf)
+        const uint32_t ab = group_reduce<OpMaxU>(mx_vec_absmax<DT>(r[i]), BV);   // fp32 bits of the block's amax (NaN sorts above Inf)
         bool bad[T::EPD];
         int nE[T::EPD], yk[T::EPD];
         float maxx[T::EPD];
+        // mx_block_consts' text, not a call of it: through the helper the two fp32 instantiations come out three s_nop longer, and no
+        // recorded benchmark launches them to show that this costs nothing
         const int E = CEIL ? mx_shared_exp_ceil(ab, f.emax, f.maxnorm) : mx_shared_exp(ab, f.emax);
 #pragma unroll
         for (int k = 0; k < T::EPD; ++k) {                    // one block per vector: the same constants for both halves of a dword
@@ -129,62 +123,32 @@ __global__ __launch_bounds__(MX_TPB) void mx_sr_cols_kernel(MxColsArgs a, MxFmt 
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE;
     constexpr int RPL = MXC_TILE_ROWS / MXC_ROW_GROUPS;   // rows per lane
-    const uint32_t rt = blockIdx.x / a.nct, ct = blockIdx.x - rt * a.nct;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const int64_t strip = (int64_t)ct * MXC_TILE_STRIPS + wave * MXC_WAVE_STRIPS + (lane & (MXC_WAVE_STRIPS - 1));
-    const int64_t row = (int64_t)rt * MXC_TILE_ROWS + (lane / MXC_WAVE_STRIPS) * RPL;
-    const bool live = strip < a.ncs;
-    const int64_t first = row * a.ncs + (live ? strip : a.ncs - 1);   // a row is ncs whole vectors: this is the flat vector index too
-    const uint4* __restrict__ xv = (const uint4*)a.x;
-
-    uint4 r[RPL];
-    if (a.ntl) {
-#pragma unroll
-        for (int i = 0; i < RPL; ++i) r[i] = ld16<true>(&xv[first + i * a.ncs]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < RPL; ++i) r[i] = ld16<false>(&xv[first + i * a.ncs]);
-    }
-
-    uint32_t w[RPL][4], acc[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        w[i][0] = r[i].x, w[i][1] = r[i].y, w[i][2] = r[i].z, w[i][3] = r[i].w;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) acc[d] = T::absmax_acc(acc[d], w[i][d]);
-    }
+    uint32_t w[RPL][4], acc[4];
+    bool live;
+    const int64_t first = mx_cols_load<DT, RPL>(a, w, acc, live);
 
     const int bmin = f.emin + 127;
     bool bad[4][T::EPD];
     int nE[4][T::EPD], yk[4][T::EPD];
     float maxx[4][T::EPD];
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const uint32_t m = mx_cols_group_max<DT>(acc[d]);   // dword d of the strip: the patterns of its EPD columns' amax
-#pragma unroll
-        for (int k = 0; k < T::EPD; ++k) {
-            const uint32_t ab = T::EPD == 1 ? m : T::absmax_finish(k ? m >> 16 : m & 0xFFFFu);   // fp32 bits of the block's amax
-            bad[d][k] = ab >= 0x7F800000u;
-            const int E = CEIL ? mx_shared_exp_ceil(ab, f.emax, f.maxnorm) : mx_shared_exp(ab, f.emax);
-            nE[d][k] = -E, yk[d][k] = E - 127 - f.mbits;
-            maxx[d][k] = __builtin_amdgcn_ldexpf(f.maxnorm, E);
-        }
-    }
+    for (int d = 0; d < 4; ++d) mx_cols_consts<DT, CEIL>(acc[d], f, bad[d], nE[d], yk[d], maxx[d]);
 #pragma unroll
     for (int i = 0; i < RPL; ++i) {                         // one row of the strip = one flat vector = one call's words
+        const int64_t v = first + i * a.ncs;               // one value for the counter and the store's address (spelled twice: + 2 VGPRs)
         uint32_t rw[EPV / 2];
-        mx_sr_words<EPV>(first + i * a.ncs, key, rw);
+        mx_sr_words<EPV>(v, key, rw);
         uint32_t o[4];
 #pragma unroll
         for (int d = 0; d < 4; ++d) o[d] = mx_sr_dword<DT>(w[i][d], d, rw, nE[d], yk[d], maxx[d], bad[d], bmin, f.mbits);
-        if (live) st16<true>(&((uint4*)a.y)[first + i * a.ncs], make_uint4(o[0], o[1], o[2], o[3]));
+        if (live) st16<true>(&((uint4*)a.y)[v], make_uint4(o[0], o[1], o[2], o[3]));
     }
 }
 
 // a and f validated by fqs_mx_fwd (fq_api.hip): nvec > 0, grid within limits
 template <int DT> int launch_mx_sr(bool ceil, MxArgs a, MxFmt f, MxSrKey k, hipStream_t st) {
     begin_launches();
-    const dim3 grid((unsigned)((a.nvec + MX_TPB * MX_VPT - 1) / (MX_TPB * MX_VPT)));
+    const dim3 grid(mx_rows_grid(a.nvec));
     if (ceil) launch(mx_sr_kernel<DT, MX_VPT, true>, grid, dim3(MX_TPB), st, a, f, k);
     else launch(mx_sr_kernel<DT, MX_VPT, false>, grid, dim3(MX_TPB), st, a, f, k);
     return launch_result();

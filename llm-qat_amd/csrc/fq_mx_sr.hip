@@ -1,5 +1,6 @@
 // fq_mx_sr.hip -- instantiations of the stochastic-rounding MX fake quantization (fq_mx_sr.h) for the three element types, and the host
-// restatement of its noise index (fqs_mx_noise): a translation unit of its own, so the other units compile exactly as before.
+// restatement of its noise index (fqs_mx_noise).  A translation unit of its own; it shares the stages of fq_mx.h and fq_mx_cols.h with
+// fq_mx.hip and fq_mx_cols.hip, so a change to one of those headers is checked on all three listings.
 #include "fq_mx_sr.h"
 namespace fq {
 FQ_INSTANTIATE_MX_SR(F32)
