@@ -34,6 +34,8 @@ EXPORTS = (
 TRAIN_EXPORTS = ("fqt_mx_fwd_cols",)
 # every symbol include/llmqat_fakequant_sr.h declares (the fqs_ family: MX fake quantization with stochastic rounding)
 SR_EXPORTS = ("fqs_mx_fwd", "fqs_mx_fwd_cols", "fqs_mx_noise")
+# every symbol include/llmqat_fakequant_infer.h declares (the fqi_ family: the inference-side entry points)
+INFER_EXPORTS = ("fqi_mx_dequant",)
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -164,6 +166,8 @@ def _bind(L):
         f.restype = i32
     L.fqs_mx_noise.argtypes = [u64, u64, i64, i64, i32, vp]
     L.fqs_mx_noise.restype = i32
+    L.fqi_mx_dequant.argtypes = [vp, vp, vp, i64, i64, i32, i32, vp]
+    L.fqi_mx_dequant.restype = i32
     return L
 
 

@@ -250,3 +250,15 @@ def mx_matmul_op(a_elems: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, w_el
 def _(a_elems, a_scales, a_fmt, w_elems, w_scales, w_fmt, a_shape, out_dtype):
     _, N, _ = ops.check_mx_matmul(tuple(a_shape), a_fmt, (w_scales.shape[0], w_scales.shape[1] * ops.MX_BLOCK), w_fmt, out_dtype)
     return a_elems.new_empty(tuple(a_shape[:-1]) + (N,), dtype=out_dtype)
+
+
+# ops.mx_dequantize on the export's tensors: the weight of MXLinear's dequantized route; inference only, as mx_matmul
+@torch.library.custom_op("llmqat_amd::mx_dequant", mutates_args=(), device_types="cuda")
+def mx_dequant_op(elements: torch.Tensor, scales: torch.Tensor, fmt: str, shape: List[int], dtype: torch.dtype) -> torch.Tensor:
+    return ops.mx_dequantize_tensors(elements, scales, fmt, tuple(shape), dtype)
+
+
+@mx_dequant_op.register_fake
+def _(elements, scales, fmt, shape, dtype):
+    ops.check_mx_dequant(fmt, tuple(shape), dtype)
+    return elements.new_empty(tuple(shape), dtype=dtype)

@@ -3,6 +3,7 @@
 #include "../../include/llmqat_fakequant.h"
 #include "../../include/llmqat_fakequant_train.h"
 #include "../../include/llmqat_fakequant_sr.h"
+#include "../../include/llmqat_fakequant_infer.h"
 
 #include <hip/hip_runtime.h>
 
@@ -643,6 +644,26 @@ FQ_API int fq_mx_gemm(const void* a_elems, const void* a_scales, int a_fmt, cons
     if (M > MXG_SKINNY_M && (N + MXG_TILE - 1) / MXG_TILE > 65535) return fail(FQ_ERR_UNSUPPORTED, "N=%lld exceeds one launch's grid", (long long)N);
     const MxGemmArgs g{(const uint8_t*)w_elems, (const uint8_t*)w_scales, (const uint8_t*)a_elems, (const uint8_t*)a_scales, out, M, N, K, w_fmt, a_fmt, out_dtype};
     return launch_mx_gemm(g, (hipStream_t)stream);
+}
+
+// include/llmqat_fakequant_infer.h: an export back to a tensor.  mx_checks' list with the export's format refusals first (the FP6 one in
+// fq_mx_export's words); nvec counts the OUTPUT's vectors.  Every check comes before any HIP call.
+FQ_API int fqi_mx_dequant(const void* elems, const void* scales, void* y, int64_t rows, int64_t cols, int fmt, int dtype, void* stream) {
+    auto formats = [&] {
+        if (fmt < FQ_MX_FP4_E2M1 || fmt > FQ_MX_FP8_E5M2) return fail(FQ_ERR_ARG, "unknown MX format code %d", fmt);
+        if (fmt == FQ_MX_FP6_E2M3 || fmt == FQ_MX_FP6_E3M2) return fail(FQ_ERR_ARG, "FP6 formats have no export packing");
+        return 0;
+    };
+    auto pointers = [&] {
+        if (!elems || !scales || !y) return fail(FQ_ERR_NULL, "elems / scales / y must not be NULL");
+        if (!aligned16(elems) || !aligned16(y)) return fail(FQ_ERR_UNSUPPORTED, "elems and y must be 16-byte aligned");
+        return 0;
+    };
+    int64_t nvec = 0;
+    if (const int rc = mx_checks(dtype, rows, cols, false, nvec, formats, pointers); rc != CONTINUE) return rc;
+    const MxDequantArgs a{(const uint8_t*)elems, (const uint8_t*)scales, y, nvec};
+    hipStream_t st = (hipStream_t)stream;
+    return by_dtype(dtype, [&](auto dt) { return launch_mx_dequant<decltype(dt)::value>(fmt, a, st); });
 }
 
 }  // extern "C"

@@ -248,6 +248,14 @@ struct MxSrKey {
 template <int DT> FQ_HIDDEN int launch_mx_sr(bool ceil, MxArgs a, MxFmt f, MxSrKey k, hipStream_t st);
 template <int DT> FQ_HIDDEN int launch_mx_sr_cols(bool ceil, MxColsArgs a, MxFmt f, MxSrKey k, int64_t row_tiles, hipStream_t st);
 FQ_HIDDEN void mx_sr_host_noise(MxSrKey k, int64_t first, int64_t n, int epv, uint16_t* out);   // host only: the kernels' noise, restated
+// an MX export back to a tensor (fq_mx_dequant.h / fq_mx_dequant.hip): y = value of the code * 2^(scale byte - 127), rounded once to DT
+struct MxDequantArgs {
+    const uint8_t* elems;   // the export's element codes (fp4: two per byte) and
+    const uint8_t* scales;  // its E8M0 bytes, one per block of 32 elements
+    void* y;
+    int64_t nvec;           // 16-byte vectors of the output: a multiple of the block's vector count
+};
+template <int DT> FQ_HIDDEN int launch_mx_dequant(int fmt, MxDequantArgs a, hipStream_t st);
 // MX block-scaled GEMM (fq_mx_gemm.h / fq_mx_gemm.hip): out[m, n] = sum_k A[m, k] * W[n, k] over two MX exports
 struct MxGemmArgs {
     const uint8_t* we;   // W: [N, K] element codes, E8M0 scales [N, K / 32]

@@ -6,6 +6,21 @@ from torch import nn
 from . import compiled, ops
 from .utils_quant import QuantizeLinear
 
+# The recommended dequant_above of MXLinear, from the layer timings of DESIGN.md section 21 (tools/mx_dequant_bench.py on one MI355X, the
+# three LLaMA-7B projections, W mxfp4 / A mxfp8_e4m3, bf16): the smallest measured token count above which the dequantized route beats the
+# GEMM route on all three shapes by more than the runs' spread; None would say there is no such count.  At 64 tokens the GEMM route still
+# wins on 4096 -> 11008 (47 against 57 us); from 128 tokens on the dequantized route wins everywhere (62 / 87 / 47 against 81 / 158 / 77 us).
+# Offered, not applied: MXLinear's own default is dequant_above=None.
+DEQUANT_ABOVE_DEFAULT = 64
+
+
+def _check_dequant_above(n):
+    """-> n, None or a Python int >= 0; ValueError for anything else (bools and strings included)"""
+    if n is None or (isinstance(n, int) and not isinstance(n, bool) and n >= 0):
+        return n
+    raise ValueError(f"MXLinear: dequant_above={n!r}: None (every call runs the MX GEMM) or an int >= 0 (calls with more rows than that "
+                     "run the dequantized route)")
+
 
 def _why_not(layer):
     """None if `layer` can become an MXLinear, else the reason."""
@@ -28,10 +43,17 @@ class MXLinear(nn.Module):
     rotate=True: the buffers hold the export of W R and the activation's export launch rotates x, so the product
     is (x R)(W R)^T -- still two launches, the same GEMM.  A constructor attribute like the formats: it is not in the state_dict.
     scale_rule: the shared-exponent rule of the activation's export launch ("floor" / "ceil"); the weight buffers
-    carry whatever rule exported them, and the GEMM reads the scale bytes as they are.  A constructor attribute too."""
+    carry whatever rule exported them, and the GEMM reads the scale bytes as they are.  A constructor attribute too.
+    dequant_above: None -- every call runs as above.  An int n >= 0: a call whose x has more than n rows (the
+    product of its leading dimensions) runs F.linear(mx_quantize(x, act_format, rotate, scale_rule), mx_dequantize(W, x.dtype)) (+ bias)
+    instead -- the fake-quantize launch, one dequantize launch, the library GEMM: the arithmetic of QuantizeLinear.eval(), bit for bit,
+    with W still read from its codes; a call with n rows or fewer runs the MX GEMM.  0 sends every call there.  That route allocates a
+    transient [out_features, in_features] tensor in x's dtype per call (90 MB for a bf16 4096 x 11008 projection), freed when the call
+    returns; the weight stays compressed between calls.  DEQUANT_ABOVE_DEFAULT is the measured recommendation.  A constructor attribute
+    like rotate: not in the state_dict."""
 
     def __init__(self, in_features, out_features, weight_format="mxfp4", act_format="mxfp8_e4m3", bias=False, device=None, dtype=None,
-                 rotate=False, scale_rule="floor"):
+                 rotate=False, scale_rule="floor", dequant_above=None):
         super().__init__()
         for what, fmt in (("weight_format", weight_format), ("act_format", act_format)):
             if fmt not in ops.MX_GEMM_FORMATS:
@@ -43,16 +65,17 @@ class MXLinear(nn.Module):
         self.rotate = bool(rotate)   # (in_features % 128 == 0 holds whole 64-element rotation runs)
         ops.check_mx_scale_rule(scale_rule, "MXLinear")
         self.scale_rule = scale_rule
+        self.dequant_above = _check_dequant_above(dequant_above)
         ebytes = in_features // 2 if weight_format == "mxfp4" else in_features
         self.register_buffer("weight_elements", torch.zeros(out_features, ebytes, dtype=torch.uint8, device=device))
         self.register_buffer("weight_scales", torch.zeros(out_features, in_features // ops.MX_BLOCK, dtype=torch.uint8, device=device))
         self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
 
     @classmethod
-    def from_quantize_linear(cls, layer):
+    def from_quantize_linear(cls, layer, dequant_above=None):
         """The inference form of a QuantizeLinear whose weight and activations both resolve to mxfp4 / mxfp8_* (explicitly or through
         default_mx_formats) and whose in_features the kernel serves; ValueError names what is missing otherwise.  The weight is exported
-        once (one launch), on the device it lives on."""
+        once (one launch), on the device it lives on.  dequant_above: the new module's (MXLinear's argument)."""
         why = _why_not(layer)
         if why is not None:
             raise ValueError(f"MXLinear.from_quantize_linear: {why}")
@@ -60,7 +83,7 @@ class MXLinear(nn.Module):
         rotate = bool(getattr(layer, "mx_rotate", False))
         rule = getattr(layer, "mx_scale_rule", "floor")
         m = cls(layer.in_features, layer.out_features, layer.weight_format, layer.act_format, bias=has_bias, device=layer.weight.device,
-                dtype=layer.weight.dtype, rotate=rotate, scale_rule=rule)
+                dtype=layer.weight.dtype, rotate=rotate, scale_rule=rule, dequant_above=dequant_above)
         e = (layer.export_weight() if hasattr(layer, "export_weight")
              else ops.mx_export(layer.weight.detach(), layer.weight_format, rotate=rotate, scale_rule=rule))
         m.weight_elements.copy_(e.elements)
@@ -77,6 +100,8 @@ class MXLinear(nn.Module):
     def forward(self, x):
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("MXLinear is an inference module and is not differentiable: call it under torch.no_grad() or on a detached input")
+        if self.dequant_above is not None and x.numel() // self.in_features > self.dequant_above:
+            return self._forward_dequant(x)
         if torch.compiler.is_compiling():
             ae, asc = compiled.mx_export(x, self.act_format, self.rotate, self.scale_rule)
             y = compiled.mx_matmul_op(ae, asc, self.act_format, self.weight_elements, self.weight_scales, self.weight_format, list(x.shape), x.dtype)
@@ -86,19 +111,33 @@ class MXLinear(nn.Module):
         # the bias in x's dtype: the output dtype follows x (fp16 + bf16 would promote the sum to fp32)
         return y if self.bias is None else y + self.bias.to(y.dtype)
 
+    def _forward_dequant(self, x):
+        """the dequantized route: x fake-quantized (one launch), W expanded to x's dtype (one launch), the library GEMM"""
+        shape = (self.out_features, self.in_features)
+        if torch.compiler.is_compiling():
+            xq = compiled.mx_fake_quant(x, self.act_format, self.rotate, self.scale_rule, False)
+            w = compiled.mx_dequant_op(self.weight_elements, self.weight_scales, self.weight_format, list(shape), x.dtype)
+        else:
+            xq = ops.mx_quantize(x, self.act_format, rotate=self.rotate, scale_rule=self.scale_rule)
+            w = ops.mx_dequantize_tensors(self.weight_elements, self.weight_scales, self.weight_format, shape, x.dtype)
+        y = nn.functional.linear(xq, w)
+        return y if self.bias is None else y + self.bias.to(y.dtype)
+
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, weight_format={self.weight_format!r}, "
                 f"act_format={self.act_format!r}, bias={self.bias is not None}" + (", rotate=True" if self.rotate else "")
-                + (f", scale_rule={self.scale_rule!r}" if self.scale_rule != "floor" else ""))
+                + (f", scale_rule={self.scale_rule!r}" if self.scale_rule != "floor" else "")
+                + (f", dequant_above={self.dequant_above}" if self.dequant_above is not None else ""))
 
 
-def convert_to_mx_inference(model):
+def convert_to_mx_inference(model, dequant_above=None):
     """Replace, in place, every QuantizeLinear of `model` that MXLinear.from_quantize_linear accepts; integer-quantized, group-wise, FP6
-    layers and those whose in_features the kernel does not serve stay as they are.  -> the number of layers replaced."""
+    layers and those whose in_features the kernel does not serve stay as they are.  dequant_above: what every new MXLinear gets.  -> the number of layers replaced."""
+    _check_dequant_above(dequant_above)
     n = 0
     for parent in list(model.modules()):
         for name, child in list(parent.named_children()):
             if isinstance(child, QuantizeLinear) and _why_not(child) is None:
-                setattr(parent, name, MXLinear.from_quantize_linear(child))
+                setattr(parent, name, MXLinear.from_quantize_linear(child, dequant_above=dequant_above))
                 n += 1
     return n

@@ -1029,7 +1029,8 @@ MX_SCALE_RULES = ("floor", "ceil")
 # two grid neighbours with the probabilities that make the result unbiased -- for the gradient operand of the backward GEMMs.  The noise is
 # Philox4x32-10 on (seed, stream, flat element index), computed inside the kernels (fqs_mx_fwd / fqs_mx_fwd_cols of the third header).
 mx_counts = {"mx_launch": 0, "mx_export_launch": 0, "mx_copy_route": 0, "mx_gemm_launch": 0, "mx_gemm_skinny": 0, "mx_gemm_tiled": 0,
-             "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0, "mx_cols_launch": 0, "mx_sr_launch": 0, "mx_sr_cols_launch": 0}
+             "mx_rotate_launch": 0, "mx_mask_launch": 0, "mx_ste_launch": 0, "mx_cols_launch": 0, "mx_sr_launch": 0, "mx_sr_cols_launch": 0,
+             "mx_dequant_launch": 0}
 
 
 def _mx_format(fmt):
@@ -1301,6 +1302,58 @@ def mx_export(x, fmt, rotate=False, scale_rule="floor"):
     scales = torch.empty(lead + (cols // MX_BLOCK,), dtype=torch.uint8, device=x.device)
     _mx_launch("mx_export", "fq_mx_export_ex", "mx_export_launch", x, (x.data_ptr(), elems.data_ptr(), scales.data_ptr()), code, dt, flags)
     return MXExport(elems, scales, fmt, tuple(x.shape), x.dtype, rotate)
+
+
+# ---- an export back to a tensor in one launch (fqi_mx_dequant of the fourth header) --------------------------------
+def check_mx_dequant(fmt, shape, dtype):
+    """The argument checks of mx_dequantize on shapes alone (the fake implementation of the compiled op runs them too) -> the number of
+    elements: ValueError for an unknown or an FP6 format, a dtype that is not served, a last dimension that is not whole blocks."""
+    if fmt not in MX_FORMATS:
+        raise ValueError(f"mx_dequantize: unknown MX format {fmt!r}: one of {', '.join(MX_GEMM_FORMATS)}")
+    if fmt not in MX_GEMM_FORMATS:
+        raise ValueError(f"mx_dequantize: {fmt!r}: FP6 formats have no export packing")
+    if dtype not in _OUT_DTYPES:
+        raise ValueError(f"mx_dequantize: dtype {dtype} is not served (float32, bfloat16, float16 are)")
+    if len(shape) == 0 or shape[-1] % MX_BLOCK:
+        raise ValueError(f"mx_dequantize: the shape needs a last dimension that is a multiple of {MX_BLOCK}, got {tuple(shape)}")
+    n = 1
+    for d in shape:
+        n *= d
+    return n
+
+
+def mx_dequantize_tensors(elements, scales, fmt, shape, dtype):
+    """mx_dequantize on the export's tensors (what MXLinear keeps as buffers): `elements` and `scales` are the uint8 code and E8M0 bytes
+    of a contiguous tensor of `shape` in `fmt`, in any shape of their own that holds those bytes in order.  -> a new contiguous tensor of
+    `shape` and `dtype`.  One launch (mx_dequant_launch); a non-contiguous or misaligned buffer is copied once first (mx_copy_route); an
+    empty shape launches nothing."""
+    shape = tuple(shape)
+    n = check_mx_dequant(fmt, shape, dtype)
+    for t in (elements, scales):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError("mx_dequantize: elements and scales are uint8 tensors")
+    if elements.numel() != (n // 2 if fmt == "mxfp4" else n):
+        raise ValueError(f"mx_dequantize: elements holds {elements.numel()} bytes, not those of a {list(shape)} {fmt} export")
+    if scales.numel() != n // MX_BLOCK:
+        raise ValueError(f"mx_dequantize: scales holds {scales.numel()} bytes, not one per {MX_BLOCK}-element block of a {list(shape)} tensor")
+    for t in (elements, scales):
+        _prep_u8(t, "mx_dequantize")      # the device: no CPU implementation
+    if elements.device != scales.device:
+        raise ValueError("mx_dequantize: elements and scales live on different devices")
+    elements, scales = _mx_aligned(elements, True), _mx_aligned(scales, True)
+    y = torch.empty(shape, dtype=dtype, device=elements.device)
+    _mx_launch("mx_dequantize", "fqi_mx_dequant", "mx_dequant_launch", elements, (elements.data_ptr(), scales.data_ptr(), y.data_ptr()),
+               MX_FORMATS[fmt], _OUT_DTYPES[dtype], dims=(n // shape[-1] if shape[-1] else 0, shape[-1]))
+    return y
+
+
+def mx_dequantize(e, dtype=None):
+    """The tensor an MXExport stands for, in one launch: e.dequantize() bit for bit (any NaN for a NaN), of e.shape and `dtype` (default
+    e.dtype) -- so mx_dequantize(mx_export(x, fmt, rotate, rule)) is mx_quantize(x, fmt, rotate, rule), in the rotated basis where the
+    export is.  Every element is the value of its code times 2^(scale byte - 127) in fp32 (exact), rounded once to the dtype."""
+    if not isinstance(e, MXExport):
+        raise TypeError("mx_dequantize: e is an MXExport object (ops.mx_export)")
+    return mx_dequantize_tensors(e.elements, e.scales, e.fmt, e.shape, e.dtype if dtype is None else dtype)
 
 
 # ---- MX block-scaled GEMM: the exported codes on gfx950's scaled matrix instruction (fq_mx_gemm, DESIGN.md section 14) ------------------

@@ -119,6 +119,7 @@ def stats(reset=False):
                                          mx_backward_format); an input it does not take goes through the row kernel: mx_copy_route + mx_launch
       mx_gemm_launch / mx_gemm_skinny / mx_gemm_tiled
                                          MX block-scaled GEMMs (ops.mx_matmul, MXLinear) launched, and which kernel served them (M <= 32: skinny)
+      mx_dequant_launch                  MX exports expanded back to a tensor (ops.mx_dequantize, the dequantized route of MXLinear(dequant_above=n))
       cpp_pair_forward / cpp_weight_forward / cpp_pair_backward / cpp_one_backward / cpp_slow_backward
                                          what the C++ autograd nodes did (_fq_node.so; `host_node()` says whether it is loaded): operand-pair and
                                          weight-only launches made from C++, pair / one-tensor (K, V) backwards, and backwards handed back to the
