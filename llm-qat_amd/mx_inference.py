@@ -22,6 +22,18 @@ def _check_dequant_above(n):
                      "run the dequantized route)")
 
 
+def _exportable(fmt):
+    """whether the MX GEMM reads this format's export (mxfp4 / mxfp8_*: FP6 has no packing)"""
+    return fmt in ops.MX_GEMM_FORMATS
+
+
+def _k_refusal(in_features):
+    """why the MX GEMM kernel does not serve this K, or None"""
+    if in_features <= 0 or in_features % ops.MX_GEMM_KSTEP:
+        return f"in_features={in_features} is not a positive multiple of {ops.MX_GEMM_KSTEP}, the K step of the MX GEMM kernel"
+    return None
+
+
 def _why_not(layer):
     """None if `layer` can become an MXLinear, else the reason."""
     if not isinstance(layer, QuantizeLinear):
@@ -29,11 +41,9 @@ def _why_not(layer):
     for what, fmt in (("weight_format", layer.weight_format), ("act_format", layer.act_format)):
         if fmt is None:
             return f"{what} is not set: the layer does not quantize that operand to an MX format"
-        if fmt not in ops.MX_GEMM_FORMATS:
+        if not _exportable(fmt):
             return f"{what}={fmt!r} has no export packing (one of {', '.join(ops.MX_GEMM_FORMATS)})"
-    if layer.in_features == 0 or layer.in_features % ops.MX_GEMM_KSTEP:
-        return f"in_features={layer.in_features} is not a positive multiple of {ops.MX_GEMM_KSTEP}, the K step of the MX GEMM kernel"
-    return None
+    return _k_refusal(layer.in_features)
 
 
 class MXLinear(nn.Module):
@@ -56,10 +66,11 @@ class MXLinear(nn.Module):
                  rotate=False, scale_rule="floor", dequant_above=None):
         super().__init__()
         for what, fmt in (("weight_format", weight_format), ("act_format", act_format)):
-            if fmt not in ops.MX_GEMM_FORMATS:
+            if not _exportable(fmt):
                 raise ValueError(f"{what}={fmt!r}: one of {', '.join(ops.MX_GEMM_FORMATS)}")
-        if in_features <= 0 or in_features % ops.MX_GEMM_KSTEP:
-            raise ValueError(f"in_features={in_features} is not a positive multiple of {ops.MX_GEMM_KSTEP}, the K step of the MX GEMM kernel")
+        why = _k_refusal(in_features)
+        if why is not None:
+            raise ValueError(why)
         self.in_features, self.out_features = in_features, out_features
         self.weight_format, self.act_format = weight_format, act_format
         self.rotate = bool(rotate)   # (in_features % 128 == 0 holds whole 64-element rotation runs)
@@ -80,12 +91,9 @@ class MXLinear(nn.Module):
         if why is not None:
             raise ValueError(f"MXLinear.from_quantize_linear: {why}")
         has_bias = getattr(layer, "bias", None) is not None
-        rotate = bool(getattr(layer, "mx_rotate", False))
-        rule = getattr(layer, "mx_scale_rule", "floor")
         m = cls(layer.in_features, layer.out_features, layer.weight_format, layer.act_format, bias=has_bias, device=layer.weight.device,
-                dtype=layer.weight.dtype, rotate=rotate, scale_rule=rule, dequant_above=dequant_above)
-        e = (layer.export_weight() if hasattr(layer, "export_weight")
-             else ops.mx_export(layer.weight.detach(), layer.weight_format, rotate=rotate, scale_rule=rule))
+                dtype=layer.weight.dtype, rotate=layer.mx_rotate, scale_rule=layer.mx_scale_rule, dequant_above=dequant_above)
+        e = layer.export_weight()
         m.weight_elements.copy_(e.elements)
         m.weight_scales.copy_(e.scales)
         if has_bias:
@@ -108,8 +116,7 @@ class MXLinear(nn.Module):
         else:
             a = ops.mx_export(x, self.act_format, rotate=self.rotate, scale_rule=self.scale_rule)
             y = ops.mx_matmul_tensors(a.elements, a.scales, a.fmt, self.weight_elements, self.weight_scales, self.weight_format, a.shape, x.dtype)
-        # the bias in x's dtype: the output dtype follows x (fp16 + bf16 would promote the sum to fp32)
-        return y if self.bias is None else y + self.bias.to(y.dtype)
+        return self._add_bias(y)
 
     def _forward_dequant(self, x):
         """the dequantized route: x fake-quantized (one launch), W expanded to x's dtype (one launch), the library GEMM"""
@@ -120,7 +127,10 @@ class MXLinear(nn.Module):
         else:
             xq = ops.mx_quantize(x, self.act_format, rotate=self.rotate, scale_rule=self.scale_rule)
             w = ops.mx_dequantize_tensors(self.weight_elements, self.weight_scales, self.weight_format, shape, x.dtype)
-        y = nn.functional.linear(xq, w)
+        return self._add_bias(nn.functional.linear(xq, w))
+
+    def _add_bias(self, y):
+        # the bias in x's dtype: the output dtype follows x (fp16 + bf16 would promote the sum to fp32)
         return y if self.bias is None else y + self.bias.to(y.dtype)
 
     def extra_repr(self):

@@ -1,4 +1,4 @@
-"""CPU tier of the MX front-end's shared helpers (ops._mx_quantize / _mx_input / _mx_launch, utils_quant._mx_check / _mx_apply, the fake
+"""CPU tier of the MX front-end's shared helpers (ops._mx_quantize / _mx_input / _mx_launch, mx_quant._mx_check / _mx_apply, the fake
 implementations and dispatchers of compiled.py): what a caller sees of them without a GPU.
 
 1. The refusal table: which exception, with which message, every combination of good and faulty arguments gives -- so also which of two
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import llm_qat_amd
-from llm_qat_amd import compiled, ops
+from llm_qat_amd import compiled, mx_quant, ops
 from llm_qat_amd import utils_quant as U
 
 BAD_FMT, BAD_RULE, BAD_AXIS = "mxfp5", "up", 5
@@ -277,7 +277,7 @@ def test_mx_apply_carries_the_axis_to_either_side(monkeypatch, compiling):
 
 def test_the_public_pair_validates_and_then_applies(monkeypatch):
     seen = []
-    monkeypatch.setattr(U, "_mx_apply", lambda *a: seen.append(a))
+    monkeypatch.setattr(mx_quant, "_mx_apply", lambda *a: seen.append(a))
     x = torch.zeros(2, 64, 64)
     llm_qat_amd.mx_quantize(x, "mxfp4", rotate=1, scale_rule="ceil", ste="clip")
     llm_qat_amd.mx_quantize_axis(x, "mxfp4")
