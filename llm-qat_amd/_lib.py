@@ -36,6 +36,8 @@ TRAIN_EXPORTS = ("fqt_mx_fwd_cols",)
 SR_EXPORTS = ("fqs_mx_fwd", "fqs_mx_fwd_cols", "fqs_mx_noise")
 # every symbol include/llmqat_fakequant_infer.h declares (the fqi_ family: the inference-side entry points)
 INFER_EXPORTS = ("fqi_mx_dequant",)
+# every symbol include/llmqat_fakequant_loss.h declares (the fql_ family: the distillation loss)
+LOSS_EXPORTS = ("fql_kd_kl_fwd", "fql_kd_kl_bwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -168,6 +170,10 @@ def _bind(L):
     L.fqs_mx_noise.restype = i32
     L.fqi_mx_dequant.argtypes = [vp, vp, vp, i64, i64, i32, i32, vp]
     L.fqi_mx_dequant.restype = i32
+    L.fql_kd_kl_fwd.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
+    L.fql_kd_kl_fwd.restype = i32
+    L.fql_kd_kl_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
+    L.fql_kd_kl_bwd.restype = i32
     return L
 
 

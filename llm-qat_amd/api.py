@@ -1,5 +1,6 @@
 """Public surface of the package."""
 from . import ops
+from . import distill   # llm_qat_amd.distill: kd_kl_loss, install (its names stay in the submodule)
 from .cpu_tensors import allow_cpu_tensors
 from ._lib import FakeQuantLibraryError
 from .ops import get_semantics, set_semantics

@@ -262,3 +262,44 @@ def mx_dequant_op(elements: torch.Tensor, scales: torch.Tensor, fmt: str, shape:
 def _(elements, scales, fmt, shape, dtype):
     ops.check_mx_dequant(fmt, tuple(shape), dtype)
     return elements.new_empty(tuple(shape), dtype=dtype)
+
+
+# ---- the distillation loss (ops.kd_kl_forward / ops.kd_kl_backward): (loss, row_stats) and the student's gradient ----
+@torch.library.custom_op("llmqat_amd::kd_kl_fwd", mutates_args=(), device_types="cuda")
+def kd_kl_fwd_op(student: torch.Tensor, teacher: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    loss, row_stats, _ = ops.kd_kl_forward(student, teacher)
+    return loss.clone(), row_stats.clone()      # the two are views of one side buffer: an op's outputs own their storage
+
+
+@kd_kl_fwd_op.register_fake
+def _(student, teacher):
+    rows, _, _ = ops.check_kd(student, teacher)
+    return student.new_empty((), dtype=torch.float32), student.new_empty((rows, 2), dtype=torch.float32)
+
+
+@torch.library.custom_op("llmqat_amd::kd_kl_bwd", mutates_args=(), device_types="cuda")
+def kd_kl_bwd_op(student: torch.Tensor, teacher: torch.Tensor, row_stats: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
+    return ops.kd_kl_backward(student, teacher, row_stats, grad_loss)
+
+
+@kd_kl_bwd_op.register_fake
+def _(student, teacher, row_stats, grad_loss):
+    ops.check_kd(student, teacher)
+    return torch.empty_like(student, memory_format=torch.contiguous_format)
+
+
+def _kd_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[1])
+
+
+def _kd_backward(ctx, grad_loss, grad_stats):
+    student, teacher, row_stats = ctx.saved_tensors
+    return kd_kl_bwd_op(student, teacher, row_stats, grad_loss), None
+
+
+kd_kl_fwd_op.register_autograd(_kd_backward, setup_context=_kd_setup)
+
+
+def kd_kl_loss(student, teacher):
+    """distill.kd_kl_loss while compiling"""
+    return kd_kl_fwd_op(student, teacher)[0]

@@ -1433,3 +1433,85 @@ def mx_matmul(a, w, out_dtype=None):
     out_dtype = a.dtype if out_dtype is None else out_dtype
     check_mx_matmul(a.shape, a.fmt, w.shape, w.fmt, out_dtype)
     return mx_matmul_tensors(a.elements, a.scales, a.fmt, w.elements, w.scales.reshape(w.shape[0], -1), w.fmt, a.shape, out_dtype)
+
+
+# ---- the distillation loss kl_div(log_softmax(student), softmax(teacher), "batchmean") (the fql_ header) ----------
+kd_counts = {"fwd_launch": 0, "bwd_launch": 0, "copy_route": 0}
+_KD_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def check_kd(student, teacher, what="kd_kl_loss"):
+    """The argument checks of the loss on types, shapes and dtypes alone (the fake implementations of the compiled ops run them too) ->
+    (rows, cols, batch): TypeError for a non-tensor, mixed dtypes or a dtype that is not served (float64 among them), ValueError for
+    unequal shapes, fewer than two dimensions, an empty shape, or a teacher that requires grad while grad mode is on."""
+    for name, t in (("student_logits", student), ("teacher_logits", teacher)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t).__name__}")
+    if student.dtype != teacher.dtype:
+        raise TypeError(f"{what}: mixed dtypes are not served: student_logits is {student.dtype}, teacher_logits is {teacher.dtype}")
+    if student.dtype not in _KD_DTYPES:
+        raise TypeError(f"{what}: dtype {student.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+    if tuple(student.shape) != tuple(teacher.shape):
+        raise ValueError(f"{what}: shape mismatch: student_logits {tuple(student.shape)}, teacher_logits {tuple(teacher.shape)}")
+    if student.dim() < 2:
+        raise ValueError(f"{what}: the logits need at least two dimensions [batch, ..., vocabulary], got {tuple(student.shape)}")
+    if student.numel() == 0:
+        raise ValueError(f"{what}: empty logits {tuple(student.shape)}: a loss has no empty launch")
+    if teacher.requires_grad and torch.is_grad_enabled():
+        raise ValueError(f"{what}: teacher_logits requires grad: the loss has no gradient for the teacher; pass teacher_logits.detach()")
+    cols = student.shape[-1]
+    return student.numel() // cols, cols, student.shape[0]
+
+
+def kd_inputs(student, teacher, what="kd_kl_loss"):
+    """check_kd, then the device (CUDA, the same one), then the copy route: a non-contiguous tensor is copied once (copy_route)
+    -> (student, teacher, rows, cols, batch)"""
+    rows, cols, batch = check_kd(student, teacher, what)
+    _prep(student, what)
+    _prep(teacher, what)
+    if student.device != teacher.device:
+        raise ValueError(f"{what}: student_logits is on {student.device}, teacher_logits on {teacher.device}")
+    if not student.is_contiguous():
+        kd_counts["copy_route"] += 1
+        student = student.contiguous()
+    if not teacher.is_contiguous():
+        kd_counts["copy_route"] += 1
+        teacher = teacher.contiguous()
+    return student, teacher, rows, cols, batch
+
+
+def kd_kl_forward(student, teacher, need_stats=True):
+    """-> (loss, row_stats, row_loss): the fp32 0-dim loss, the [rows, 2] fp32 (lse_s, lse_t) the backward reads (None with
+    need_stats=False: no buffer, nothing written) and the [rows] fp32 row losses, rows = numel / shape[-1].  fp32 arithmetic whatever
+    the logits' dtype; two launches on the current stream (the rows, the sum), counted as one fwd_launch."""
+    student, teacher, rows, cols, batch = kd_inputs(student, teacher, "kd_kl_forward")
+    side = torch.empty(rows * (3 if need_stats else 1) + 1, dtype=torch.float32, device=student.device)   # row_stats | row_loss | loss
+    stats = side[:2 * rows].view(rows, 2) if need_stats else None
+    row_loss, loss = side[-rows - 1:-1], side[-1]
+    rc = _launch(student, _lib.lib().fql_kd_kl_fwd, student.data_ptr(), teacher.data_ptr(), stats.data_ptr() if need_stats else None,
+                 row_loss.data_ptr(), loss.data_ptr(), rows, cols, batch, _KD_DTYPES[student.dtype])
+    _lib.check(rc, "kd_kl_forward")
+    kd_counts["fwd_launch"] += 1
+    return loss, stats, row_loss
+
+
+def kd_kl_backward(student, teacher, row_stats, grad_loss):
+    """-> grad_student = (grad_loss / batch) (softmax(student) - softmax(teacher)), of student's shape and dtype, rounded once from fp32.
+    row_stats: kd_kl_forward's, on the same logits; grad_loss: the upstream gradient of the loss, a one-element CUDA tensor that the kernel
+    reads on the device (no host synchronisation).  One launch (bwd_launch)."""
+    with torch.no_grad():
+        student, teacher, rows, cols, batch = kd_inputs(student, teacher, "kd_kl_backward")
+    if not (isinstance(row_stats, torch.Tensor) and row_stats.dtype == torch.float32 and tuple(row_stats.shape) == (rows, 2)
+            and row_stats.device == student.device and row_stats.is_contiguous()):
+        raise ValueError(f"kd_kl_backward: row_stats is kd_kl_forward's contiguous fp32 [{rows}, 2] tensor on {student.device}")
+    if not (isinstance(grad_loss, torch.Tensor) and grad_loss.numel() == 1 and grad_loss.device == student.device):
+        raise ValueError(f"kd_kl_backward: grad_loss is a one-element tensor on {student.device}")
+    g = grad_loss.detach().reshape(1)
+    if g.dtype != torch.float32:
+        g = g.float()
+    grad = torch.empty_like(student)
+    rc = _launch(student, _lib.lib().fql_kd_kl_bwd, student.data_ptr(), teacher.data_ptr(), row_stats.data_ptr(), g.data_ptr(), grad.data_ptr(),
+                 rows, cols, batch, _KD_DTYPES[student.dtype])
+    _lib.check(rc, "kd_kl_backward")
+    kd_counts["bwd_launch"] += 1
+    return grad
