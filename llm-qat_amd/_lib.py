@@ -38,6 +38,9 @@ SR_EXPORTS = ("fqs_mx_fwd", "fqs_mx_fwd_cols", "fqs_mx_noise")
 INFER_EXPORTS = ("fqi_mx_dequant",)
 # every symbol include/llmqat_fakequant_loss.h declares (the fql_ family: the distillation loss)
 LOSS_EXPORTS = ("fql_kd_kl_fwd", "fql_kd_kl_bwd")
+# every symbol include/llmqat_fakequant_ce.h declares (the fqc_ family: the language-model cross-entropy loss)
+CE_EXPORTS = ("fqc_ce_fwd", "fqc_ce_bwd")
+CE_MEAN, CE_SUM = 0, 1   # FQC_REDUCTION_*
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -174,6 +177,10 @@ def _bind(L):
     L.fql_kd_kl_fwd.restype = i32
     L.fql_kd_kl_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
     L.fql_kd_kl_bwd.restype = i32
+    L.fqc_ce_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i64, i32, i32, vp]
+    L.fqc_ce_fwd.restype = i32
+    L.fqc_ce_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i64, i32, i32, vp]
+    L.fqc_ce_bwd.restype = i32
     return L
 
 

@@ -303,3 +303,47 @@ kd_kl_fwd_op.register_autograd(_kd_backward, setup_context=_kd_setup)
 def kd_kl_loss(student, teacher):
     """distill.kd_kl_loss while compiling"""
     return kd_kl_fwd_op(student, teacher)[0]
+
+
+# ---- the language-model loss (ops.ce_forward / ops.ce_backward, DESIGN.md section 23): (loss, row_lse, n_valid) and the logits' gradient ----
+@torch.library.custom_op("llmqat_amd::ce_fwd", mutates_args=(), device_types="cuda")
+def ce_fwd_op(logits: torch.Tensor, labels: torch.Tensor, shift: bool, ignore_index: int, reduction: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    loss, row_lse, _, n_valid = ops.ce_forward(logits, labels, shift, ignore_index, reduction)
+    return loss.clone(), row_lse.clone(), n_valid.clone()      # the three are views of one side buffer: an op's outputs own their storage
+
+
+@ce_fwd_op.register_fake
+def _(logits, labels, shift, ignore_index, reduction):
+    rows, _, _ = ops.check_ce(logits, labels, shift, ignore_index, reduction)
+    return (logits.new_empty((), dtype=torch.float32), logits.new_empty((rows,), dtype=torch.float32),
+            logits.new_empty((1,), dtype=torch.int64))
+
+
+@torch.library.custom_op("llmqat_amd::ce_bwd", mutates_args=(), device_types="cuda")
+def ce_bwd_op(logits: torch.Tensor, labels: torch.Tensor, row_lse: torch.Tensor, n_valid: torch.Tensor, grad_loss: torch.Tensor, shift: bool,
+              ignore_index: int, reduction: str) -> torch.Tensor:
+    return ops.ce_backward(logits, labels, row_lse, n_valid, grad_loss, shift, ignore_index, reduction)
+
+
+@ce_bwd_op.register_fake
+def _(logits, labels, row_lse, n_valid, grad_loss, shift, ignore_index, reduction):
+    ops.check_ce(logits, labels, shift, ignore_index, reduction)
+    return torch.empty_like(logits, memory_format=torch.contiguous_format)
+
+
+def _ce_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[1], output[2])
+    ctx.ce_settings = inputs[2:]
+
+
+def _ce_backward(ctx, grad_loss, grad_lse, grad_n):
+    logits, labels, row_lse, n_valid = ctx.saved_tensors
+    return ce_bwd_op(logits, labels, row_lse, n_valid, grad_loss, *ctx.ce_settings), None, None, None, None
+
+
+ce_fwd_op.register_autograd(_ce_backward, setup_context=_ce_setup)
+
+
+def ce_loss(logits, labels, shift, ignore_index, reduction):
+    """lm_loss.cross_entropy / causal_lm_loss while compiling"""
+    return ce_fwd_op(logits, labels, shift, ignore_index, reduction)[0]

@@ -1515,3 +1515,96 @@ def kd_kl_backward(student, teacher, row_stats, grad_loss):
     _lib.check(rc, "kd_kl_backward")
     kd_counts["bwd_launch"] += 1
     return grad
+
+
+# ---- the language-model loss cross_entropy(logits, labels, ignore_index), the causal shift in the kernel (the fqc_ header) ----
+ce_counts = {"fwd_launch": 0, "bwd_launch": 0, "copy_route": 0}
+_CE_REDUCTIONS = {"mean": _lib.CE_MEAN, "sum": _lib.CE_SUM}
+_CE_SERVED = ("int64 class-index labels with ignore_index and reduction 'mean' or 'sum' are served; class weights, label smoothing, "
+              "probability targets and reduction='none' are not")
+
+
+def check_ce(logits, labels, shift=False, ignore_index=-100, reduction="mean", what="cross_entropy"):
+    """The argument checks of the loss on types, shapes and dtypes alone (the fake implementations of the compiled ops run them too) ->
+    (rows, cols, seq_len): TypeError for a non-tensor, a logits dtype that is not served (float64 among them), labels that are not int64
+    (probability targets among them) or an ignore_index that is no int; ValueError for fewer than two dimensions, labels that are not of
+    the logits' shape without its last dimension, an empty shape, or a reduction other than 'mean' and 'sum'."""
+    for name, t in (("logits", logits), ("labels", labels)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t).__name__}")
+    if logits.dtype not in _KD_DTYPES:
+        raise TypeError(f"{what}: dtype {logits.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+    if labels.dtype != torch.int64:
+        raise TypeError(f"{what}: labels of dtype {labels.dtype} are not served: {_CE_SERVED}")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+        raise TypeError(f"{what}: ignore_index is an int, got {type(ignore_index).__name__}")
+    if reduction not in _CE_REDUCTIONS:
+        raise ValueError(f"{what}: reduction={reduction!r} is not served: {_CE_SERVED}")
+    if logits.dim() < 2:
+        raise ValueError(f"{what}: the logits need at least two dimensions [..., positions, vocabulary], got {tuple(logits.shape)}")
+    if tuple(labels.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"{what}: shape mismatch: logits {tuple(logits.shape)} want labels {tuple(logits.shape[:-1])}, got {tuple(labels.shape)}")
+    if logits.numel() == 0:
+        raise ValueError(f"{what}: empty logits {tuple(logits.shape)}: a loss has no empty launch")
+    cols = logits.shape[-1]
+    return logits.numel() // cols, cols, logits.shape[-2]
+
+
+def ce_inputs(logits, labels, shift=False, ignore_index=-100, reduction="mean", what="cross_entropy"):
+    """check_ce, then the device (CUDA, the same one), then the copy route: a non-contiguous tensor is copied once (copy_route)
+    -> (logits, labels, rows, cols, seq_len)"""
+    rows, cols, seq_len = check_ce(logits, labels, shift, ignore_index, reduction, what)
+    _prep(logits, what)
+    if labels.device != logits.device:
+        raise ValueError(f"{what}: logits are on {logits.device}, labels on {labels.device}")
+    if not logits.is_contiguous():
+        ce_counts["copy_route"] += 1
+        logits = logits.contiguous()
+    if not labels.is_contiguous():
+        ce_counts["copy_route"] += 1
+        labels = labels.contiguous()
+    return logits, labels, rows, cols, seq_len
+
+
+def ce_forward(logits, labels, shift=False, ignore_index=-100, reduction="mean", need_stats=True):
+    """-> (loss, row_lse, row_loss, n_valid): the fp32 0-dim loss, the [rows] fp32 logsumexp of every valid row that the backward reads
+    (None with need_stats=False: no buffer, nothing written), the [rows] fp32 row losses (0 for ignored rows) and the int64 [1] count
+    of valid rows, rows = numel / shape[-1]; all four are views of one buffer.  shift: row r is scored against labels[r + 1] and the
+    last position of every sequence (shape[-2] positions) is ignored.  fp32 arithmetic whatever the logits' dtype; two launches on the
+    current stream (the rows, the sum and the count), counted as one fwd_launch."""
+    logits, labels, rows, cols, seq_len = ce_inputs(logits, labels, shift, ignore_index, reduction, "ce_forward")
+    side = torch.empty(2 + rows * (2 if need_stats else 1) + 1, dtype=torch.float32, device=logits.device)   # n_valid | row_lse | row_loss | loss
+    n_valid = side[:2].view(torch.int64)
+    row_lse = side[2:2 + rows] if need_stats else None
+    row_loss, loss = side[-rows - 1:-1], side[-1]
+    rc = _launch(logits, _lib.lib().fqc_ce_fwd, logits.data_ptr(), labels.data_ptr(), row_lse.data_ptr() if need_stats else None,
+                 row_loss.data_ptr(), loss.data_ptr(), n_valid.data_ptr(), rows, cols, seq_len, int(bool(shift)), ignore_index,
+                 _CE_REDUCTIONS[reduction], _KD_DTYPES[logits.dtype])
+    _lib.check(rc, "ce_forward")
+    ce_counts["fwd_launch"] += 1
+    return loss, row_lse, row_loss, n_valid
+
+
+def ce_backward(logits, labels, row_lse, n_valid, grad_loss, shift=False, ignore_index=-100, reduction="mean"):
+    """-> grad_logits = (grad_loss / n) (softmax(logits) - onehot(label)) for valid rows (the divisor is 1 under 'sum'), zeros for ignored
+    ones, of the logits' shape and dtype, rounded once from fp32.  row_lse, n_valid: ce_forward's, on the same logits, labels and
+    settings; grad_loss: the upstream gradient of the loss, a one-element CUDA tensor that the kernel reads on the device, as it reads
+    n_valid (no host synchronisation).  One launch (bwd_launch)."""
+    with torch.no_grad():
+        logits, labels, rows, cols, seq_len = ce_inputs(logits, labels, shift, ignore_index, reduction, "ce_backward")
+    if not (isinstance(row_lse, torch.Tensor) and row_lse.dtype == torch.float32 and tuple(row_lse.shape) == (rows,)
+            and row_lse.device == logits.device and row_lse.is_contiguous()):
+        raise ValueError(f"ce_backward: row_lse is ce_forward's contiguous fp32 [{rows}] tensor on {logits.device}")
+    if not (isinstance(n_valid, torch.Tensor) and n_valid.dtype == torch.int64 and n_valid.numel() == 1 and n_valid.device == logits.device):
+        raise ValueError(f"ce_backward: n_valid is ce_forward's one-element int64 tensor on {logits.device}")
+    if not (isinstance(grad_loss, torch.Tensor) and grad_loss.numel() == 1 and grad_loss.device == logits.device):
+        raise ValueError(f"ce_backward: grad_loss is a one-element tensor on {logits.device}")
+    g = grad_loss.detach().reshape(1)
+    if g.dtype != torch.float32:
+        g = g.float()
+    grad = torch.empty_like(logits)
+    rc = _launch(logits, _lib.lib().fqc_ce_bwd, logits.data_ptr(), labels.data_ptr(), row_lse.data_ptr(), n_valid.data_ptr(), g.data_ptr(),
+                 grad.data_ptr(), rows, cols, seq_len, int(bool(shift)), ignore_index, _CE_REDUCTIONS[reduction], _KD_DTYPES[logits.dtype])
+    _lib.check(rc, "ce_backward")
+    ce_counts["bwd_launch"] += 1
+    return grad
