@@ -1,7 +1,7 @@
 // fq_ce_loss.h -- the language-model loss cross_entropy(logits, labels, ignore_index) with the causal one-position shift done in the
 // kernel, and its gradient: the kernels behind include/llmqat_fakequant_ce.h.  fp32 arithmetic whatever the
 // logits' dtype; neither a shifted [B, T-1, V] copy nor an fp32 [rows, cols] tensor ever exists.  The simpler sibling of fq_kd_loss.h (one
-// logit tensor instead of two), whose exponentials, reference point, unpacking and reductions it reuses.
+// logit tensor instead of two); both stand on the row-softmax layer of fq_loss_rows.h.
 //
 //   ce_fwd_kernel   one pass over a row with an online logsumexp.  A lane's running state is m, z = max and sum e^(x - m) of the elements
 //                   it has seen, rebased once per 16-byte vector to the vector's maximum (as kd_accumulate), not once per element.  At
@@ -12,7 +12,7 @@
 //                   the stream, and a label outside [0, cols) is never an address (the row's loss is NaN).
 //   ce_sum_kernel   one workgroup: the row losses summed in float64 in a fixed order and the valid rows counted (int64), loss = sum / n
 //                   ("mean": 0 / 0 = NaN when every row is ignored) or sum, rounded once to fp32; n is left on the device for the backward.
-//   ce_bwd_kernel   one pass: grad = (g / n) (e^(x - lse) - [c == y]), rounded once to the dtype (kd_exp_acc).  The one-hot is applied
+//   ce_bwd_kernel   one pass: grad = (g / n) (e^(x - lse) - [c == y]), rounded once to the dtype (loss_exp_acc).  The one-hot is applied
 //                   per vector: one range test of the label's column against the vector's, taken by one lane of the row once.
 //
 // The effective label of row r (ce_label): labels[r], or with shift, labels[r + 1] for every row but the last of each sequence of
@@ -20,23 +20,17 @@
 // checks), so r + 1 < rows wherever it is read.  An IGNORED ROW IS NEVER READ: the forward writes row_loss = 0 (and lse = 0) and returns,
 // the backward stores zeros with the width it stores gradients with, so a NaN or inf there reaches nothing.
 //
-// Launch shape and access paths are those of fq_kd_loss.h: rows of CE_WIDE elements or more take a 256-thread workgroup each, shorter
-// ones a wave each, four to a workgroup (no LDS, no barrier); 16-byte accesses where the base pointers are 16-byte aligned and a row is
-// whole vectors, else element accesses in groups of KD_EG strided elements (any cols, any alignment).  A row is valid or ignored as a
-// whole, and a row belongs to one wave (TPR = 64) or one workgroup (TPR = 256): the early return is uniform over whatever meets a barrier.
+// Launch shape, access paths, the exponentials and the reference point are the shared layer's (fq_loss_rows.h).  A row is valid or ignored
+// as a whole, and a row belongs to one wave (TPR = 64) or one workgroup (TPR = 256): the early return is uniform over whatever meets a barrier.
 // CE_FWD_VIF / CE_BWD_VIF: 16-byte vectors a lane keeps in flight (A/B macros, as the two cache policies; DESIGN.md section 23 has the
 // measurement).
 //
-// Special values.  v_max_f32 ignores a NaN operand, but e^(NaN - m) is NaN: z, hence lse, the row's loss and its gradient are NaN.
-// A row of only -inf has reference point 0 (kd_ref) and z = 0: lse = -inf, row_loss = -inf - -inf = NaN, as ATen's.  x[y] = -inf under a
+// Special values of this loss.  A NaN element makes z, hence lse, the row's loss and its gradient NaN.  A row of only -inf has
+// reference point 0 and z = 0: lse = -inf, row_loss = -inf - -inf = NaN, as ATen's.  x[y] = -inf under a
 // finite lse gives +inf.  A row that is -inf but for a 0 at the label: m = 0, z = 1, lse = 0 + log 1 = 0, row_loss = 0 - 0 = 0.0 and
 // the gradient e^0 - 1 = 0, e^-inf = 0 elsewhere.
 #pragma once
-// fq_kd_loss.h defines one kernel that is no template, kd_sum_kernel: a second unit that includes the header would define it a second
-// time and collide with fq_kd_loss.hip's at link.  Here it takes a name of this unit's own (and is never launched).
-#define kd_sum_kernel kd_sum_kernel_in_ce_unit
-#include "fq_kd_loss.h"
-#undef kd_sum_kernel
+#include "fq_loss_rows.h"
 
 #ifndef CE_NT_LOAD
 #define CE_NT_LOAD 0     // the logits were written by the GEMM just before and are read again by the backward
@@ -53,7 +47,6 @@
 
 namespace fq {
 
-constexpr int64_t CE_WIDE = KD_WIDE;   // cols from which a row takes the whole workgroup
 constexpr int CE_SUM_TPB = 1024;       // threads of the one workgroup that sums the rows
 constexpr int CE_MEAN = 0, CE_SUM = 1; // FQC_REDUCTION_*
 #define CE_NAN (__builtin_nanf(""))
@@ -95,36 +88,38 @@ __device__ __forceinline__ bool ce_label(const CeLabels& l, int64_t row, int64_t
 }
 
 struct CeState {
-    float m = KD_NEG_INF, z = 0.0f;
+    float m = LOSS_NEG_INF, z = 0.0f;
 };
 // the state re-expressed against the maximum m >= st.m; a lane that has seen nothing finite holds z == 0 and takes the factor 0, not
 // e^(0 - m), which may be inf
 __device__ __forceinline__ void ce_rebase(CeState& st, float m) {
-    const float f = st.m == KD_NEG_INF ? 0.0f : kd_exp(kd_ref(st.m) - kd_ref(m));
+    const float f = st.m == LOSS_NEG_INF ? 0.0f : loss_exp(loss_ref(st.m) - loss_ref(m));
     st.z *= f;
     st.m = m;
 }
+// (not one form with kd_accumulate: this one sums the vector's exponentials first and adds once, that one adds each into the running sum,
+// and either order in the other's place changes its bits)
 template <int N> __device__ __forceinline__ void ce_accumulate(CeState& st, const float (&x)[N]) {
     float vm = x[0];
 #pragma unroll
     for (int i = 1; i < N; ++i) vm = __builtin_fmaxf(vm, x[i]);
     ce_rebase(st, __builtin_fmaxf(st.m, vm));
-    const float r = kd_ref(st.m);
+    const float r = loss_ref(st.m);
     float z = 0.0f;
 #pragma unroll
-    for (int i = 0; i < N; ++i) z += kd_exp(x[i] - r);
+    for (int i = 0; i < N; ++i) z += loss_exp(x[i] - r);
     st.z += z;
 }
 
 template <int DT, bool VEC, int TPR>
-__global__ __launch_bounds__(KD_TPB) void ce_fwd_kernel(CeFwdArgs a) {
+__global__ __launch_bounds__(LOSS_TPB) void ce_fwd_kernel(CeFwdArgs a) {
     using T = Ty<DT>;
-    constexpr int EPV = 16 / T::ESIZE, RPB = KD_TPB / TPR, NW = TPR / 64, VIF = CE_FWD_VIF;
+    constexpr int EPV = 16 / T::ESIZE, NW = TPR / 64, VIF = CE_FWD_VIF;
     constexpr uint32_t NEG_INF_WORD = DT == F32 ? 0xFF800000u : DT == BF16 ? 0xFF80FF80u : 0xFC00FC00u;   // -inf in every element of a dword
     __shared__ uint32_t lds_max[1][4], lds_sum[1][4];
-    const int lane = threadIdx.x & (TPR - 1);
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / TPR;
-    if (row >= a.lab.rows) return;      // RPB > 1 only: a whole wave, and those rows meet no barrier
+    int64_t row;
+    int lane;
+    if (!loss_row_lane<TPR>(a.lab.rows, row, lane)) return;
     int64_t y;
     if (!ce_label(a.lab, row, y)) {     // uniform over the row's lanes: nothing of the row is read
         if (lane == 0) {
@@ -153,30 +148,24 @@ __global__ __launch_bounds__(KD_TPB) void ce_fwd_kernel(CeFwdArgs a) {
             for (int i = 0; i < VIF; ++i) {
                 if (i > 0 && v + i * TPR >= nvec) r[i] = make_uint4(NEG_INF_WORD, NEG_INF_WORD, NEG_INF_WORD, NEG_INF_WORD);
                 float f[EPV];
-                kd_unpack<DT>(r[i], f);
+                loss_unpack<DT>(r[i], f);
                 ce_accumulate(st, f);
             }
         }
     } else {
-        for (int64_t c = lane; c < a.cols; c += KD_EG * TPR) {
-            float f[KD_EG];
-#pragma unroll
-            for (int i = 0; i < KD_EG; ++i) {
-                const int64_t ci = c + i * TPR;
-                const bool in = ci < a.cols;
-                const float x = T::load1(a.x, base + (in ? ci : c));
-                f[i] = in ? x : KD_NEG_INF;
-            }
+        for (int64_t c = lane; c < a.cols; c += LOSS_EG * TPR) {
+            float f[LOSS_EG];
+            loss_load_group<DT, TPR>(a.x, base, c, a.cols, f);
             ce_accumulate(st, f);
         }
     }
     uint32_t m[1] = {as_u(st.m)};
-    kd_reduce<OpMaxF, NW>(m, lds_max);
+    loss_reduce<OpMaxF, NW>(m, lds_max);
     ce_rebase(st, as_f(m[0]));
     uint32_t z[1] = {as_u(st.z)};
-    kd_reduce<OpAddF, NW>(z, lds_sum);
+    loss_reduce<OpAddF, NW>(z, lds_sum);
     if (lane == 0) {
-        const float lse = kd_ref(st.m) + __builtin_logf(as_f(z[0]));
+        const float lse = loss_ref(st.m) + __builtin_logf(as_f(z[0]));
         if (a.row_lse) a.row_lse[row] = lse;
         a.row_loss[row] = lse - xy;
     }
@@ -213,7 +202,7 @@ __global__ __launch_bounds__(CE_SUM_TPB) void ce_sum_kernel(const float* row_los
 // e^(x - lse) in place, the 1 of the one-hot taken from slot `hot` (a slot of this vector, or anything else: no slot), times gn
 template <int N> __device__ __forceinline__ void ce_grad(float (&x)[N], float lse, float gn, uint64_t hot) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) x[i] = kd_exp_acc(x[i] - lse);
+    for (int i = 0; i < N; ++i) x[i] = loss_exp_acc(x[i] - lse);
     if (hot < (uint64_t)N) {            // one test per vector; true for one lane of the row, once
 #pragma unroll
         for (int i = 0; i < N; ++i) x[i] -= (uint64_t)i == hot ? 1.0f : 0.0f;
@@ -224,26 +213,18 @@ template <int N> __device__ __forceinline__ void ce_grad(float (&x)[N], float ls
 template <int DT> __device__ __forceinline__ uint4 ce_grad_vec(const uint4& x, float lse, float gn, uint64_t hot) {
     using T = Ty<DT>;
     float f[16 / T::ESIZE];
-    kd_unpack<DT>(x, f);
+    loss_unpack<DT>(x, f);
     ce_grad(f, lse, gn, hot);
-    uint32_t o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        float e[T::EPD];
-#pragma unroll
-        for (int k = 0; k < T::EPD; ++k) e[k] = f[d * T::EPD + k];
-        o[d] = T::pack(e);
-    }
-    return make_uint4(o[0], o[1], o[2], o[3]);
+    return loss_pack<DT>(f);
 }
 
 template <int DT, bool VEC, int TPR>
-__global__ __launch_bounds__(KD_TPB) void ce_bwd_kernel(CeBwdArgs a) {
+__global__ __launch_bounds__(LOSS_TPB) void ce_bwd_kernel(CeBwdArgs a) {
     using T = Ty<DT>;
-    constexpr int EPV = 16 / T::ESIZE, RPB = KD_TPB / TPR, VIF = CE_BWD_VIF;
-    const int lane = threadIdx.x & (TPR - 1);
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / TPR;
-    if (row >= a.lab.rows) return;
+    constexpr int EPV = 16 / T::ESIZE, VIF = CE_BWD_VIF;
+    int64_t row;
+    int lane;
+    if (!loss_row_lane<TPR>(a.lab.rows, row, lane)) return;
     const int64_t base = row * a.cols;
     int64_t y;
     if (!ce_label(a.lab, row, y)) {     // zeros, with the width the gradient is stored with; the row's logits are not read
@@ -277,10 +258,10 @@ __global__ __launch_bounds__(KD_TPB) void ce_bwd_kernel(CeBwdArgs a) {
             }
         }
     } else {
-        for (int64_t c = lane; c < a.cols; c += KD_EG * TPR) {
-            float f[KD_EG];
+        for (int64_t c = lane; c < a.cols; c += LOSS_EG * TPR) {
+            float f[LOSS_EG];
 #pragma unroll
-            for (int i = 0; i < KD_EG; ++i) {
+            for (int i = 0; i < LOSS_EG; ++i) {
                 const int64_t ci = c + i * TPR;
                 f[i] = T::load1(a.x, base + (ci < a.cols ? ci : c));
             }
@@ -288,7 +269,7 @@ __global__ __launch_bounds__(KD_TPB) void ce_bwd_kernel(CeBwdArgs a) {
             const int64_t d = y - c;
             ce_grad(f, lse, gn, d >= 0 && d % TPR == 0 ? (uint64_t)(d / TPR) : ~(uint64_t)0);
 #pragma unroll
-            for (int i = 0; i < KD_EG; ++i) {
+            for (int i = 0; i < LOSS_EG; ++i) {
                 const int64_t ci = c + i * TPR;
                 if (ci < a.cols) T::store1(a.gx, base + ci, f[i]);
             }

@@ -1360,7 +1360,7 @@ def mx_dequantize(e, dtype=None):
 MX_GEMM_KSTEP = 128      # k of one v_mfma_scale_f32_16x16x128_f8f6f4: K must be a multiple
 MX_GEMM_SKINNY_M = 32    # rows of `a` up to which the skinny (decode) kernel runs
 MX_GEMM_FORMATS = ("mxfp4", "mxfp8_e4m3", "mxfp8_e5m2")
-_OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+_OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}   # what the GEMM and the dequantize write, and the logits the losses read
 
 
 def check_mx_matmul(a_shape, a_fmt, w_shape, w_fmt, out_dtype):
@@ -1435,28 +1435,63 @@ def mx_matmul(a, w, out_dtype=None):
     return mx_matmul_tensors(a.elements, a.scales, a.fmt, w.elements, w.scales.reshape(w.shape[0], -1), w.fmt, a.shape, out_dtype)
 
 
+# ---- what the fused losses share.  The four argument checks stand one by one, because each loss puts checks of
+# its own between them and the order of its refusals is pinned: one message each, whatever the order ---------------------------------------
+def _loss_tensors(what, **named):
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t).__name__}")
+
+
+def _loss_dtype(what, logits):
+    if logits.dtype not in _OUT_DTYPES:
+        raise TypeError(f"{what}: dtype {logits.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+
+
+def _loss_dims(what, logits, layout):
+    if logits.dim() < 2:
+        raise ValueError(f"{what}: the logits need at least two dimensions {layout}, got {tuple(logits.shape)}")
+
+
+def _loss_not_empty(what, logits):
+    if logits.numel() == 0:
+        raise ValueError(f"{what}: empty logits {tuple(logits.shape)}: a loss has no empty launch")
+
+
+def _loss_contig(t, counts):   # the copy route: a non-contiguous tensor is copied once, and counted
+    if not t.is_contiguous():
+        counts["copy_route"] += 1
+    return t.contiguous()
+
+
+def _loss_stats(what, t, name, shape, logits):   # the forward's row statistics (name: "<argument> is <forward>'s") as the backward wants them
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape and t.device == logits.device and t.is_contiguous()):
+        raise ValueError(f"{what}: {name} contiguous fp32 {list(shape)} tensor on {logits.device}")
+
+
+def _loss_grad(what, grad_loss, logits):   # the upstream gradient as the kernel reads it on the device: detached, fp32, [1]
+    if not (isinstance(grad_loss, torch.Tensor) and grad_loss.numel() == 1 and grad_loss.device == logits.device):
+        raise ValueError(f"{what}: grad_loss is a one-element tensor on {logits.device}")
+    g = grad_loss.detach().reshape(1)
+    return g if g.dtype == torch.float32 else g.float()
+
+
 # ---- the distillation loss kl_div(log_softmax(student), softmax(teacher), "batchmean") (the fql_ header) ----------
 kd_counts = {"fwd_launch": 0, "bwd_launch": 0, "copy_route": 0}
-_KD_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 
 
 def check_kd(student, teacher, what="kd_kl_loss"):
     """The argument checks of the loss on types, shapes and dtypes alone (the fake implementations of the compiled ops run them too) ->
     (rows, cols, batch): TypeError for a non-tensor, mixed dtypes or a dtype that is not served (float64 among them), ValueError for
     unequal shapes, fewer than two dimensions, an empty shape, or a teacher that requires grad while grad mode is on."""
-    for name, t in (("student_logits", student), ("teacher_logits", teacher)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t).__name__}")
+    _loss_tensors(what, student_logits=student, teacher_logits=teacher)
     if student.dtype != teacher.dtype:
         raise TypeError(f"{what}: mixed dtypes are not served: student_logits is {student.dtype}, teacher_logits is {teacher.dtype}")
-    if student.dtype not in _KD_DTYPES:
-        raise TypeError(f"{what}: dtype {student.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+    _loss_dtype(what, student)
     if tuple(student.shape) != tuple(teacher.shape):
         raise ValueError(f"{what}: shape mismatch: student_logits {tuple(student.shape)}, teacher_logits {tuple(teacher.shape)}")
-    if student.dim() < 2:
-        raise ValueError(f"{what}: the logits need at least two dimensions [batch, ..., vocabulary], got {tuple(student.shape)}")
-    if student.numel() == 0:
-        raise ValueError(f"{what}: empty logits {tuple(student.shape)}: a loss has no empty launch")
+    _loss_dims(what, student, "[batch, ..., vocabulary]")
+    _loss_not_empty(what, student)
     if teacher.requires_grad and torch.is_grad_enabled():
         raise ValueError(f"{what}: teacher_logits requires grad: the loss has no gradient for the teacher; pass teacher_logits.detach()")
     cols = student.shape[-1]
@@ -1471,13 +1506,7 @@ def kd_inputs(student, teacher, what="kd_kl_loss"):
     _prep(teacher, what)
     if student.device != teacher.device:
         raise ValueError(f"{what}: student_logits is on {student.device}, teacher_logits on {teacher.device}")
-    if not student.is_contiguous():
-        kd_counts["copy_route"] += 1
-        student = student.contiguous()
-    if not teacher.is_contiguous():
-        kd_counts["copy_route"] += 1
-        teacher = teacher.contiguous()
-    return student, teacher, rows, cols, batch
+    return _loss_contig(student, kd_counts), _loss_contig(teacher, kd_counts), rows, cols, batch
 
 
 def kd_kl_forward(student, teacher, need_stats=True):
@@ -1489,7 +1518,7 @@ def kd_kl_forward(student, teacher, need_stats=True):
     stats = side[:2 * rows].view(rows, 2) if need_stats else None
     row_loss, loss = side[-rows - 1:-1], side[-1]
     rc = _launch(student, _lib.lib().fql_kd_kl_fwd, student.data_ptr(), teacher.data_ptr(), stats.data_ptr() if need_stats else None,
-                 row_loss.data_ptr(), loss.data_ptr(), rows, cols, batch, _KD_DTYPES[student.dtype])
+                 row_loss.data_ptr(), loss.data_ptr(), rows, cols, batch, _OUT_DTYPES[student.dtype])
     _lib.check(rc, "kd_kl_forward")
     kd_counts["fwd_launch"] += 1
     return loss, stats, row_loss
@@ -1501,17 +1530,11 @@ def kd_kl_backward(student, teacher, row_stats, grad_loss):
     reads on the device (no host synchronisation).  One launch (bwd_launch)."""
     with torch.no_grad():
         student, teacher, rows, cols, batch = kd_inputs(student, teacher, "kd_kl_backward")
-    if not (isinstance(row_stats, torch.Tensor) and row_stats.dtype == torch.float32 and tuple(row_stats.shape) == (rows, 2)
-            and row_stats.device == student.device and row_stats.is_contiguous()):
-        raise ValueError(f"kd_kl_backward: row_stats is kd_kl_forward's contiguous fp32 [{rows}, 2] tensor on {student.device}")
-    if not (isinstance(grad_loss, torch.Tensor) and grad_loss.numel() == 1 and grad_loss.device == student.device):
-        raise ValueError(f"kd_kl_backward: grad_loss is a one-element tensor on {student.device}")
-    g = grad_loss.detach().reshape(1)
-    if g.dtype != torch.float32:
-        g = g.float()
+    _loss_stats("kd_kl_backward", row_stats, "row_stats is kd_kl_forward's", (rows, 2), student)
+    g = _loss_grad("kd_kl_backward", grad_loss, student)
     grad = torch.empty_like(student)
     rc = _launch(student, _lib.lib().fql_kd_kl_bwd, student.data_ptr(), teacher.data_ptr(), row_stats.data_ptr(), g.data_ptr(), grad.data_ptr(),
-                 rows, cols, batch, _KD_DTYPES[student.dtype])
+                 rows, cols, batch, _OUT_DTYPES[student.dtype])
     _lib.check(rc, "kd_kl_backward")
     kd_counts["bwd_launch"] += 1
     return grad
@@ -1529,23 +1552,18 @@ def check_ce(logits, labels, shift=False, ignore_index=-100, reduction="mean", w
     (rows, cols, seq_len): TypeError for a non-tensor, a logits dtype that is not served (float64 among them), labels that are not int64
     (probability targets among them) or an ignore_index that is no int; ValueError for fewer than two dimensions, labels that are not of
     the logits' shape without its last dimension, an empty shape, or a reduction other than 'mean' and 'sum'."""
-    for name, t in (("logits", logits), ("labels", labels)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t).__name__}")
-    if logits.dtype not in _KD_DTYPES:
-        raise TypeError(f"{what}: dtype {logits.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+    _loss_tensors(what, logits=logits, labels=labels)
+    _loss_dtype(what, logits)
     if labels.dtype != torch.int64:
         raise TypeError(f"{what}: labels of dtype {labels.dtype} are not served: {_CE_SERVED}")
     if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
         raise TypeError(f"{what}: ignore_index is an int, got {type(ignore_index).__name__}")
     if reduction not in _CE_REDUCTIONS:
         raise ValueError(f"{what}: reduction={reduction!r} is not served: {_CE_SERVED}")
-    if logits.dim() < 2:
-        raise ValueError(f"{what}: the logits need at least two dimensions [..., positions, vocabulary], got {tuple(logits.shape)}")
+    _loss_dims(what, logits, "[..., positions, vocabulary]")
     if tuple(labels.shape) != tuple(logits.shape[:-1]):
         raise ValueError(f"{what}: shape mismatch: logits {tuple(logits.shape)} want labels {tuple(logits.shape[:-1])}, got {tuple(labels.shape)}")
-    if logits.numel() == 0:
-        raise ValueError(f"{what}: empty logits {tuple(logits.shape)}: a loss has no empty launch")
+    _loss_not_empty(what, logits)
     cols = logits.shape[-1]
     return logits.numel() // cols, cols, logits.shape[-2]
 
@@ -1557,13 +1575,7 @@ def ce_inputs(logits, labels, shift=False, ignore_index=-100, reduction="mean", 
     _prep(logits, what)
     if labels.device != logits.device:
         raise ValueError(f"{what}: logits are on {logits.device}, labels on {labels.device}")
-    if not logits.is_contiguous():
-        ce_counts["copy_route"] += 1
-        logits = logits.contiguous()
-    if not labels.is_contiguous():
-        ce_counts["copy_route"] += 1
-        labels = labels.contiguous()
-    return logits, labels, rows, cols, seq_len
+    return _loss_contig(logits, ce_counts), _loss_contig(labels, ce_counts), rows, cols, seq_len
 
 
 def ce_forward(logits, labels, shift=False, ignore_index=-100, reduction="mean", need_stats=True):
@@ -1579,7 +1591,7 @@ def ce_forward(logits, labels, shift=False, ignore_index=-100, reduction="mean",
     row_loss, loss = side[-rows - 1:-1], side[-1]
     rc = _launch(logits, _lib.lib().fqc_ce_fwd, logits.data_ptr(), labels.data_ptr(), row_lse.data_ptr() if need_stats else None,
                  row_loss.data_ptr(), loss.data_ptr(), n_valid.data_ptr(), rows, cols, seq_len, int(bool(shift)), ignore_index,
-                 _CE_REDUCTIONS[reduction], _KD_DTYPES[logits.dtype])
+                 _CE_REDUCTIONS[reduction], _OUT_DTYPES[logits.dtype])
     _lib.check(rc, "ce_forward")
     ce_counts["fwd_launch"] += 1
     return loss, row_lse, row_loss, n_valid
@@ -1592,19 +1604,13 @@ def ce_backward(logits, labels, row_lse, n_valid, grad_loss, shift=False, ignore
     n_valid (no host synchronisation).  One launch (bwd_launch)."""
     with torch.no_grad():
         logits, labels, rows, cols, seq_len = ce_inputs(logits, labels, shift, ignore_index, reduction, "ce_backward")
-    if not (isinstance(row_lse, torch.Tensor) and row_lse.dtype == torch.float32 and tuple(row_lse.shape) == (rows,)
-            and row_lse.device == logits.device and row_lse.is_contiguous()):
-        raise ValueError(f"ce_backward: row_lse is ce_forward's contiguous fp32 [{rows}] tensor on {logits.device}")
+    _loss_stats("ce_backward", row_lse, "row_lse is ce_forward's", (rows,), logits)
     if not (isinstance(n_valid, torch.Tensor) and n_valid.dtype == torch.int64 and n_valid.numel() == 1 and n_valid.device == logits.device):
         raise ValueError(f"ce_backward: n_valid is ce_forward's one-element int64 tensor on {logits.device}")
-    if not (isinstance(grad_loss, torch.Tensor) and grad_loss.numel() == 1 and grad_loss.device == logits.device):
-        raise ValueError(f"ce_backward: grad_loss is a one-element tensor on {logits.device}")
-    g = grad_loss.detach().reshape(1)
-    if g.dtype != torch.float32:
-        g = g.float()
+    g = _loss_grad("ce_backward", grad_loss, logits)
     grad = torch.empty_like(logits)
     rc = _launch(logits, _lib.lib().fqc_ce_bwd, logits.data_ptr(), labels.data_ptr(), row_lse.data_ptr(), n_valid.data_ptr(), g.data_ptr(),
-                 grad.data_ptr(), rows, cols, seq_len, int(bool(shift)), ignore_index, _CE_REDUCTIONS[reduction], _KD_DTYPES[logits.dtype])
+                 grad.data_ptr(), rows, cols, seq_len, int(bool(shift)), ignore_index, _CE_REDUCTIONS[reduction], _OUT_DTYPES[logits.dtype])
     _lib.check(rc, "ce_backward")
     ce_counts["bwd_launch"] += 1
     return grad
