@@ -41,6 +41,8 @@ LOSS_EXPORTS = ("fql_kd_kl_fwd", "fql_kd_kl_bwd")
 # every symbol include/llmqat_fakequant_ce.h declares (the fqc_ family: the language-model cross-entropy loss)
 CE_EXPORTS = ("fqc_ce_fwd", "fqc_ce_bwd")
 CE_MEAN, CE_SUM = 0, 1   # FQC_REDUCTION_*
+# every symbol include/llmqat_fakequant_norm.h declares (the fqn_ family: the RMSNorm in front of the quantized projections)
+NORM_EXPORTS = ("fqn_rms_norm_fwd", "fqn_rms_norm_bwd", "fqn_rms_norm_bwd_parts", "fqn_rms_norm_bwd_workspace_bytes")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -181,6 +183,14 @@ def _bind(L):
     L.fqc_ce_fwd.restype = i32
     L.fqc_ce_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i64, i32, i32, vp]
     L.fqc_ce_bwd.restype = i32
+    L.fqn_rms_norm_fwd.argtypes = [vp, vp, vp, vp, i64, i64, f32, i32, i32, vp]
+    L.fqn_rms_norm_fwd.restype = i32
+    L.fqn_rms_norm_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i32, i32, vp]
+    L.fqn_rms_norm_bwd.restype = i32
+    L.fqn_rms_norm_bwd_parts.argtypes = [i64, i64]
+    L.fqn_rms_norm_bwd_parts.restype = i64
+    L.fqn_rms_norm_bwd_workspace_bytes.argtypes = [i64, i64]
+    L.fqn_rms_norm_bwd_workspace_bytes.restype = sz
     return L
 
 

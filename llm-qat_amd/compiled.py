@@ -347,3 +347,50 @@ ce_fwd_op.register_autograd(_ce_backward, setup_context=_ce_setup)
 def ce_loss(logits, labels, shift, ignore_index, reduction):
     """lm_loss.cross_entropy / causal_lm_loss while compiling"""
     return ce_fwd_op(logits, labels, shift, ignore_index, reduction)[0]
+
+
+# ---- the RMSNorm (ops.rms_norm_forward / ops.rms_norm_backward, DESIGN.md section 25): (y, rstd) and (dx, dw) ------------------------------
+@torch.library.custom_op("llmqat_amd::rms_norm_fwd", mutates_args=(), device_types="cuda")
+def rms_norm_fwd_op(x: torch.Tensor, weight: torch.Tensor, eps: float, need_stats: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    y, rstd = ops.rms_norm_forward(x, weight, eps, need_stats)
+    return y, (rstd if need_stats else x.new_empty(0, dtype=torch.float32))      # an op returns tensors: an empty one for "not written"
+
+
+@rms_norm_fwd_op.register_fake
+def _(x, weight, eps, need_stats):
+    rows, _ = ops.check_rms_norm(x, weight, eps)
+    return x.new_empty(x.shape, dtype=weight.dtype), x.new_empty((rows if need_stats else 0,), dtype=torch.float32)
+
+
+@torch.library.custom_op("llmqat_amd::rms_norm_bwd", mutates_args=(), device_types="cuda")
+def rms_norm_bwd_op(g: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, rstd: torch.Tensor, need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    dx, dw = ops.rms_norm_backward(g, x, weight, rstd, need_dx, need_dw)
+    return (dx if need_dx else x.new_empty(0)), (dw if need_dw else weight.new_empty(0))      # an op returns tensors: an empty one for "not asked for"
+
+
+@rms_norm_bwd_op.register_fake
+def _(g, x, weight, rstd, need_dx, need_dw):
+    ops.check_rms_norm(x, weight)
+    return (torch.empty_like(x, memory_format=torch.contiguous_format) if need_dx else x.new_empty(0),
+            torch.empty_like(weight) if need_dw else weight.new_empty(0))
+
+
+def _rms_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[1])
+
+
+def _rms_backward(ctx, grad_y, grad_rstd):
+    x, weight, rstd = ctx.saved_tensors
+    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    dx, dw = rms_norm_bwd_op(grad_y, x, weight, rstd, need_dx, need_dw)
+    return (dx if need_dx else None), (dw if need_dw else None), None, None
+
+
+rms_norm_fwd_op.register_autograd(_rms_backward, setup_context=_rms_setup)
+
+
+def rms_norm(x, weight, eps):
+    """norm.rms_norm while compiling; as in eager mode no rstd is written when no gradient can be asked for (grad mode and the inputs'
+    requires_grad are known while tracing)"""
+    need = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)
+    return rms_norm_fwd_op(x, weight, float(eps), need)[0]

@@ -64,3 +64,12 @@ def low_bit_weight(w, w_bits, layerwise):
         sc, nb, cv = 2 * m, 2 ** (w_bits - 1), 1 - 1e-2
         q = sc * (torch.round(torch.clamp(w / sc, -cv, cv) * nb - 0.5) + 0.5) / nb
     return q - w + w
+
+
+def rms_norm(x, w, eps):
+    """LlamaRMSNorm.forward (models/modeling_llama_quant.py:121-129), differentiated by autograd as the reference's is"""
+    variance = x.to(torch.float32).pow(2).mean(-1, keepdim=True)
+    x = x * torch.rsqrt(variance + eps)
+    if w.dtype in (torch.float16, torch.bfloat16):
+        x = x.to(w.dtype)
+    return w * x

@@ -1614,3 +1614,84 @@ def ce_backward(logits, labels, row_lse, n_valid, grad_loss, shift=False, ignore
     _lib.check(rc, "ce_backward")
     ce_counts["bwd_launch"] += 1
     return grad
+
+
+# ---- the RMSNorm  w * (x * rsqrt(mean(x^2) + eps))  in front of the quantized projections (the fqn_ header) ----------
+norm_counts = {"fwd_launch": 0, "bwd_launch": 0, "copy_route": 0}
+_NORM_SERVED = "equal dtypes (float32, bfloat16, float16) and the pairs in which exactly one of x and weight is float32 are served"
+
+
+def check_rms_norm(x, w, eps=1e-6, what="rms_norm"):
+    """The argument checks of the norm on types, shapes and dtypes alone (the fake implementations of the compiled ops run them too) ->
+    (rows, cols): TypeError for a non-tensor, a dtype or a dtype pair that is not served (float64 and bfloat16 with float16 among them) or
+    an eps that is no number; ValueError for an eps that is negative, NaN or inf, a weight that is not 1-D, an x whose last dimension is
+    not the weight's length, or an empty shape."""
+    _loss_tensors(what, x=x, weight=w)
+    for name, t in (("x", x), ("weight", w)):
+        if t.dtype not in _OUT_DTYPES:
+            raise TypeError(f"{what}: {name} of dtype {t.dtype} is not served: {_NORM_SERVED}; the arithmetic is fp32 for all of them")
+    if x.dtype != w.dtype and torch.float32 not in (x.dtype, w.dtype):
+        raise TypeError(f"{what}: the dtype pair (x {x.dtype}, weight {w.dtype}) is not served: {_NORM_SERVED}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)):
+        raise TypeError(f"{what}: eps is a number, got {type(eps).__name__}")
+    if not 0 <= eps < float("inf"):
+        raise ValueError(f"{what}: eps={eps} must be finite and not negative")
+    if w.dim() != 1:
+        raise ValueError(f"{what}: weight is 1-D [hidden], got shape {tuple(w.shape)}")
+    if x.dim() < 1 or x.shape[-1] != w.shape[0]:
+        raise ValueError(f"{what}: shape mismatch: x {tuple(x.shape)} wants a weight of {x.shape[-1] if x.dim() else '?'} elements, got {w.shape[0]}")
+    if x.numel() == 0:
+        raise ValueError(f"{what}: empty x {tuple(x.shape)}: a norm has no empty launch")
+    return x.numel() // w.shape[0], w.shape[0]
+
+
+def rms_norm_inputs(x, w, eps=1e-6, what="rms_norm"):
+    """check_rms_norm, then the device (CUDA, the same one), then the copy route: a non-contiguous tensor is copied once (copy_route)
+    -> (x, w, rows, cols)"""
+    rows, cols = check_rms_norm(x, w, eps, what)
+    _prep(x, what)
+    _prep(w, what)
+    if x.device != w.device:
+        raise ValueError(f"{what}: x is on {x.device}, weight on {w.device}")
+    return _loss_contig(x, norm_counts), _loss_contig(w, norm_counts), rows, cols
+
+
+def rms_norm_forward(x, w, eps=1e-6, need_stats=True):
+    """-> (y, rstd): y = w * (x * rsqrt(mean(x^2, -1) + eps)) of x's shape and w's dtype, in fp32 arithmetic with the reference chain's
+    roundings, and the fp32 [rows] rstd the backward reads (None with need_stats=False: no buffer, nothing written),
+    rows = numel / shape[-1].  One launch on the current stream (fwd_launch)."""
+    x, w, rows, cols = rms_norm_inputs(x, w, eps, "rms_norm_forward")
+    y = torch.empty(x.shape, dtype=w.dtype, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if need_stats else None
+    rc = _launch(x, _lib.lib().fqn_rms_norm_fwd, x.data_ptr(), w.data_ptr(), y.data_ptr(), rstd.data_ptr() if need_stats else None, rows, cols,
+                 float(eps), _OUT_DTYPES[x.dtype], _OUT_DTYPES[w.dtype])
+    _lib.check(rc, "rms_norm_forward")
+    norm_counts["fwd_launch"] += 1
+    return y, rstd
+
+
+def rms_norm_backward(g, x, w, rstd, need_dx=True, need_dw=True):
+    """-> (dx, dw): with a = g w, n = x rstd and s = mean(a n, -1): dx = rstd (a - n s) of x's shape and dtype, dw = sum over the rows of
+    g n of w's shape and dtype, each rounded once from fp32; None for the one that is not needed (need_dw=False: no partial sums, no second
+    launch, no workspace).  g: the gradient of rms_norm_forward's y (its shape, w's dtype); rstd: rms_norm_forward's, on the same x and
+    eps.  No atomics: two calls give the same bits.  The workspace comes from the caching allocator.  Counted as one bwd_launch."""
+    with torch.no_grad():
+        x, w, rows, cols = rms_norm_inputs(x, w, 0.0, "rms_norm_backward")
+    if not (need_dx or need_dw):
+        raise ValueError("rms_norm_backward: neither dx nor dw is asked for")
+    _loss_tensors("rms_norm_backward", g=g)
+    if g.dtype != w.dtype or tuple(g.shape) != tuple(x.shape) or g.device != x.device:
+        raise ValueError(f"rms_norm_backward: g is the gradient of y: {tuple(x.shape)} of {w.dtype} on {x.device}, got {tuple(g.shape)} of {g.dtype} on {g.device}")
+    _loss_stats("rms_norm_backward", rstd, "rstd is rms_norm_forward's", (rows,), x)
+    g = _loss_contig(g.detach(), norm_counts)
+    L = _lib.lib()
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w) if need_dw else None
+    ws_bytes = L.fqn_rms_norm_bwd_workspace_bytes(rows, cols) if need_dw else 0
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if need_dw else None
+    rc = _launch(x, L.fqn_rms_norm_bwd, g.data_ptr(), x.data_ptr(), w.data_ptr(), rstd.data_ptr(), dx.data_ptr() if need_dx else None,
+                 dw.data_ptr() if need_dw else None, ws.data_ptr() if need_dw else None, ws_bytes, rows, cols, _OUT_DTYPES[x.dtype],
+                 _OUT_DTYPES[w.dtype])
+    _lib.check(rc, "rms_norm_backward")
+    norm_counts["bwd_launch"] += 1
+    return dx, dw
