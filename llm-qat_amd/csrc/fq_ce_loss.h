@@ -1,7 +1,7 @@
 // fq_ce_loss.h -- the language-model loss cross_entropy(logits, labels, ignore_index) with the causal one-position shift done in the
 // kernel, and its gradient: the kernels behind include/llmqat_fakequant_ce.h.  fp32 arithmetic whatever the
 // logits' dtype; neither a shifted [B, T-1, V] copy nor an fp32 [rows, cols] tensor ever exists.  The simpler sibling of fq_kd_loss.h (one
-// logit tensor instead of two); both stand on the row-softmax layer of fq_loss_rows.h.
+// logit tensor instead of two); both stand on the row-softmax layer of fq_loss_rows.h, and that on the row layer of fq_rows.h.
 //
 //   ce_fwd_kernel   one pass over a row with an online logsumexp.  A lane's running state is m, z = max and sum e^(x - m) of the elements
 //                   it has seen, rebased once per 16-byte vector to the vector's maximum (as kd_accumulate), not once per element.  At
@@ -20,8 +20,9 @@
 // checks), so r + 1 < rows wherever it is read.  An IGNORED ROW IS NEVER READ: the forward writes row_loss = 0 (and lse = 0) and returns,
 // the backward stores zeros with the width it stores gradients with, so a NaN or inf there reaches nothing.
 //
-// Launch shape, access paths, the exponentials and the reference point are the shared layer's (fq_loss_rows.h).  A row is valid or ignored
-// as a whole, and a row belongs to one wave (TPR = 64) or one workgroup (TPR = 256): the early return is uniform over whatever meets a barrier.
+// Launch shape and access paths are the row layer's (fq_rows.h), the exponentials and the reference point the softmax layer's
+// (fq_loss_rows.h).  A row is valid or ignored as a whole, and a row belongs to one wave (TPR = 64) or one workgroup (TPR = 256): the early
+// return is uniform over whatever meets a barrier.
 // CE_FWD_VIF / CE_BWD_VIF: 16-byte vectors a lane keeps in flight (A/B macros, as the two cache policies; DESIGN.md section 23 has the
 // measurement).
 //
@@ -112,14 +113,14 @@ template <int N> __device__ __forceinline__ void ce_accumulate(CeState& st, cons
 }
 
 template <int DT, bool VEC, int TPR>
-__global__ __launch_bounds__(LOSS_TPB) void ce_fwd_kernel(CeFwdArgs a) {
+__global__ __launch_bounds__(ROW_TPB) void ce_fwd_kernel(CeFwdArgs a) {
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE, NW = TPR / 64, VIF = CE_FWD_VIF;
     constexpr uint32_t NEG_INF_WORD = DT == F32 ? 0xFF800000u : DT == BF16 ? 0xFF80FF80u : 0xFC00FC00u;   // -inf in every element of a dword
     __shared__ uint32_t lds_max[1][4], lds_sum[1][4];
     int64_t row;
     int lane;
-    if (!loss_row_lane<TPR>(a.lab.rows, row, lane)) return;
+    if (!row_lane<TPR>(a.lab.rows, row, lane)) return;
     int64_t y;
     if (!ce_label(a.lab, row, y)) {     // uniform over the row's lanes: nothing of the row is read
         if (lane == 0) {
@@ -148,22 +149,22 @@ __global__ __launch_bounds__(LOSS_TPB) void ce_fwd_kernel(CeFwdArgs a) {
             for (int i = 0; i < VIF; ++i) {
                 if (i > 0 && v + i * TPR >= nvec) r[i] = make_uint4(NEG_INF_WORD, NEG_INF_WORD, NEG_INF_WORD, NEG_INF_WORD);
                 float f[EPV];
-                loss_unpack<DT>(r[i], f);
+                row_unpack<DT>(r[i], f);
                 ce_accumulate(st, f);
             }
         }
     } else {
         for (int64_t c = lane; c < a.cols; c += LOSS_EG * TPR) {
             float f[LOSS_EG];
-            loss_load_group<DT, TPR>(a.x, base, c, a.cols, f);
+            row_load_group<DT, TPR>(a.x, base, c, a.cols, LOSS_NEG_INF, f);
             ce_accumulate(st, f);
         }
     }
     uint32_t m[1] = {as_u(st.m)};
-    loss_reduce<OpMaxF, NW>(m, lds_max);
+    row_reduce<OpMaxF, NW>(m, lds_max);
     ce_rebase(st, as_f(m[0]));
     uint32_t z[1] = {as_u(st.z)};
-    loss_reduce<OpAddF, NW>(z, lds_sum);
+    row_reduce<OpAddF, NW>(z, lds_sum);
     if (lane == 0) {
         const float lse = loss_ref(st.m) + __builtin_logf(as_f(z[0]));
         if (a.row_lse) a.row_lse[row] = lse;
@@ -213,18 +214,18 @@ template <int N> __device__ __forceinline__ void ce_grad(float (&x)[N], float ls
 template <int DT> __device__ __forceinline__ uint4 ce_grad_vec(const uint4& x, float lse, float gn, uint64_t hot) {
     using T = Ty<DT>;
     float f[16 / T::ESIZE];
-    loss_unpack<DT>(x, f);
+    row_unpack<DT>(x, f);
     ce_grad(f, lse, gn, hot);
-    return loss_pack<DT>(f);
+    return row_pack<DT>(f);
 }
 
 template <int DT, bool VEC, int TPR>
-__global__ __launch_bounds__(LOSS_TPB) void ce_bwd_kernel(CeBwdArgs a) {
+__global__ __launch_bounds__(ROW_TPB) void ce_bwd_kernel(CeBwdArgs a) {
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE, VIF = CE_BWD_VIF;
     int64_t row;
     int lane;
-    if (!loss_row_lane<TPR>(a.lab.rows, row, lane)) return;
+    if (!row_lane<TPR>(a.lab.rows, row, lane)) return;
     const int64_t base = row * a.cols;
     int64_t y;
     if (!ce_label(a.lab, row, y)) {     // zeros, with the width the gradient is stored with; the row's logits are not read
@@ -260,6 +261,8 @@ __global__ __launch_bounds__(LOSS_TPB) void ce_bwd_kernel(CeBwdArgs a) {
     } else {
         for (int64_t c = lane; c < a.cols; c += LOSS_EG * TPR) {
             float f[LOSS_EG];
+            // (not row_load_group: a slot past the row is never stored and holds the repeated element; the fill's select makes the six
+            // VEC = false backwards differ, 32 -> 38 VGPRs)
 #pragma unroll
             for (int i = 0; i < LOSS_EG; ++i) {
                 const int64_t ci = c + i * TPR;

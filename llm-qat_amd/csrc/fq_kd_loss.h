@@ -16,8 +16,9 @@
 //   kd_bwd_kernel   one pass: grad = (g / batch) (e^(s - lse_s) - e^(t - lse_t)), rounded once to the dtype (loss_exp_acc: the product
 //                   with log2(e) carried to twice the precision).
 //
-// Launch shape, access paths, the exponentials and the reference point are the shared layer's (fq_loss_rows.h).  Slots past the end of a
-// row hold -inf in both tensors: e^-inf = 0 adds nothing to a sum, and a term whose e^(t - mt) is 0 is dropped:
+// Launch shape and access paths are the row layer's (fq_rows.h), the exponentials and the reference point the softmax layer's
+// (fq_loss_rows.h).  Slots past the end of a row hold -inf in both tensors: e^-inf = 0 adds nothing to a sum, and a term whose
+// e^(t - mt) is 0 is dropped:
 //
 // Special values of this loss.  A term is dropped where e^(t - mt) == 0 (kl_div's xlogy rule: p_t == 0 contributes 0; here also where s is
 // -inf, the one deviation from ATen, which gives NaN for -inf in both).  s = -inf under e^(t - mt) > 0 gives a = +inf.  A row of only
@@ -88,13 +89,13 @@ template <int N> __device__ __forceinline__ void kd_accumulate(KdState& st, cons
 }
 
 template <int DT, bool VEC, int TPR>
-__global__ __launch_bounds__(LOSS_TPB) void kd_fwd_kernel(KdFwdArgs a) {
+__global__ __launch_bounds__(ROW_TPB) void kd_fwd_kernel(KdFwdArgs a) {
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE, NW = TPR / 64;
     __shared__ uint32_t lds_max[2][4], lds_sum[3][4];
     int64_t row;
     int lane;
-    if (!loss_row_lane<TPR>(a.rows, row, lane)) return;
+    if (!row_lane<TPR>(a.rows, row, lane)) return;
     const int64_t base = row * a.cols;
     KdState st;
     if constexpr (VEC) {
@@ -107,19 +108,19 @@ __global__ __launch_bounds__(LOSS_TPB) void kd_fwd_kernel(KdFwdArgs a) {
             const uint4 s0 = ld16<KD_NT_LOAD != 0>(ps + v), t0 = ld16<KD_NT_LOAD != 0>(pt + v);
             const uint4 s1 = ld16<KD_NT_LOAD != 0>(ps + (more ? v1 : v)), t1 = ld16<KD_NT_LOAD != 0>(pt + (more ? v1 : v));
             float fs[EPV], ft[EPV];
-            loss_unpack<DT>(s0, fs);
-            loss_unpack<DT>(t0, ft);
+            row_unpack<DT>(s0, fs);
+            row_unpack<DT>(t0, ft);
             kd_accumulate(st, fs, ft);
             if (more) {
-                loss_unpack<DT>(s1, fs);
-                loss_unpack<DT>(t1, ft);
+                row_unpack<DT>(s1, fs);
+                row_unpack<DT>(t1, ft);
                 kd_accumulate(st, fs, ft);
             }
         }
     } else {
         for (int64_t c = lane; c < a.cols; c += LOSS_EG * TPR) {
             float fs[LOSS_EG], ft[LOSS_EG];
-            // (loss_load_group written out for two tensors: through the helper, per tensor or per slot, the s and t loads of a slot are
+            // (row_load_group written out for two tensors: through the helper, per tensor or per slot, the s and t loads of a slot are
             // no longer issued together and the six VEC = false instantiations take 39 VGPRs for 37)
 #pragma unroll
             for (int i = 0; i < LOSS_EG; ++i) {
@@ -133,10 +134,10 @@ __global__ __launch_bounds__(LOSS_TPB) void kd_fwd_kernel(KdFwdArgs a) {
         }
     }
     uint32_t m[2] = {as_u(st.ms), as_u(st.mt)};
-    loss_reduce<OpMaxF, NW>(m, lds_max);
+    row_reduce<OpMaxF, NW>(m, lds_max);
     kd_rebase(st, as_f(m[0]), as_f(m[1]));
     uint32_t z[3] = {as_u(st.zs), as_u(st.zt), as_u(st.a)};
-    loss_reduce<OpAddF, NW>(z, lds_sum);
+    row_reduce<OpAddF, NW>(z, lds_sum);
     if (lane == 0) {
         const float zs = as_f(z[0]), zt = as_f(z[1]);
         const float lse_s = loss_ref(st.ms) + __builtin_logf(zs), lse_t = loss_ref(st.mt) + __builtin_logf(zt);
@@ -168,19 +169,19 @@ template <int N> __device__ __forceinline__ void kd_grad(float (&s)[N], const fl
 template <int DT> __device__ __forceinline__ uint4 kd_grad_vec(const uint4& s, const uint4& t, float lse_s, float lse_t, float gb) {
     using T = Ty<DT>;
     float fs[16 / T::ESIZE], ft[16 / T::ESIZE];
-    loss_unpack<DT>(s, fs);
-    loss_unpack<DT>(t, ft);
+    row_unpack<DT>(s, fs);
+    row_unpack<DT>(t, ft);
     kd_grad(fs, ft, lse_s, lse_t, gb);
-    return loss_pack<DT>(fs);
+    return row_pack<DT>(fs);
 }
 
 template <int DT, bool VEC, int TPR>
-__global__ __launch_bounds__(LOSS_TPB) void kd_bwd_kernel(KdBwdArgs a) {
+__global__ __launch_bounds__(ROW_TPB) void kd_bwd_kernel(KdBwdArgs a) {
     using T = Ty<DT>;
     constexpr int EPV = 16 / T::ESIZE;
     int64_t row;
     int lane;
-    if (!loss_row_lane<TPR>(a.rows, row, lane)) return;
+    if (!row_lane<TPR>(a.rows, row, lane)) return;
     const int64_t base = row * a.cols;
     const float lse_s = a.stats[2 * row], lse_t = a.stats[2 * row + 1], gb = a.g[0] / a.batch;
     if constexpr (VEC) {

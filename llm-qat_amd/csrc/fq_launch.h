@@ -59,7 +59,7 @@ template <class F> inline int by_dtype(int dtype, F&& f) {
         default: return f(Const<BF16>{});
     }
 }
-// one launch of a row kernel over `rows` rows: TPR == 64 puts four rows into a 256-thread block (fq_kernels.h row_and_lane)
+// one launch of a row kernel over `rows` rows: TPR == 64 puts four rows into a 256-thread block (fq_kernels.h row_and_lane, fq_rows.h row_lane)
 template <int TPR, typename... P, typename... A> inline void launch_rows(void (*kernel)(P...), int64_t rows, hipStream_t st, A&&... a) {
     launch(kernel, dim3((unsigned)(TPR == 64 ? (rows + 3) / 4 : rows)), dim3(TPR == 64 ? 256 : TPR), st, std::forward<A>(a)...);
 }

@@ -1,9 +1,9 @@
 // fq_rms_norm.h -- the root-mean-square layer norm  y = w * (x * rsqrt(mean(x^2) + eps))  and its gradients: the
 // kernels behind include/llmqat_fakequant_norm.h.  fp32 arithmetic whatever the dtypes, in the reference's op order with its roundings
-// (models/modeling_llama_quant.py:112-129); no fp32 [rows, cols] tensor ever exists.  It stands on the row layer of fq_loss_rows.h: the
+// (models/modeling_llama_quant.py:112-129); no fp32 [rows, cols] tensor ever exists.  It stands on the row layer of fq_rows.h: the
 // launch shape, unpack / pack, the one-barrier reduction over a row's waves.
 //
-//   rms_fwd_kernel   one row per workgroup (rows of LOSS_WIDE elements or more) or per wave.  A lane reads one SWEEP of the row into
+//   rms_fwd_kernel   one row per workgroup (rows of ROW_WIDE elements or more) or per wave.  A lane reads one SWEEP of the row into
 //                    registers (RmsIO: NS slots), sums the squares in slot order, the lanes' sums are added (DPP butterfly, then the waves
 //                    through LDS in wave order: a fixed order), rstd = v_rsq_f32(ss / cols + eps), and the sweep is scaled from the
 //                    registers: a row of up to SWEEP elements (8192 on the 16-byte path of a workgroup, 4096 on the element path) is read
@@ -26,7 +26,7 @@
 // RMS_NT_LOAD / RMS_NT_STORE / RMS_VIF: cache policies of the 16-byte streams and 16-byte vectors of a 16-bit tensor a lane holds per sweep
 // (an fp32 tensor: twice as many), A/B macros as CE_* are.
 #pragma once
-#include "fq_loss_rows.h"
+#include "fq_rows.h"
 
 #ifndef RMS_NT_LOAD
 #define RMS_NT_LOAD 0     // x was written by the kernel just before, and the backward reads it again
@@ -38,7 +38,7 @@
 #define RMS_VIF 4         // 4 * 8 * 256 = 8192 elements of a workgroup's row in registers
 #endif
 #ifndef RMS_BWD_PARTS_WIDE
-#define RMS_BWD_PARTS_WIDE 512      // workgroups of the backward at most (rows of LOSS_WIDE elements or more)
+#define RMS_BWD_PARTS_WIDE 512      // workgroups of the backward at most (rows of ROW_WIDE elements or more)
 #endif
 #ifndef RMS_BWD_PARTS_NARROW
 #define RMS_BWD_PARTS_NARROW 2048   // waves of the backward at most (shorter rows)
@@ -99,12 +99,14 @@ template <int DT, bool VEC, int TPR, int NGV> struct RmsIO {
 #pragma unroll
             for (int i = 0; i < NG; ++i) {
                 float e[EPV];
-                loss_unpack<DT>(r[i], e);
+                row_unpack<DT>(r[i], e);
                 const bool in = (int64_t)i * TPR + lane < nvec;
 #pragma unroll
                 for (int k = 0; k < EPV; ++k) f[i * EPV + k] = in ? e[k] : 0.0f;
             }
         } else {
+            // (not row_load_group: a lane's first column, which that clamps to, may lie past the row here, where every lane of the row
+            // loads; with a clamp that tests for it the element-path kernels differ, v_cndmask_b32 220 -> 252 in the backwards)
 #pragma unroll
             for (int i = 0; i < NG; ++i) {
                 const int64_t c = c0 + (int64_t)i * TPR + lane;
@@ -125,7 +127,7 @@ template <int DT, bool VEC, int TPR, int NGV> struct RmsIO {
                 float e[EPV];
 #pragma unroll
                 for (int k = 0; k < EPV; ++k) e[k] = f[i * EPV + k];
-                if (vi < nvec) st16<NT>(pv + vi, loss_pack<DT>(e));
+                if (vi < nvec) st16<NT>(pv + vi, row_pack<DT>(e));
             }
         } else {
 #pragma unroll
@@ -190,7 +192,7 @@ template <int WDT, int N> __device__ __forceinline__ void rms_scale(float (&x)[N
 }
 
 template <int XDT, int WDT, bool VEC, int TPR, int NGV>
-__global__ __launch_bounds__(LOSS_TPB) void rms_fwd_kernel(RmsFwdArgs a) {
+__global__ __launch_bounds__(ROW_TPB) void rms_fwd_kernel(RmsFwdArgs a) {
     using IX = RmsIO<XDT, VEC, TPR, NGV>;
     using IW = RmsIO<WDT, VEC, TPR, NGV>;
     constexpr int NS = IX::NS, NW = TPR / 64;
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(LOSS_TPB) void rms_fwd_kernel(RmsFwdArgs a) {
     __shared__ uint32_t lds[1][4];
     int64_t row;
     int lane;
-    if (!loss_row_lane<TPR>(a.rows, row, lane)) return;
+    if (!row_lane<TPR>(a.rows, row, lane)) return;
     const int64_t base = row * a.cols;
     float f[NS];
     IX::template load<RMS_NT_LOAD != 0>(a.x, base, 0, a.cols, lane, f);
@@ -212,9 +214,11 @@ __global__ __launch_bounds__(LOSS_TPB) void rms_fwd_kernel(RmsFwdArgs a) {
         for (int i = 0; i < NS; ++i) ss += t[i] * t[i];
     }
     uint32_t v[1] = {as_u(ss)};
-    loss_reduce<OpAddF, NW>(v, lds);
+    row_reduce<OpAddF, NW>(v, lds);
     const float rstd = __builtin_amdgcn_rsqf(as_f(v[0]) / (float)a.cols + a.eps);
     if (lane == 0 && a.rstd) a.rstd[row] = rstd;
+    // (load w, scale, store: written out twice.  As one helper 15 kernels are reordered and 5 differ, the bf16 16-byte forwards of one
+    // vector by 37 -> 41 VGPRs)
     if (a.cols <= IX::SWEEP) {              // the row is in registers
         float w[NS];
         IW::template load<false>(a.w, 0, 0, a.cols, lane, w);
@@ -231,8 +235,16 @@ __global__ __launch_bounds__(LOSS_TPB) void rms_fwd_kernel(RmsFwdArgs a) {
     }
 }
 
-// one sweep of one row of the backward: x -> n = x rstd, g -> a = g w, gn = g n (n is not rounded); -> the lane's part of sum(a n)
-template <int N> __device__ __forceinline__ float rms_bwd_terms(float (&x)[N], float (&g)[N], float (&gn)[N], const float (&w)[N], float rstd) {
+// the sweep that starts at column c0 of one row of the backward: x and g are loaded, and w with LOADW (else it is the caller's, loaded once
+// for all rows); x -> n = x rstd, g -> a = g w, gn = g n (n is not rounded); -> the lane's part of sum(a n).  (The tensors come as pointers:
+// with the RmsBwdArgs by reference four element-path kernels lose a v_mov_b32 and ten more are reordered.  As it stands the 18 kernels
+// of the 16-byte path are reordered, two base addresses trading registers, and the rest identical: DESIGN.md section 26)
+template <class IX, class IW, bool LOADW, int N>
+__device__ __forceinline__ float rms_bwd_sweep(const void* pg, const void* px, const void* pw, int64_t cols, int64_t base, int64_t c0, int lane,
+                                               float rstd, float (&x)[N], float (&g)[N], float (&gn)[N], float (&w)[N]) {
+    IX::template load<RMS_NT_LOAD != 0>(px, base, c0, cols, lane, x);
+    IW::template load<RMS_NT_LOAD != 0>(pg, base, c0, cols, lane, g);
+    if constexpr (LOADW) IW::template load<false>(pw, 0, c0, cols, lane, w);
     float p = 0.0f;
 #pragma unroll
     for (int i = 0; i < N; ++i) {
@@ -254,7 +266,7 @@ template <int XDT, int N> __device__ __forceinline__ void rms_dx(float (&a)[N], 
 }
 
 template <int XDT, int WDT, bool VEC, int TPR, int NGV>
-__global__ __launch_bounds__(LOSS_TPB) void rms_bwd_kernel(RmsBwdArgs a) {
+__global__ __launch_bounds__(ROW_TPB) void rms_bwd_kernel(RmsBwdArgs a) {
     using IX = RmsIO<XDT, VEC, TPR, NGV>;
     using IW = RmsIO<WDT, VEC, TPR, NGV>;
     constexpr int NS = IX::NS, NW = TPR / 64;
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(LOSS_TPB) void rms_bwd_kernel(RmsBwdArgs a) {
     __shared__ uint32_t lds[2][1][4];       // two, used in turn: a row's sums are read while the next row's are written
     int64_t part;
     int lane;
-    if (!loss_row_lane<TPR>(a.parts, part, lane)) return;
+    if (!row_lane<TPR>(a.parts, part, lane)) return;
     const int64_t r0 = part * a.rpp, r1 = r0 + a.rpp < a.rows ? r0 + a.rpp : a.rows;
     const int64_t wsb = part * a.cols;
     int par = 0;
@@ -275,10 +287,8 @@ __global__ __launch_bounds__(LOSS_TPB) void rms_bwd_kernel(RmsBwdArgs a) {
             const int64_t base = row * a.cols;
             const float rstd = a.rstd[row];
             float x[NS], g[NS], gn[NS];
-            IX::template load<RMS_NT_LOAD != 0>(a.x, base, 0, a.cols, lane, x);
-            IW::template load<RMS_NT_LOAD != 0>(a.g, base, 0, a.cols, lane, g);
-            uint32_t v[1] = {as_u(rms_bwd_terms(x, g, gn, w, rstd))};
-            loss_reduce<OpAddF, NW>(v, lds[par]);
+            uint32_t v[1] = {as_u(rms_bwd_sweep<IX, IW, false>(a.g, a.x, a.w, a.cols, base, 0, lane, rstd, x, g, gn, w))};
+            row_reduce<OpAddF, NW>(v, lds[par]);
             if (a.ws) {
 #pragma unroll
                 for (int i = 0; i < NS; ++i) acc[i] += gn[i];
@@ -296,20 +306,14 @@ __global__ __launch_bounds__(LOSS_TPB) void rms_bwd_kernel(RmsBwdArgs a) {
             float p = 0.0f;
             for (int64_t c0 = 0; c0 < a.cols; c0 += IX::SWEEP) {
                 float x[NS], g[NS], gn[NS], w[NS];
-                IX::template load<RMS_NT_LOAD != 0>(a.x, base, c0, a.cols, lane, x);
-                IW::template load<RMS_NT_LOAD != 0>(a.g, base, c0, a.cols, lane, g);
-                IW::template load<false>(a.w, 0, c0, a.cols, lane, w);
-                p += rms_bwd_terms(x, g, gn, w, rstd);
+                p += rms_bwd_sweep<IX, IW, true>(a.g, a.x, a.w, a.cols, base, c0, lane, rstd, x, g, gn, w);
             }
             uint32_t v[1] = {as_u(p)};
-            loss_reduce<OpAddF, NW>(v, lds[par]);
+            row_reduce<OpAddF, NW>(v, lds[par]);
             const float s = as_f(v[0]) / (float)a.cols;
             for (int64_t c0 = 0; c0 < a.cols; c0 += IX::SWEEP) {
                 float x[NS], g[NS], gn[NS], w[NS];
-                IX::template load<RMS_NT_LOAD != 0>(a.x, base, c0, a.cols, lane, x);
-                IW::template load<RMS_NT_LOAD != 0>(a.g, base, c0, a.cols, lane, g);
-                IW::template load<false>(a.w, 0, c0, a.cols, lane, w);
-                rms_bwd_terms(x, g, gn, w, rstd);
+                rms_bwd_sweep<IX, IW, true>(a.g, a.x, a.w, a.cols, base, c0, lane, rstd, x, g, gn, w);
                 if (a.ws) {
                     if (row > r0) {         // the part's own row of the workspace: the lane that wrote a column is the one that reads it
                         float acc[NS];
@@ -352,7 +356,7 @@ __global__ __launch_bounds__(RMS_DW_TPB) void rms_dw_kernel(const float* ws, voi
 
 // ---- host part: the chunks of the backward, a function of the shape alone ---------------------------------------------------------------
 inline int64_t rms_rows_per_part(int64_t rows, int64_t cols) {
-    const int64_t most = loss_wide(cols) ? RMS_BWD_PARTS_WIDE : RMS_BWD_PARTS_NARROW;
+    const int64_t most = row_wide(cols) ? RMS_BWD_PARTS_WIDE : RMS_BWD_PARTS_NARROW;
     return (rows + most - 1) / most;
 }
 inline int64_t rms_parts(int64_t rows, int64_t cols) {

@@ -1435,14 +1435,26 @@ def mx_matmul(a, w, out_dtype=None):
     return mx_matmul_tensors(a.elements, a.scales, a.fmt, w.elements, w.scales.reshape(w.shape[0], -1), w.fmt, a.shape, out_dtype)
 
 
-# ---- what the fused losses share.  The four argument checks stand one by one, because each loss puts checks of
-# its own between them and the order of its refusals is pinned: one message each, whatever the order ---------------------------------------
-def _loss_tensors(what, **named):
+# ---- what the row operations share, the fused losses and the norm (DESIGN.md sections 24 and 26) ------------------------------------------
+def _row_tensors(what, **named):
     for name, t in named.items():
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t).__name__}")
 
 
+def _row_contig(t, counts):   # the copy route: a non-contiguous tensor is copied once, and counted
+    if not t.is_contiguous():
+        counts["copy_route"] += 1
+    return t.contiguous()
+
+
+def _row_stats(what, t, name, shape, like):   # the forward's row statistics (name: "<argument> is <forward>'s") as the backward wants them
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape and t.device == like.device and t.is_contiguous()):
+        raise ValueError(f"{what}: {name} contiguous fp32 {list(shape)} tensor on {like.device}")
+
+
+# ---- what only the fused losses share.  The argument checks stand one by one, because each loss puts checks of its own between them and
+# the order of its refusals is pinned: one message each, whatever the order -------------------------------------------------------------
 def _loss_dtype(what, logits):
     if logits.dtype not in _OUT_DTYPES:
         raise TypeError(f"{what}: dtype {logits.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
@@ -1456,17 +1468,6 @@ def _loss_dims(what, logits, layout):
 def _loss_not_empty(what, logits):
     if logits.numel() == 0:
         raise ValueError(f"{what}: empty logits {tuple(logits.shape)}: a loss has no empty launch")
-
-
-def _loss_contig(t, counts):   # the copy route: a non-contiguous tensor is copied once, and counted
-    if not t.is_contiguous():
-        counts["copy_route"] += 1
-    return t.contiguous()
-
-
-def _loss_stats(what, t, name, shape, logits):   # the forward's row statistics (name: "<argument> is <forward>'s") as the backward wants them
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape and t.device == logits.device and t.is_contiguous()):
-        raise ValueError(f"{what}: {name} contiguous fp32 {list(shape)} tensor on {logits.device}")
 
 
 def _loss_grad(what, grad_loss, logits):   # the upstream gradient as the kernel reads it on the device: detached, fp32, [1]
@@ -1484,7 +1485,7 @@ def check_kd(student, teacher, what="kd_kl_loss"):
     """The argument checks of the loss on types, shapes and dtypes alone (the fake implementations of the compiled ops run them too) ->
     (rows, cols, batch): TypeError for a non-tensor, mixed dtypes or a dtype that is not served (float64 among them), ValueError for
     unequal shapes, fewer than two dimensions, an empty shape, or a teacher that requires grad while grad mode is on."""
-    _loss_tensors(what, student_logits=student, teacher_logits=teacher)
+    _row_tensors(what, student_logits=student, teacher_logits=teacher)
     if student.dtype != teacher.dtype:
         raise TypeError(f"{what}: mixed dtypes are not served: student_logits is {student.dtype}, teacher_logits is {teacher.dtype}")
     _loss_dtype(what, student)
@@ -1506,7 +1507,7 @@ def kd_inputs(student, teacher, what="kd_kl_loss"):
     _prep(teacher, what)
     if student.device != teacher.device:
         raise ValueError(f"{what}: student_logits is on {student.device}, teacher_logits on {teacher.device}")
-    return _loss_contig(student, kd_counts), _loss_contig(teacher, kd_counts), rows, cols, batch
+    return _row_contig(student, kd_counts), _row_contig(teacher, kd_counts), rows, cols, batch
 
 
 def kd_kl_forward(student, teacher, need_stats=True):
@@ -1530,7 +1531,7 @@ def kd_kl_backward(student, teacher, row_stats, grad_loss):
     reads on the device (no host synchronisation).  One launch (bwd_launch)."""
     with torch.no_grad():
         student, teacher, rows, cols, batch = kd_inputs(student, teacher, "kd_kl_backward")
-    _loss_stats("kd_kl_backward", row_stats, "row_stats is kd_kl_forward's", (rows, 2), student)
+    _row_stats("kd_kl_backward", row_stats, "row_stats is kd_kl_forward's", (rows, 2), student)
     g = _loss_grad("kd_kl_backward", grad_loss, student)
     grad = torch.empty_like(student)
     rc = _launch(student, _lib.lib().fql_kd_kl_bwd, student.data_ptr(), teacher.data_ptr(), row_stats.data_ptr(), g.data_ptr(), grad.data_ptr(),
@@ -1552,7 +1553,7 @@ def check_ce(logits, labels, shift=False, ignore_index=-100, reduction="mean", w
     (rows, cols, seq_len): TypeError for a non-tensor, a logits dtype that is not served (float64 among them), labels that are not int64
     (probability targets among them) or an ignore_index that is no int; ValueError for fewer than two dimensions, labels that are not of
     the logits' shape without its last dimension, an empty shape, or a reduction other than 'mean' and 'sum'."""
-    _loss_tensors(what, logits=logits, labels=labels)
+    _row_tensors(what, logits=logits, labels=labels)
     _loss_dtype(what, logits)
     if labels.dtype != torch.int64:
         raise TypeError(f"{what}: labels of dtype {labels.dtype} are not served: {_CE_SERVED}")
@@ -1575,7 +1576,7 @@ def ce_inputs(logits, labels, shift=False, ignore_index=-100, reduction="mean", 
     _prep(logits, what)
     if labels.device != logits.device:
         raise ValueError(f"{what}: logits are on {logits.device}, labels on {labels.device}")
-    return _loss_contig(logits, ce_counts), _loss_contig(labels, ce_counts), rows, cols, seq_len
+    return _row_contig(logits, ce_counts), _row_contig(labels, ce_counts), rows, cols, seq_len
 
 
 def ce_forward(logits, labels, shift=False, ignore_index=-100, reduction="mean", need_stats=True):
@@ -1604,7 +1605,7 @@ def ce_backward(logits, labels, row_lse, n_valid, grad_loss, shift=False, ignore
     n_valid (no host synchronisation).  One launch (bwd_launch)."""
     with torch.no_grad():
         logits, labels, rows, cols, seq_len = ce_inputs(logits, labels, shift, ignore_index, reduction, "ce_backward")
-    _loss_stats("ce_backward", row_lse, "row_lse is ce_forward's", (rows,), logits)
+    _row_stats("ce_backward", row_lse, "row_lse is ce_forward's", (rows,), logits)
     if not (isinstance(n_valid, torch.Tensor) and n_valid.dtype == torch.int64 and n_valid.numel() == 1 and n_valid.device == logits.device):
         raise ValueError(f"ce_backward: n_valid is ce_forward's one-element int64 tensor on {logits.device}")
     g = _loss_grad("ce_backward", grad_loss, logits)
@@ -1626,7 +1627,7 @@ def check_rms_norm(x, w, eps=1e-6, what="rms_norm"):
     (rows, cols): TypeError for a non-tensor, a dtype or a dtype pair that is not served (float64 and bfloat16 with float16 among them) or
     an eps that is no number; ValueError for an eps that is negative, NaN or inf, a weight that is not 1-D, an x whose last dimension is
     not the weight's length, or an empty shape."""
-    _loss_tensors(what, x=x, weight=w)
+    _row_tensors(what, x=x, weight=w)
     for name, t in (("x", x), ("weight", w)):
         if t.dtype not in _OUT_DTYPES:
             raise TypeError(f"{what}: {name} of dtype {t.dtype} is not served: {_NORM_SERVED}; the arithmetic is fp32 for all of them")
@@ -1653,7 +1654,7 @@ def rms_norm_inputs(x, w, eps=1e-6, what="rms_norm"):
     _prep(w, what)
     if x.device != w.device:
         raise ValueError(f"{what}: x is on {x.device}, weight on {w.device}")
-    return _loss_contig(x, norm_counts), _loss_contig(w, norm_counts), rows, cols
+    return _row_contig(x, norm_counts), _row_contig(w, norm_counts), rows, cols
 
 
 def rms_norm_forward(x, w, eps=1e-6, need_stats=True):
@@ -1679,11 +1680,11 @@ def rms_norm_backward(g, x, w, rstd, need_dx=True, need_dw=True):
         x, w, rows, cols = rms_norm_inputs(x, w, 0.0, "rms_norm_backward")
     if not (need_dx or need_dw):
         raise ValueError("rms_norm_backward: neither dx nor dw is asked for")
-    _loss_tensors("rms_norm_backward", g=g)
+    _row_tensors("rms_norm_backward", g=g)
     if g.dtype != w.dtype or tuple(g.shape) != tuple(x.shape) or g.device != x.device:
         raise ValueError(f"rms_norm_backward: g is the gradient of y: {tuple(x.shape)} of {w.dtype} on {x.device}, got {tuple(g.shape)} of {g.dtype} on {g.device}")
-    _loss_stats("rms_norm_backward", rstd, "rstd is rms_norm_forward's", (rows,), x)
-    g = _loss_contig(g.detach(), norm_counts)
+    _row_stats("rms_norm_backward", rstd, "rstd is rms_norm_forward's", (rows,), x)
+    g = _row_contig(g.detach(), norm_counts)
     L = _lib.lib()
     dx = torch.empty_like(x) if need_dx else None
     dw = torch.empty_like(w) if need_dw else None

@@ -55,7 +55,7 @@ def test_loss_header_names_equal_loss_exports_and_the_library_has_them():
 
 def test_the_build_lists_the_new_unit_and_headers():
     src = open(os.path.join(ROOT, "llm-qat_amd", "build.py")).read()
-    for name in ("fq_kd_loss.hip", "fq_kd_loss.h", "fq_loss_rows.h", "llmqat_fakequant_loss.h"):
+    for name in ("fq_kd_loss.hip", "fq_kd_loss.h", "fq_loss_rows.h", "fq_rows.h", "llmqat_fakequant_loss.h"):
         assert f'"{name}"' in src, name
 
 

@@ -70,7 +70,7 @@ def test_norm_header_names_equal_norm_exports_and_the_library_has_them():
 
 def test_the_build_lists_the_new_unit_and_header():
     src = open(os.path.join(ROOT, "llm-qat_amd", "build.py")).read()
-    for name in ("fq_rms_norm.hip", "fq_rms_norm.h", "fq_loss_rows.h", "llmqat_fakequant_norm.h"):
+    for name in ("fq_rms_norm.hip", "fq_rms_norm.h", "fq_rows.h", "llmqat_fakequant_norm.h"):
         assert f'"{name}"' in src, name
 
 
