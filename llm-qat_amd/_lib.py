@@ -43,6 +43,8 @@ CE_EXPORTS = ("fqc_ce_fwd", "fqc_ce_bwd")
 CE_MEAN, CE_SUM = 0, 1   # FQC_REDUCTION_*
 # every symbol include/llmqat_fakequant_norm.h declares (the fqn_ family: the RMSNorm in front of the quantized projections)
 NORM_EXPORTS = ("fqn_rms_norm_fwd", "fqn_rms_norm_bwd", "fqn_rms_norm_bwd_parts", "fqn_rms_norm_bwd_workspace_bytes")
+# every symbol include/llmqat_fakequant_act.h declares (the fqa_ family: the gated activation of the MLP)
+ACT_EXPORTS = ("fqa_swiglu_fwd", "fqa_swiglu_bwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -191,6 +193,10 @@ def _bind(L):
     L.fqn_rms_norm_bwd_parts.restype = i64
     L.fqn_rms_norm_bwd_workspace_bytes.argtypes = [i64, i64]
     L.fqn_rms_norm_bwd_workspace_bytes.restype = sz
+    L.fqa_swiglu_fwd.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, vp]
+    L.fqa_swiglu_fwd.restype = i32
+    L.fqa_swiglu_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, vp]
+    L.fqa_swiglu_bwd.restype = i32
     return L
 
 

@@ -394,3 +394,48 @@ def rms_norm(x, weight, eps):
     requires_grad are known while tracing)"""
     need = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)
     return rms_norm_fwd_op(x, weight, float(eps), need)[0]
+
+
+# ---- the gated activation (ops.swiglu_forward / ops.swiglu_backward, DESIGN.md section 27): y and (dgate, dup) ----------------------------------
+@torch.library.custom_op("llmqat_amd::swiglu_fwd", mutates_args=(), device_types="cuda")
+def swiglu_fwd_op(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
+    return ops.swiglu_forward(gate, up)
+
+
+@swiglu_fwd_op.register_fake
+def _(gate, up):
+    ops.check_swiglu(gate, up)
+    return gate.new_empty(gate.shape)
+
+
+@torch.library.custom_op("llmqat_amd::swiglu_bwd", mutates_args=(), device_types="cuda")
+def swiglu_bwd_op(dy: torch.Tensor, gate: torch.Tensor, up: torch.Tensor, need_dgate: bool, need_dup: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    dgate, dup = ops.swiglu_backward(dy, gate, up, need_dgate, need_dup)
+    return (dgate if need_dgate else gate.new_empty(0)), (dup if need_dup else gate.new_empty(0))      # an op returns tensors: an empty one for "not asked for"
+
+
+@swiglu_bwd_op.register_fake
+def _(dy, gate, up, need_dgate, need_dup):
+    ops.check_swiglu(gate, up)
+    return (gate.new_empty(gate.shape) if need_dgate else gate.new_empty(0)), (gate.new_empty(gate.shape) if need_dup else gate.new_empty(0))
+
+
+def _swiglu_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+
+
+def _swiglu_backward(ctx, grad_y):
+    gate, up = ctx.saved_tensors
+    need_dgate, need_dup = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if not (need_dgate or need_dup):
+        return None, None
+    dgate, dup = swiglu_bwd_op(grad_y, gate, up, need_dgate, need_dup)
+    return (dgate if need_dgate else None), (dup if need_dup else None)
+
+
+swiglu_fwd_op.register_autograd(_swiglu_backward, setup_context=_swiglu_setup)
+
+
+def swiglu(gate, up):
+    """mlp.swiglu while compiling"""
+    return swiglu_fwd_op(gate, up)

@@ -73,3 +73,8 @@ def rms_norm(x, w, eps):
     if w.dtype in (torch.float16, torch.bfloat16):
         x = x.to(w.dtype)
     return w * x
+
+
+def swiglu(gate, up):
+    """the middle of LlamaMLP.forward (models/modeling_llama_quant.py:235) with act_fn = SiLU, differentiated by autograd as the reference's is"""
+    return torch.nn.functional.silu(gate) * up

@@ -1696,3 +1696,122 @@ def rms_norm_backward(g, x, w, rstd, need_dx=True, need_dw=True):
     _lib.check(rc, "rms_norm_backward")
     norm_counts["bwd_launch"] += 1
     return dx, dw
+
+
+# ---- the gated activation  silu(gate) * up  of the MLP (the fqa_ header) --------------------------------------------------
+class _ActCounts:
+    """fwd_launch / bwd_launch / copy_route as a mapping: what this module counted plus what the C++ node of mlp.swiglu counted (its
+    backward runs on the autograd engine's thread without the GIL and cannot touch a dict)"""
+    _KEYS = ("fwd_launch", "bwd_launch", "copy_route")
+
+    def __init__(self):
+        self._own = dict.fromkeys(self._KEYS, 0)
+
+    def __getitem__(self, key):
+        from . import _act_node
+        return self._own[key] + _act_node.counters()[self._KEYS.index(key)]
+
+    def __setitem__(self, key, value):       # counts[key] += 1: the node's share stays the node's
+        from . import _act_node
+        self._own[key] = value - _act_node.counters()[self._KEYS.index(key)]
+
+    def keys(self):
+        return self._KEYS
+
+    def __iter__(self):
+        return iter(self._KEYS)
+
+    def __len__(self):
+        return len(self._KEYS)
+
+    def __eq__(self, other):
+        return dict(self) == dict(other)
+
+    def __repr__(self):
+        return repr(dict(self))
+
+
+act_counts = _ActCounts()
+
+
+def check_swiglu(gate, up, what="swiglu"):
+    """The argument checks of the activation on types, shapes and dtypes alone (the fake implementations of the compiled ops run them
+    too) -> (rows, cols), (0, 0) for an empty shape: TypeError for a non-tensor, a dtype that is not served (float64 and the integer
+    dtypes among them) or unequal dtypes (no promotion); ValueError for unequal shapes (no broadcasting), a 0-dim tensor, or tensors on
+    different devices."""
+    if (type(gate) is torch.Tensor and type(up) is torch.Tensor and gate.dtype is up.dtype and gate.dtype in _OUT_DTYPES and gate.shape == up.shape
+            and gate.dim() >= 1 and gate.device == up.device and gate.numel()):       # the call that is served, in one line; else: which refusal
+        return gate.numel() // gate.shape[-1], gate.shape[-1]
+    _row_tensors(what, gate=gate, up=up)
+    for name, t in (("gate", gate), ("up", up)):
+        if t.dtype not in _OUT_DTYPES:
+            raise TypeError(f"{what}: {name} of dtype {t.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+    if gate.dtype != up.dtype:
+        raise TypeError(f"{what}: mixed dtypes are not served (no promotion): gate is {gate.dtype}, up is {up.dtype}")
+    if tuple(gate.shape) != tuple(up.shape):
+        raise ValueError(f"{what}: shape mismatch (no broadcasting): gate {tuple(gate.shape)}, up {tuple(up.shape)}")
+    if gate.dim() < 1:
+        raise ValueError(f"{what}: the tensors need at least one dimension, got a 0-dim tensor")
+    if gate.device != up.device:
+        raise ValueError(f"{what}: gate is on {gate.device}, up on {up.device}")
+    if gate.numel() == 0:
+        return 0, 0
+    return gate.numel() // gate.shape[-1], gate.shape[-1]
+
+
+def _act_rows(t):
+    """-> (t or its one copy, row stride in elements): a tensor is served where it lies when its last stride is 1 and its leading
+    dimensions collapse to one row stride of at least a row (rows_view); anything else is copied once and counted (copy_route)"""
+    cols = t.shape[-1]
+    v = rows_view(t)
+    if v is None:
+        return t, cols
+    if v and (t.dim() == 2 or v[1] == v[0] * v[2]) and v[2] >= cols:
+        return t, v[2]
+    act_counts["copy_route"] += 1
+    return t.contiguous(), cols
+
+
+def swiglu_launch_forward(gate, up, rows, cols):
+    """swiglu_forward behind check_swiglu's (rows, cols), for a caller that has run the checks (mlp.swiglu: every microsecond of host time
+    before the launch is added to the kernel's, which is shorter than the eager chain's two by some twenty of them) -> (y, gate, up), the
+    inputs as the launch read them: each the tensor itself where it is served where it lies, else its one contiguous copy"""
+    _prep(gate, "swiglu_forward")
+    y = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
+    if rows == 0:
+        return y, gate, up
+    (g, sg), (u, su) = _act_rows(gate), _act_rows(up)
+    rc = _launch(g, _lib.lib().fqa_swiglu_fwd, g.data_ptr(), u.data_ptr(), y.data_ptr(), rows, cols, sg, su, _OUT_DTYPES[g.dtype])
+    _lib.check(rc, "swiglu_forward")
+    act_counts["fwd_launch"] += 1
+    return y, g, u
+
+
+def swiglu_forward(gate, up):
+    """-> y = silu(gate) * up, contiguous, of gate's shape and dtype: fp32 arithmetic with the roundings of the eager chain
+    F.silu(gate) * up, whose bits it gives.  Row views (the halves of gate_up.chunk(2, -1)) are read where they lie.  One launch on the
+    current stream (fwd_launch); an empty tensor gives an empty result without one."""
+    return swiglu_launch_forward(gate, up, *check_swiglu(gate, up, "swiglu_forward"))[0]
+
+
+def swiglu_backward(dy, gate, up, need_dgate=True, need_dup=True, checked=None):
+    """-> (dgate, dup), contiguous, of gate's shape and dtype, the bits of the eager chain's autograd; None for the one that is not needed
+    (neither computed nor stored).  dy: the gradient of swiglu_forward's y (its shape, dtype and device).  One launch (bwd_launch); an
+    empty tensor gives empty results without one.  checked: check_swiglu's (rows, cols) of a caller that has run it on gate and up."""
+    rows, cols = checked or check_swiglu(gate, up, "swiglu_backward")
+    if not (need_dgate or need_dup):
+        raise ValueError("swiglu_backward: neither dgate nor dup is asked for")
+    _row_tensors("swiglu_backward", dy=dy)
+    if dy.dtype != gate.dtype or dy.shape != gate.shape or dy.device != gate.device:
+        raise ValueError(f"swiglu_backward: dy is the gradient of y: {tuple(gate.shape)} of {gate.dtype} on {gate.device}, got {tuple(dy.shape)} of {dy.dtype} on {dy.device}")
+    _prep(gate, "swiglu_backward")
+    dgate = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device) if need_dgate else None
+    dup = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device) if need_dup else None
+    if rows == 0:
+        return dgate, dup
+    (d, sd), (g, sg), (u, su) = _act_rows(dy), _act_rows(gate), _act_rows(up)
+    rc = _launch(g, _lib.lib().fqa_swiglu_bwd, d.data_ptr(), g.data_ptr(), u.data_ptr(), dgate.data_ptr() if need_dgate else None,
+                 dup.data_ptr() if need_dup else None, rows, cols, sd, sg, su, _OUT_DTYPES[g.dtype])
+    _lib.check(rc, "swiglu_backward")
+    act_counts["bwd_launch"] += 1
+    return dgate, dup
