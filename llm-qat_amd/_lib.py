@@ -45,6 +45,8 @@ CE_MEAN, CE_SUM = 0, 1   # FQC_REDUCTION_*
 NORM_EXPORTS = ("fqn_rms_norm_fwd", "fqn_rms_norm_bwd", "fqn_rms_norm_bwd_parts", "fqn_rms_norm_bwd_workspace_bytes")
 # every symbol include/llmqat_fakequant_act.h declares (the fqa_ family: the gated activation of the MLP)
 ACT_EXPORTS = ("fqa_swiglu_fwd", "fqa_swiglu_bwd")
+# every symbol include/llmqat_fakequant_rope.h declares (the fqr_ family: the rotary position embedding of q and k)
+ROPE_EXPORTS = ("fqr_rope_dense_strides", "fqr_rope_fwd", "fqr_rope_bwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -197,6 +199,12 @@ def _bind(L):
     L.fqa_swiglu_fwd.restype = i32
     L.fqa_swiglu_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, vp]
     L.fqa_swiglu_bwd.restype = i32
+    L.fqr_rope_dense_strides.argtypes = [i64] * 7 + [ctypes.POINTER(i64)]
+    L.fqr_rope_dense_strides.restype = i32
+    L.fqr_rope_fwd.argtypes = [vp] * 7 + [i64] * 13 + [i32, i32, i32, vp]
+    L.fqr_rope_fwd.restype = i32
+    L.fqr_rope_bwd.argtypes = [vp] * 7 + [i64] * 19 + [i32, i32, i32, vp]
+    L.fqr_rope_bwd.restype = i32
     return L
 
 

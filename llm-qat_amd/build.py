@@ -13,9 +13,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libllmqat_fakequant.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("fq_api.hip", "fq_bf16.hip", "fq_f32.hip", "fq_f16.hip", "fq_export.hip", "fq_f64.hip", "fq_group.hip", "fq_mx.hip", "fq_mx_gemm.hip", "fq_mx_cols.hip", "fq_mx_sr.hip", "fq_mx_dequant.hip", "fq_kd_loss.hip", "fq_ce_loss.hip", "fq_rms_norm.hip", "fq_swiglu.hip")]
-DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("fq_kernels.h", "fq_device.h", "fq_launch.h", "fq_shapes.h", "fq_dtype_impl.h", "fq_export.h", "fq_group.h", "fq_mx.h", "fq_mx_gemm.h", "fq_mx_cols.h", "fq_mx_sr.h", "fq_mx_dequant.h", "fq_rows.h", "fq_loss_rows.h", "fq_kd_loss.h", "fq_ce_loss.h", "fq_rms_norm.h", "fq_swiglu.h")] + [
-    os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_train.h", "llmqat_fakequant_sr.h", "llmqat_fakequant_infer.h", "llmqat_fakequant_loss.h", "llmqat_fakequant_ce.h", "llmqat_fakequant_norm.h", "llmqat_fakequant_act.h")]
+SOURCES = [os.path.join(CSRC, f) for f in ("fq_api.hip", "fq_bf16.hip", "fq_f32.hip", "fq_f16.hip", "fq_export.hip", "fq_f64.hip", "fq_group.hip", "fq_mx.hip", "fq_mx_gemm.hip", "fq_mx_cols.hip", "fq_mx_sr.hip", "fq_mx_dequant.hip", "fq_kd_loss.hip", "fq_ce_loss.hip", "fq_rms_norm.hip", "fq_swiglu.hip", "fq_rope.hip")]
+DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("fq_kernels.h", "fq_device.h", "fq_launch.h", "fq_shapes.h", "fq_dtype_impl.h", "fq_export.h", "fq_group.h", "fq_mx.h", "fq_mx_gemm.h", "fq_mx_cols.h", "fq_mx_sr.h", "fq_mx_dequant.h", "fq_rows.h", "fq_loss_rows.h", "fq_kd_loss.h", "fq_ce_loss.h", "fq_rms_norm.h", "fq_swiglu.h", "fq_rope.h")] + [
+    os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_train.h", "llmqat_fakequant_sr.h", "llmqat_fakequant_infer.h", "llmqat_fakequant_loss.h", "llmqat_fakequant_ce.h", "llmqat_fakequant_norm.h", "llmqat_fakequant_act.h", "llmqat_fakequant_rope.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",
          "-fPIC", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 
@@ -63,7 +63,12 @@ NODE_DEPS = [NODE_SRC, os.path.join(os.path.dirname(HERE), "include", "llmqat_fa
 ACT_NODE_SRC = os.path.join(CSRC, "fq_swiglu_node.cpp")
 ACT_NODE_LIB = os.path.join(HERE, "_fq_act_node.so")
 ACT_NODE_DEPS = [ACT_NODE_SRC] + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_act.h")]
-_EXTENSIONS = ((NODE_SRC, NODE_LIB, NODE_DEPS, "_fq_node"), (ACT_NODE_SRC, ACT_NODE_LIB, ACT_NODE_DEPS, "_fq_act_node"))
+# the C++ autograd node of llm_qat_amd.rope.rotary (csrc/fq_rope_node.cpp -> _fq_rope_node.so): a third extension, host code only
+ROPE_NODE_SRC = os.path.join(CSRC, "fq_rope_node.cpp")
+ROPE_NODE_LIB = os.path.join(HERE, "_fq_rope_node.so")
+ROPE_NODE_DEPS = [ROPE_NODE_SRC] + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_rope.h")]
+_EXTENSIONS = ((NODE_SRC, NODE_LIB, NODE_DEPS, "_fq_node"), (ACT_NODE_SRC, ACT_NODE_LIB, ACT_NODE_DEPS, "_fq_act_node"),
+               (ROPE_NODE_SRC, ROPE_NODE_LIB, ROPE_NODE_DEPS, "_fq_rope_node"))
 
 
 def _ext_up_to_date(lib, deps):
@@ -79,8 +84,8 @@ def node_up_to_date():
 
 def build_node(force=False, verbose=False):
     """g++ against the PyTorch of this interpreter (its headers, its C++ ABI flag) and the HIP runtime headers (for the current stream);
-    linked against libtorch / libc10_hip only -- the kernels are reached through function pointers of the C ABI at run time.  Two
-    extensions: QuantizeLinear's node (-> its path) and, compiled beside it, the SwiGLU node."""
+    linked against libtorch / libc10_hip only -- the kernels are reached through function pointers of the C ABI at run time.  Three
+    extensions: QuantizeLinear's node (-> its path) and, compiled beside it, the SwiGLU node and the rotary node."""
     import sysconfig
     import torch
     tdir = os.path.dirname(torch.__file__)

@@ -8,7 +8,7 @@ ONE graph.  `utils_quant` routes here while `torch.compiler.is_compiling()`; res
 what a compiled graph keeps alive is planned by the partitioner, so the STE-mask / sharing / pairing machinery of the
 eager path is not replicated here.
 """
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -439,3 +439,59 @@ swiglu_fwd_op.register_autograd(_swiglu_backward, setup_context=_swiglu_setup)
 def swiglu(gate, up):
     """mlp.swiglu while compiling"""
     return swiglu_fwd_op(gate, up)
+
+
+# ---- the rotary embedding (ops.rope_forward / ops.rope_backward, DESIGN.md section 28): (q_embed, k_embed) and (dq, dk) -----------------------
+def _rope_empty(like, shape, strides, dtype):
+    return like.new_empty_strided(shape, ops.rope_dense_like(shape, strides), dtype=dtype)
+
+
+@torch.library.custom_op("llmqat_amd::rope_fwd", mutates_args=(), device_types="cuda")
+def rope_fwd_op(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, position_ids: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.rope_forward(q, k, cos, sin, position_ids)
+
+
+@rope_fwd_op.register_fake
+def _(q, k, cos, sin, position_ids):
+    ops.check_rope(q, k, cos, sin, position_ids)
+    rdt = ops.rope_result_dtype(q.dtype, k.dtype)
+    return _rope_empty(q, list(q.shape), list(q.stride()), rdt), _rope_empty(k, list(k.shape), list(k.stride()), rdt)
+
+
+@torch.library.custom_op("llmqat_amd::rope_bwd", mutates_args=(), device_types="cuda")
+def rope_bwd_op(dq_out: torch.Tensor, dk_out: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, position_ids: Optional[torch.Tensor],
+                q_shape: List[int], q_strides: List[int], q_dtype: torch.dtype, k_shape: List[int], k_strides: List[int], k_dtype: torch.dtype,
+                need_dq: bool, need_dk: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    dq, dk = ops.rope_backward(dq_out, dk_out, cos, sin, position_ids, (q_shape, q_strides, q_dtype), (k_shape, k_strides, k_dtype), need_dq, need_dk)
+    return (dq if need_dq else cos.new_empty(0)), (dk if need_dk else cos.new_empty(0))      # an op returns tensors: an empty one for "not asked for"
+
+
+@rope_bwd_op.register_fake
+def _(dq_out, dk_out, cos, sin, position_ids, q_shape, q_strides, q_dtype, k_shape, k_strides, k_dtype, need_dq, need_dk):
+    return ((_rope_empty(dq_out, q_shape, q_strides, q_dtype) if need_dq else cos.new_empty(0)),
+            (_rope_empty(dk_out, k_shape, k_strides, k_dtype) if need_dk else cos.new_empty(0)))
+
+
+def _rope_setup(ctx, inputs, output):
+    q, k, cos, sin, position_ids = inputs
+    ctx.save_for_backward(cos, sin, *(() if position_ids is None else (position_ids,)))       # the tables and positions alone
+    ctx.like = (list(q.shape), list(q.stride()), q.dtype, list(k.shape), list(k.stride()), k.dtype)
+
+
+def _rope_backward(ctx, dq_out, dk_out):
+    cos, sin, *pos = ctx.saved_tensors
+    need_dq, need_dk = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if not (need_dq or need_dk):
+        return None, None, None, None, None
+    dq, dk = rope_bwd_op(dq_out, dk_out, cos, sin, pos[0] if pos else None, *ctx.like, need_dq, need_dk)
+    return (dq if need_dq else None), (dk if need_dk else None), None, None, None
+
+
+rope_fwd_op.register_autograd(_rope_backward, setup_context=_rope_setup)
+
+
+def rope(q, k, cos, sin, position_ids=None):
+    """rope.rotary while compiling (a tensor whose last stride is not 1 is copied in front of the op, so that the op's results have the
+    layout its fake implementation states)"""
+    q, k = (t if t.stride(-1) == 1 else t.contiguous() for t in (q, k))
+    return rope_fwd_op(q, k, cos, sin, position_ids)

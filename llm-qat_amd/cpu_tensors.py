@@ -78,3 +78,19 @@ def rms_norm(x, w, eps):
 def swiglu(gate, up):
     """the middle of LlamaMLP.forward (models/modeling_llama_quant.py:235) with act_fn = SiLU, differentiated by autograd as the reference's is"""
     return torch.nn.functional.silu(gate) * up
+
+
+def rope(q, k, cos, sin, position_ids=None):
+    """apply_rotary_pos_emb (models/modeling_llama_quant.py:181-196) with the cast of the tables to the tensors' dtype that the rotary module
+    makes in front of it (:176-177; where q and k differ in dtype, one of them is float32 and so are the tables, as v's dtype makes them
+    there), differentiated by autograd as the reference's is; position_ids None: the token index"""
+    D = q.shape[-1]
+    dt = q.dtype if q.dtype == k.dtype else torch.float32
+    cos, sin = cos.reshape(-1, D).to(dtype=dt), sin.reshape(-1, D).to(dtype=dt)
+    if position_ids is None:
+        position_ids = torch.arange(q.shape[2], device=q.device).unsqueeze(0)
+    cos, sin = cos[position_ids].unsqueeze(1), sin[position_ids].unsqueeze(1)
+
+    def rotate_half(x):
+        return torch.cat((-x[..., D // 2:], x[..., : D // 2]), dim=-1)
+    return (q * cos) + (rotate_half(q) * sin), (k * cos) + (rotate_half(k) * sin)

@@ -4,6 +4,7 @@ Everything here is host-side plumbing (shape -> [rows, cols], dtype codes, strea
 workspace); the arithmetic happens in the HIP kernels.  CPU tensors are rejected: this
 package is the MI355X path and has no CPU implementation.
 """
+import ctypes
 import os
 
 import torch
@@ -1815,3 +1816,193 @@ def swiglu_backward(dy, gate, up, need_dgate=True, need_dup=True, checked=None):
     _lib.check(rc, "swiglu_backward")
     act_counts["bwd_launch"] += 1
     return dgate, dup
+
+
+# ---- the rotary position embedding of q and k (the fqr_ header) ---------------------------------------------------------
+class _RopeCounts(_ActCounts):
+    """fwd_launch / bwd_launch / copy_route of the rotary embedding: this module's counts plus those of the C++ node of rope.rotary"""
+
+    def __getitem__(self, key):
+        from . import _rope_node
+        return self._own[key] + _rope_node.counters()[self._KEYS.index(key)]
+
+    def __setitem__(self, key, value):
+        from . import _rope_node
+        self._own[key] = value - _rope_node.counters()[self._KEYS.index(key)]
+
+
+rope_counts = _RopeCounts()
+
+
+def check_rope_tables(cos, sin, position_ids, lead, B, T, D, what, dtype):
+    """check_rope's checks of the tables and positions against a tensor `lead` on the tensors' device; dtype: rope_result_dtype"""
+    named = dict(cos=cos, sin=sin)
+    if position_ids is not None:
+        named["position_ids"] = position_ids
+    _row_tensors(what, **named)
+    if cos.dtype != sin.dtype or (cos.dtype != dtype and cos.dtype != torch.float32):
+        raise TypeError(f"{what}: the tables are both in the tensors' dtype ({dtype}) or both in float32, got {cos.dtype} and {sin.dtype}")
+    if tuple(cos.shape) != tuple(sin.shape) or not ((cos.dim() == 2 or (cos.dim() == 4 and cos.shape[0] == cos.shape[1] == 1)) and cos.shape[-1] == D and cos.shape[-2] > 0):
+        raise ValueError(f"{what}: the tables are [P, {D}] or [1, 1, P, {D}] with P > 0 and equal shapes, got {tuple(cos.shape)} and {tuple(sin.shape)}")
+    if position_ids is not None:
+        if position_ids.dtype != torch.int64:
+            raise TypeError(f"{what}: position_ids of dtype {position_ids.dtype}: int64 is served")
+        if position_ids.dim() != 2 or position_ids.shape[1] != T or position_ids.shape[0] not in (1, B):
+            raise ValueError(f"{what}: position_ids are [{B}, {T}] or [1, {T}], got {tuple(position_ids.shape)}")
+    for name, t in named.items():
+        if t.device != lead.device:
+            raise ValueError(f"{what}: the tensors are on {lead.device}, {name} on {t.device}")
+
+
+def check_rope(q, k, cos, sin, position_ids=None, what="rotary"):
+    """The argument checks of the rotary embedding on types, shapes, dtypes and devices alone (the fake implementations of the compiled
+    ops run them too) -> (B, Hq, Hk, T, D, P): TypeError for a non-tensor, a dtype that is not served, unequal dtypes of q and k, tables
+    that are neither in that dtype nor float32, positions that are not int64; ValueError for shapes (q, k not 4-D or unequal in batch,
+    tokens or head size, an odd head size, an empty tensor, tables that are not [P, D] or [1, 1, P, D], positions that are not [B, T] or
+    [1, T]) and for tensors on different devices."""
+    try:                                                   # the call that is served, in one expression; else: which refusal
+        T, D, dev, p = q.shape[2], q.shape[3], q.device, position_ids
+        if (type(q) is type(k) is type(cos) is type(sin) is torch.Tensor and q.dtype in _OUT_DTYPES and k.dtype in _OUT_DTYPES
+                and (q.dtype is k.dtype or torch.float32 in (q.dtype, k.dtype)) and q.dim() == 4 and k.dim() == 4
+                and k.shape[0] == q.shape[0] and k.shape[2] == T and k.shape[3] == D and D % 2 == 0 and q.numel() and k.numel()
+                and cos.dtype is sin.dtype and (cos.dtype is torch.float32 or cos.dtype is q.dtype is k.dtype) and cos.shape == sin.shape and cos.shape[-1] == D
+                and (cos.dim() == 2 or (cos.dim() == 4 and cos.shape[0] == cos.shape[1] == 1)) and cos.shape[-2] > 0
+                and k.device == dev and cos.device == dev and sin.device == dev
+                and (p is None or (type(p) is torch.Tensor and p.dtype is torch.int64 and p.dim() == 2 and p.shape[1] == T and p.shape[0] in (1, q.shape[0]) and p.device == dev))):
+            return q.shape[0], q.shape[1], k.shape[1], T, D, cos.shape[-2]
+    except (AttributeError, IndexError):
+        pass
+    named = dict(q=q, k=k, cos=cos, sin=sin)
+    if position_ids is not None:
+        named["position_ids"] = position_ids
+    _row_tensors(what, **named)
+    for name, t in (("q", q), ("k", k)):
+        if t.dtype not in _OUT_DTYPES:
+            raise TypeError(f"{what}: {name} of dtype {t.dtype} is not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+    if q.dtype != k.dtype and torch.float32 not in (q.dtype, k.dtype):
+        raise TypeError(f"{what}: q is {q.dtype}, k is {k.dtype}: two dtypes are served where one of them is float32 (the chain then promotes)")
+    if q.dim() != 4 or k.dim() != 4:
+        raise ValueError(f"{what}: q and k are [B, H, T, D], got {tuple(q.shape)} and {tuple(k.shape)}")
+    B, Hq, T, D = q.shape
+    if (k.shape[0], k.shape[2], k.shape[3]) != (B, T, D):
+        raise ValueError(f"{what}: q and k differ in batch, tokens or head size: {tuple(q.shape)} and {tuple(k.shape)}")
+    Hk = k.shape[1]
+    if q.numel() == 0 or k.numel() == 0:
+        raise ValueError(f"{what}: empty tensors are not served: q {tuple(q.shape)}, k {tuple(k.shape)}")
+    if D % 2:
+        raise ValueError(f"{what}: odd head size D={D}: a rotation pairs the two halves of a head")
+    check_rope_tables(cos, sin, position_ids, q, B, T, D, what, rope_result_dtype(q.dtype, k.dtype))
+    if k.device != q.device:
+        raise ValueError(f"{what}: q is on {q.device}, k on {k.device}")
+    return B, Hq, Hk, T, D, cos.shape[-2]
+
+
+def rope_result_dtype(q_dtype, k_dtype):
+    """the dtype of both results, of both incoming gradients, and the one the tables are rounded to: the tensors' dtype, or float32 where
+    q and k differ (one of them then is float32, and the chain promotes)"""
+    return q_dtype if q_dtype == k_dtype else torch.float32
+
+
+def _rope_served(t):
+    """-> t, or its one counted copy where the last stride is not 1"""
+    if t.stride(-1) == 1 or t.shape[-1] == 1:
+        return t
+    rope_counts["copy_route"] += 1
+    return t.contiguous()
+
+
+def _rope_table(t, D):
+    """-> the table as [P, D] with contiguous rows: a view where it is, else its one counted copy"""
+    t = t.reshape(t.shape[-2], D) if t.dim() == 4 else t
+    if t.stride(1) == 1 and (t.stride(0) == D or t.shape[0] == 1):
+        return t
+    rope_counts["copy_route"] += 1
+    return t.contiguous()
+
+
+def _rope_positions(position_ids, B):
+    """-> (positions or None, their batch stride in elements)"""
+    if position_ids is None:
+        return None, 0
+    if not position_ids.is_contiguous():
+        rope_counts["copy_route"] += 1
+        position_ids = position_ids.contiguous()
+    return position_ids, (position_ids.shape[1] if position_ids.shape[0] == B and B > 1 else 0)
+
+
+def rope_dense_like(shape, strides):
+    """-> the strides of the dense tensor in the dimension order of a [B, H, T, D] tensor with the given strides: the layout of the
+    rotary embedding's results, which is the eager chain's (the rule of include/llmqat_fakequant_rope.h, asked of the library)"""
+    out = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.lib().fqr_rope_dense_strides(shape[0], shape[1], shape[2], shape[3], strides[0], strides[1], strides[2], out), "rope_dense_like")
+    return (out[0], out[1], out[2], 1)
+
+
+def rope_launch_forward(q, k, cos, sin, position_ids, geom):
+    """rope_forward behind check_rope's geometry, for a caller that has run the checks -> (q_out, k_out, cos, sin, positions, q, k): the
+    tables, positions and tensors as the launch read them (a backward needs the first three and the shapes, strides and dtypes of q, k)"""
+    B, Hq, Hk, T, D, P = geom
+    _prep(q, "rope_forward")
+    q, k = _rope_served(q), _rope_served(k)
+    cos, sin = _rope_table(cos, D), _rope_table(sin, D)
+    pos, pbs = _rope_positions(position_ids, B)
+    rdt = rope_result_dtype(q.dtype, k.dtype)
+    qo = torch.empty_strided(q.shape, rope_dense_like(q.shape, q.stride()), dtype=rdt, device=q.device)
+    ko = torch.empty_strided(k.shape, rope_dense_like(k.shape, k.stride()), dtype=rdt, device=k.device)
+    rc = _launch(q, _lib.lib().fqr_rope_fwd, q.data_ptr(), k.data_ptr(), qo.data_ptr(), ko.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                 pos.data_ptr() if pos is not None else None, pbs, B, Hq, Hk, T, D, P, *q.stride()[:3], *k.stride()[:3], _OUT_DTYPES[q.dtype],
+                 _OUT_DTYPES[k.dtype], _OUT_DTYPES[cos.dtype])
+    _lib.check(rc, "rope_forward")
+    rope_counts["fwd_launch"] += 1
+    return qo, ko, cos, sin, pos, q, k
+
+
+def rope_forward(q, k, cos, sin, position_ids=None):
+    """-> (q_embed, k_embed) = the eager chain's x * cos[pos] + rotate_half(x) * sin[pos] for q and k, bit for bit, each dense in its
+    input's dimension order (the chain's own layout).  q and k have one dtype, or one of them is float32 and the tables are: the results
+    are then float32, as the chain's promotion makes them.  q [B, Hq, T, D], k [B, Hk, T, D] with a last stride of 1 are read where they lie
+    (any other layout is copied once and counted); cos, sin [P, D] or [1, 1, P, D] in the tensors' dtype or float32; position_ids int64
+    [B, T] or [1, T], None: the token index.  One launch on the current stream (fwd_launch)."""
+    geom = check_rope(q, k, cos, sin, position_ids, "rope_forward")
+    return rope_launch_forward(q, k, cos, sin, position_ids, geom)[:2]
+
+
+def rope_backward(dq_out, dk_out, cos, sin, position_ids, q_like, k_like, need_dq=True, need_dk=True):
+    """-> (dq, dk), the bits of the eager chain's autograd, dense in the dimension order of the forward's q and k; None for the one that
+    is not needed (neither read, computed nor stored).  dq_out, dk_out: the gradients of rope_forward's results; q_like, k_like: the
+    forward's q and k, or their (shape, strides, dtype) -- no value of q or k is read.  One launch (bwd_launch)."""
+    if not (need_dq or need_dk):
+        raise ValueError("rope_backward: neither dq nor dk is asked for")
+    (qshape, qstr, qdt), (kshape, kstr, kdt) = ((tuple(t.shape), tuple(t.stride()), t.dtype) if isinstance(t, torch.Tensor) else (tuple(t[0]), tuple(t[1]), t[2])
+                                                for t in (q_like, k_like))
+    lead = dq_out if need_dq else dk_out
+    grads = {}
+    for name, g, shape, need in (("dq_out", dq_out, qshape, need_dq), ("dk_out", dk_out, kshape, need_dk)):
+        if need:
+            _row_tensors("rope_backward", **{name: g})
+            if tuple(g.shape) != shape or g.dtype != lead.dtype or g.device != lead.device:
+                raise ValueError(f"rope_backward: {name} is the gradient of a result: {shape} of {lead.dtype} on {lead.device}, got {tuple(g.shape)} of {g.dtype} on {g.device}")
+            grads[name] = g
+    if len(qshape) != 4 or len(kshape) != 4 or (kshape[0], kshape[2], kshape[3]) != (qshape[0], qshape[2], qshape[3]) or qshape[3] % 2 or not all(qshape + kshape):
+        raise ValueError(f"rope_backward: q and k are non-empty [B, H, T, D] with an even D and equal B, T, D, got {qshape} and {kshape}")
+    B, Hq, T, D = qshape
+    Hk = kshape[1]
+    if qdt not in _OUT_DTYPES or kdt not in _OUT_DTYPES or (qdt != kdt and torch.float32 not in (qdt, kdt)) or lead.dtype != rope_result_dtype(qdt, kdt):
+        raise TypeError(f"rope_backward: q of {qdt} and k of {kdt} with gradients of {lead.dtype} are not served")
+    check_rope_tables(cos, sin, position_ids, lead, B, T, D, "rope_backward", lead.dtype)
+    _prep(lead, "rope_backward")
+    gq = _rope_served(dq_out) if need_dq else None
+    gk = _rope_served(dk_out) if need_dk else None
+    cos, sin = _rope_table(cos, D), _rope_table(sin, D)
+    pos, pbs = _rope_positions(position_ids, B)
+    dq = torch.empty_strided(qshape, rope_dense_like(qshape, qstr), dtype=qdt, device=lead.device) if need_dq else None
+    dk = torch.empty_strided(kshape, rope_dense_like(kshape, kstr), dtype=kdt, device=lead.device) if need_dk else None
+    zero3 = (0, 0, 0)
+    rc = _launch(lead, _lib.lib().fqr_rope_bwd, gq.data_ptr() if need_dq else None, gk.data_ptr() if need_dk else None,
+                 dq.data_ptr() if need_dq else None, dk.data_ptr() if need_dk else None, cos.data_ptr(), sin.data_ptr(),
+                 pos.data_ptr() if pos is not None else None, pbs, B, Hq, Hk, T, D, cos.shape[0],
+                 *(gq.stride()[:3] if need_dq else zero3), *(gk.stride()[:3] if need_dk else zero3), *qstr[:3], *kstr[:3],
+                 _OUT_DTYPES[qdt], _OUT_DTYPES[kdt], _OUT_DTYPES[cos.dtype])
+    _lib.check(rc, "rope_backward")
+    rope_counts["bwd_launch"] += 1
+    return dq, dk
