@@ -47,6 +47,8 @@ NORM_EXPORTS = ("fqn_rms_norm_fwd", "fqn_rms_norm_bwd", "fqn_rms_norm_bwd_parts"
 ACT_EXPORTS = ("fqa_swiglu_fwd", "fqa_swiglu_bwd")
 # every symbol include/llmqat_fakequant_rope.h declares (the fqr_ family: the rotary position embedding of q and k)
 ROPE_EXPORTS = ("fqr_rope_dense_strides", "fqr_rope_fwd", "fqr_rope_bwd")
+# every symbol include/llmqat_fakequant_attn.h declares (the fqs2_ family: the softmax chain between the two attention products)
+ATTN_EXPORTS = ("fqs2_attn_softmax_fwd", "fqs2_attn_softmax_bwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -205,6 +207,10 @@ def _bind(L):
     L.fqr_rope_fwd.restype = i32
     L.fqr_rope_bwd.argtypes = [vp] * 7 + [i64] * 19 + [i32, i32, i32, vp]
     L.fqr_rope_bwd.restype = i32
+    L.fqs2_attn_softmax_fwd.argtypes = [vp] * 4 + [i64] * 7 + [f32, i32, i32, vp]
+    L.fqs2_attn_softmax_fwd.restype = i32
+    L.fqs2_attn_softmax_bwd.argtypes = [vp] * 5 + [i64] * 7 + [f32, i32, i32, vp]
+    L.fqs2_attn_softmax_bwd.restype = i32
     return L
 
 

@@ -5,6 +5,7 @@ from . import lm_loss   # llm_qat_amd.lm_loss: cross_entropy, causal_lm_loss, Cr
 from . import norm      # llm_qat_amd.norm: rms_norm, RMSNorm, install, convert (likewise)
 from . import mlp       # llm_qat_amd.mlp: swiglu, SwiGLUMLP, install, convert (likewise)
 from . import rope      # llm_qat_amd.rope: apply_rotary_pos_emb, rotary, install (likewise)
+from . import attention  # llm_qat_amd.attention: attn_softmax, install, convert (likewise)
 from .cpu_tensors import allow_cpu_tensors
 from ._lib import FakeQuantLibraryError
 from .ops import get_semantics, set_semantics

@@ -13,9 +13,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libllmqat_fakequant.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("fq_api.hip", "fq_bf16.hip", "fq_f32.hip", "fq_f16.hip", "fq_export.hip", "fq_f64.hip", "fq_group.hip", "fq_mx.hip", "fq_mx_gemm.hip", "fq_mx_cols.hip", "fq_mx_sr.hip", "fq_mx_dequant.hip", "fq_kd_loss.hip", "fq_ce_loss.hip", "fq_rms_norm.hip", "fq_swiglu.hip", "fq_rope.hip")]
-DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("fq_kernels.h", "fq_device.h", "fq_launch.h", "fq_shapes.h", "fq_dtype_impl.h", "fq_export.h", "fq_group.h", "fq_mx.h", "fq_mx_gemm.h", "fq_mx_cols.h", "fq_mx_sr.h", "fq_mx_dequant.h", "fq_rows.h", "fq_loss_rows.h", "fq_kd_loss.h", "fq_ce_loss.h", "fq_rms_norm.h", "fq_swiglu.h", "fq_rope.h")] + [
-    os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_train.h", "llmqat_fakequant_sr.h", "llmqat_fakequant_infer.h", "llmqat_fakequant_loss.h", "llmqat_fakequant_ce.h", "llmqat_fakequant_norm.h", "llmqat_fakequant_act.h", "llmqat_fakequant_rope.h")]
+SOURCES = [os.path.join(CSRC, f) for f in ("fq_api.hip", "fq_bf16.hip", "fq_f32.hip", "fq_f16.hip", "fq_export.hip", "fq_f64.hip", "fq_group.hip", "fq_mx.hip", "fq_mx_gemm.hip", "fq_mx_cols.hip", "fq_mx_sr.hip", "fq_mx_dequant.hip", "fq_kd_loss.hip", "fq_ce_loss.hip", "fq_rms_norm.hip", "fq_swiglu.hip", "fq_rope.hip", "fq_attn_softmax.hip")]
+DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("fq_kernels.h", "fq_device.h", "fq_launch.h", "fq_shapes.h", "fq_dtype_impl.h", "fq_export.h", "fq_group.h", "fq_mx.h", "fq_mx_gemm.h", "fq_mx_cols.h", "fq_mx_sr.h", "fq_mx_dequant.h", "fq_rows.h", "fq_loss_rows.h", "fq_kd_loss.h", "fq_ce_loss.h", "fq_rms_norm.h", "fq_swiglu.h", "fq_rope.h", "fq_attn_softmax.h")] + [
+    os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_train.h", "llmqat_fakequant_sr.h", "llmqat_fakequant_infer.h", "llmqat_fakequant_loss.h", "llmqat_fakequant_ce.h", "llmqat_fakequant_norm.h", "llmqat_fakequant_act.h", "llmqat_fakequant_rope.h", "llmqat_fakequant_attn.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",
          "-fPIC", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 

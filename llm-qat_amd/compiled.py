@@ -495,3 +495,49 @@ def rope(q, k, cos, sin, position_ids=None):
     layout its fake implementation states)"""
     q, k = (t if t.stride(-1) == 1 else t.contiguous() for t in (q, k))
     return rope_fwd_op(q, k, cos, sin, position_ids)
+
+
+# ---- the attention softmax (ops.attn_softmax_forward / ops.attn_softmax_backward, DESIGN.md section 29): (y, stats) and dx ------------------
+@torch.library.custom_op("llmqat_amd::attn_softmax_fwd", mutates_args=(), device_types="cuda")
+def attn_softmax_fwd_op(scores: torch.Tensor, mask: Optional[torch.Tensor], inv: float, need_stats: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    y, stats = ops.attn_softmax_forward(scores, mask, scale=inv, need_stats=need_stats)
+    return y, (stats if need_stats else scores.new_empty((0, 2), dtype=torch.float32))      # an op returns tensors: an empty one for "not written"
+
+
+@attn_softmax_fwd_op.register_fake
+def _(scores, mask, inv, need_stats):
+    B, H, T, _, _ = ops.check_attn_softmax(scores, mask, scale=inv)
+    return torch.empty_like(scores, memory_format=torch.contiguous_format), scores.new_empty((B * H * T if need_stats else 0, 2), dtype=torch.float32)
+
+
+@torch.library.custom_op("llmqat_amd::attn_softmax_bwd", mutates_args=(), device_types="cuda")
+def attn_softmax_bwd_op(g: torch.Tensor, scores: torch.Tensor, mask: Optional[torch.Tensor], stats: torch.Tensor, inv: float) -> torch.Tensor:
+    return ops.attn_softmax_backward(g, scores, mask, stats, scale=inv)
+
+
+@attn_softmax_bwd_op.register_fake
+def _(g, scores, mask, stats, inv):
+    ops.check_attn_softmax(scores, mask, scale=inv)
+    return torch.empty_like(scores, memory_format=torch.contiguous_format)
+
+
+def _attn_setup(ctx, inputs, output):
+    scores, mask, inv, _ = inputs
+    ctx.save_for_backward(scores, output[1], *(() if mask is None else (mask,)))       # the scores, the stats and the mask alone
+    ctx.inv = inv
+
+
+def _attn_backward(ctx, grad_y, grad_stats):
+    scores, stats, *mask = ctx.saved_tensors
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None
+    return attn_softmax_bwd_op(grad_y, scores, mask[0] if mask else None, stats, ctx.inv), None, None, None
+
+
+attn_softmax_fwd_op.register_autograd(_attn_backward, setup_context=_attn_setup)
+
+
+def attn_softmax(scores, mask, inv):
+    """attention.attn_softmax while compiling; as in eager mode no stats are written when no gradient can be asked for"""
+    need = torch.is_grad_enabled() and scores.requires_grad
+    return attn_softmax_fwd_op(scores, mask, inv, need)[0]

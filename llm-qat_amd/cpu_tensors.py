@@ -6,6 +6,7 @@ It is NOT a fallback: it is selected by `tensor.device.type == "cpu"` only, and 
 LLMQAT_AMD_CPU_TENSORS=1 (the default keeps raising).  A CUDA tensor never comes here: if the HIP library is missing or a launch
 fails, the GPU path raises.  Nothing here touches the test infrastructure; ATen's CPU kernels ARE the reference's CPU path.
 """
+import math
 import os
 
 import torch
@@ -94,3 +95,14 @@ def rope(q, k, cos, sin, position_ids=None):
     def rotate_half(x):
         return torch.cat((-x[..., D // 2:], x[..., : D // 2]), dim=-1)
     return (q * cos) + (rotate_half(q) * sin), (k * cos) + (rotate_half(k) * sin)
+
+
+def attn_softmax(scores, mask, head_dim=None, scale=None):
+    """the lines between the two attention products of LlamaAttention.forward (models/modeling_llama_quant.py:352-375), differentiated by
+    autograd as the reference's are: the division by sqrt(head_dim) (a true division, as ATen's on the CPU; a given scale multiplies), the
+    mask and the clamp where there is a mask, the fp32 softmax and its cast back"""
+    attn = scores / math.sqrt(head_dim) if scale is None else scores * scale
+    if mask is not None:
+        attn = attn + mask
+        attn = torch.max(attn, torch.tensor(torch.finfo(attn.dtype).min))
+    return torch.nn.functional.softmax(attn, dim=-1, dtype=torch.float32).to(scores.dtype)

@@ -2006,3 +2006,109 @@ def rope_backward(dq_out, dk_out, cos, sin, position_ids, q_like, k_like, need_d
     _lib.check(rc, "rope_backward")
     rope_counts["bwd_launch"] += 1
     return dq, dk
+
+
+# ---- the softmax chain between the two attention products (the fqs2_ header) ------------------------------------------------
+attn_counts = {"fwd_launch": 0, "bwd_launch": 0, "copy_route": 0}
+
+
+@torch.compiler.assume_constant_result      # Python numbers in, a Python float out: a constant of the graph while compiling
+def attn_inv(head_dim=None, scale=None, what="attn_softmax"):
+    """-> the fp32 factor the scores are multiplied by, as a Python float: `scale` rounded to fp32, or the fp32 reciprocal of
+    (float)sqrt(head_dim), which is what `tensor / math.sqrt(head_dim)` multiplies by on the device.  Exactly one of the two is given."""
+    if (head_dim is None) == (scale is None):
+        raise TypeError(f"{what}: give head_dim (the scores are divided by sqrt(head_dim)) or scale (they are multiplied by it), and not both")
+    if scale is not None:
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+            raise TypeError(f"{what}: scale is a number, got {type(scale).__name__}")
+        return ctypes.c_float(scale).value
+    if isinstance(head_dim, bool) or not isinstance(head_dim, int):
+        raise TypeError(f"{what}: head_dim is an int, got {type(head_dim).__name__}")
+    if head_dim <= 0:
+        raise ValueError(f"{what}: head_dim={head_dim} must be positive")
+    return ctypes.c_float(1.0 / ctypes.c_float(head_dim ** 0.5).value).value      # the quotient of two floats in double, rounded once: fp32's own
+
+
+def check_attn_softmax(scores, attention_mask=None, head_dim=None, scale=None, what="attn_softmax"):
+    """The argument checks of the attention softmax on types, shapes, dtypes and devices alone (the fake implementations of the compiled
+    ops run them too) -> (B, H, T, S, inv): TypeError for a non-tensor, a dtype that is not served (float64), a mask whose dtype is neither
+    the scores' nor float32, a head_dim / scale of the wrong type or both or neither of them; ValueError for scores that are not a
+    non-empty [B, H, T, S], a mask that is not [B, 1, T, S] or [1, 1, T, S], a head_dim that is not positive, tensors on two devices."""
+    _row_tensors(what, scores=scores)
+    if attention_mask is not None:
+        _row_tensors(what, attention_mask=attention_mask)
+    if scores.dtype not in _OUT_DTYPES:
+        raise TypeError(f"{what}: scores of dtype {scores.dtype} are not served (float32, bfloat16, float16 are; the arithmetic is fp32 for all three)")
+    if attention_mask is not None and attention_mask.dtype not in (scores.dtype, torch.float32):
+        raise TypeError(f"{what}: a mask of dtype {attention_mask.dtype} beside scores of {scores.dtype} is not served: the scores' dtype or float32")
+    inv = attn_inv(head_dim, scale, what)
+    if scores.dim() != 4 or scores.numel() == 0:
+        raise ValueError(f"{what}: scores are a non-empty [B, H, T, S], got {tuple(scores.shape)}")
+    B, H, T, S = scores.shape
+    if attention_mask is not None:
+        if attention_mask.dim() != 4 or tuple(attention_mask.shape[1:]) != (1, T, S) or attention_mask.shape[0] not in (1, B):
+            raise ValueError(f"{what}: the mask is [{B}, 1, {T}, {S}] or [1, 1, {T}, {S}], got {tuple(attention_mask.shape)}")
+        if attention_mask.device != scores.device:
+            raise ValueError(f"{what}: scores are on {scores.device}, the mask on {attention_mask.device}")
+    return B, H, T, S, inv
+
+
+def _attn_mask(mask, B, T):
+    """-> (mask as the launch reads it or None, batch stride, row stride, dtype code): read where it lies with a last stride of 1, else its
+    one counted copy; a batch of size 1 beside B > 1 (or an expanded one) has batch stride 0"""
+    if mask is None:
+        return None, 0, 0, _lib.DTYPE_F32
+    if mask.stride(-1) != 1 and mask.shape[-1] > 1:
+        attn_counts["copy_route"] += 1
+        mask = mask.contiguous()
+    return mask, (mask.stride(0) if mask.shape[0] == B and B > 1 else 0), (mask.stride(2) if T > 1 else 0), _OUT_DTYPES[mask.dtype]
+
+
+def attn_launch_forward(scores, mask, geom, need_stats=True):
+    """attn_softmax_forward behind check_attn_softmax's geometry, for a caller that has run the checks -> (y, stats, scores, mask): the
+    scores and the mask as the launch read them (what a backward needs)"""
+    B, H, T, S, inv = geom
+    _prep(scores, "attn_softmax_forward")
+    scores = _row_contig(scores, attn_counts)
+    mask, mbs, mrs, mcode = _attn_mask(mask, B, T)
+    rows = B * H * T
+    y = torch.empty_like(scores)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=scores.device) if need_stats else None
+    rc = _launch(scores, _lib.lib().fqs2_attn_softmax_fwd, scores.data_ptr(), mask.data_ptr() if mask is not None else None, y.data_ptr(),
+                 stats.data_ptr() if need_stats else None, rows, S, B, H, T, mbs, mrs, inv, _OUT_DTYPES[scores.dtype], mcode)
+    _lib.check(rc, "attn_softmax_forward")
+    attn_counts["fwd_launch"] += 1
+    return y, stats, scores, mask
+
+
+def attn_softmax_forward(scores, attention_mask=None, head_dim=None, scale=None, need_stats=True):
+    """-> (y, stats): y = softmax(max(scores / sqrt(head_dim) + mask, finfo.min), -1, float32) in the scores' dtype with the eager chain's
+    roundings in front of the softmax (no clamp without a mask, as the reference), and the fp32 [rows, 2] row maxima and sums the
+    backward reads (None with need_stats=False: no buffer, nothing written).  scores [B, H, T, S]; the mask [B, 1, T, S] or [1, 1, T, S]
+    in the scores' dtype or float32 (the sum then promotes), read where it lies with a last stride of 1.  One launch (fwd_launch)."""
+    geom = check_attn_softmax(scores, attention_mask, head_dim, scale, "attn_softmax_forward")
+    return attn_launch_forward(scores, attention_mask, geom, need_stats)[:2]
+
+
+def attn_softmax_backward(g, scores, attention_mask, stats, head_dim=None, scale=None):
+    """-> dx of the scores' shape and dtype: the chain's autograd with its casts and the gradient of torch.max (a tie gets half, an element
+    below finfo.min none).  g: the gradient of attn_softmax_forward's y (its shape and dtype); scores, mask, head_dim / scale: the
+    forward's; stats: the forward's.  No atomics: two calls give the same bits.  One launch (bwd_launch)."""
+    with torch.no_grad():
+        B, H, T, S, inv = check_attn_softmax(scores, attention_mask, head_dim, scale, "attn_softmax_backward")
+    _prep(scores, "attn_softmax_backward")
+    _row_tensors("attn_softmax_backward", g=g)
+    if g.dtype != scores.dtype or tuple(g.shape) != tuple(scores.shape) or g.device != scores.device:
+        raise ValueError(f"attn_softmax_backward: g is the gradient of y: {tuple(scores.shape)} of {scores.dtype} on {scores.device}, got "
+                         f"{tuple(g.shape)} of {g.dtype} on {g.device}")
+    rows = B * H * T
+    _row_stats("attn_softmax_backward", stats, "stats is attn_softmax_forward's", (rows, 2), scores)
+    scores = _row_contig(scores.detach(), attn_counts)
+    g = _row_contig(g.detach(), attn_counts)
+    mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
+    dx = torch.empty_like(scores)
+    rc = _launch(scores, _lib.lib().fqs2_attn_softmax_bwd, g.data_ptr(), scores.data_ptr(), mask.data_ptr() if mask is not None else None,
+                 stats.data_ptr(), dx.data_ptr(), rows, S, B, H, T, mbs, mrs, inv, _OUT_DTYPES[scores.dtype], mcode)
+    _lib.check(rc, "attn_softmax_backward")
+    attn_counts["bwd_launch"] += 1
+    return dx
