@@ -26,7 +26,11 @@ HEAD_DIM = 128
 #   on the MI355X (ROCm's ATen kernels):  C_y 18.3729 (randn_s60_S33_none), C_dx 17.2965 (randn_s60_S33_causal)       <- what the caps are made of
 #   on the CPU (ATen's CPU kernels):      C_y 60.0508 (ramp_S2049_none), C_dx 45.6167 (randn_s60_S2049_none)
 # The fused path runs on the MI355X, so its bar is the chain it replaces there.  (The fused path itself, fp32: 27.2 and 27.4.)
-EAGER_C_Y = 18.38
+# The launch ladder's cases (tests/row_ladder_cases.py: a seeded row that three elements carry, 1 .. 16392 columns) are part of the list
+# since tests/test_gpu_attn_softmax_shapes.py measures the chain on each of them beside the kernels.  On the MI355X its largest measures
+# there: C_y 18.9271 (520 columns, masked; 18.70 at 516, 18.54 at 512, below 18 elsewhere), C_dx 11.386 (2044 columns, masked).  C_y is
+# above CASES' 18.3729, so the cap on y is made of it (73.52 -> 75.72); the cap on dx stays CASES'.  (The fused path there, fp32: 32.9, 16.4.)
+EAGER_C_Y = 18.93
 EAGER_C_DX = 17.30
 Y_CAP = 4 * EAGER_C_Y
 DX_CAP = 4 * EAGER_C_DX

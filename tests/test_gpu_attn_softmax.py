@@ -1,6 +1,7 @@
 """GPU tier of the fused attention softmax (llm_qat_amd.attention): the kernels against float64 under the caps that the
-eager chain set (tests/attn_softmax_reference.py), every launch shape, the device's scalar rule and the roundings in front of the softmax
-bit for bit, masked rows, special values, memory, counters, torch.compile and a tiny LLaMA through install."""
+eager chain set (tests/attn_softmax_reference.py), ten launch shapes (the whole ladder: tests/test_gpu_attn_softmax_shapes.py), the device's
+scalar rule and the roundings in front of the softmax bit for bit, masked rows, special values, memory, counters, torch.compile and a tiny
+LLaMA through install."""
 import types
 
 import numpy as np
@@ -87,6 +88,7 @@ def _check(x, mask, g, what):
 
 @pytest.mark.parametrize("S", [1, 7, 33, 64, 255, 2047, 2048, 2049, 4099, 8200])
 def test_every_launch_shape_alignment_and_pair(S):
+    """(the full ladder, every register rung and every boundary of it: tests/test_gpu_attn_softmax_shapes.py)"""
     for ds, dm in PAIRS:
         for offset in (0, 1):
             _check(*_shape_case(1, 1, 5, S, ds, dm, S + offset, offset=offset), what=(S, ds, dm, offset))

@@ -14,6 +14,7 @@ from llm_qat_amd import _lib, norm, ops
 from llm_qat_amd.norm import rms_norm
 
 import rms_norm_reference as R
+import row_ladder_cases as C
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,16 +89,48 @@ def test_a_mixed_pair_with_several_wide_rows_per_part():
         assert_contract(*inputs(shape, 1150, xdt, wdt), f"{shape} x {xdt} w {wdt}")
 
 
-@pytest.mark.parametrize("shape", [(5, 256), (3, 2048), (2, 8200), (1027, 4104)], ids=lambda s: f"{s[0]}x{s[1]}")
+OFFSET_SHAPES = [(5, 256), (3, 2048), (2, 8200), (1027, 4104)]
+
+
+def offset_by_one(t):
+    """the same values in storage that is not 16-byte aligned"""
+    n = t.numel()
+    out = torch.empty(n + 8, dtype=t.dtype, device="cuda")[1:n + 1].view(t.shape).copy_(t)
+    assert out.data_ptr() % 16 != 0 and out.is_contiguous()
+    return out
+
+
+@pytest.mark.parametrize("shape", OFFSET_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_a_base_pointer_offset_by_one_element_takes_the_element_path(shape):
     for dtype in DTYPES:
         x, w, g = inputs(shape, 1200 + shape[1], dtype, dtype)
-        n = x.numel()
-        xo = torch.empty(n + 8, dtype=dtype, device="cuda")[1:n + 1].view(shape).copy_(x)
-        go = torch.empty(n + 8, dtype=dtype, device="cuda")[1:n + 1].view(shape).copy_(g)
-        assert xo.data_ptr() % 16 != 0 and xo.is_contiguous()
         # (not compared bit for bit with the 16-byte path: the two assign columns to lanes differently, so the sums run in another order)
-        assert_contract(xo, w, go, f"offset {shape} {dtype}")
+        assert_contract(offset_by_one(x), w, offset_by_one(g), f"offset {shape} {dtype}")
+
+
+# ---- the register ladder (tests/row_ladder_cases.py): SHAPES holds the wave path's quarter rung alone -------------------------------------------
+
+LADDER = [(C.rows_of(c), c) for c in C.rms_new_cols(torch.float32)]      # both ends of the wave path's three rungs, the workgroup's full rung filled
+LADDER_OFFSET = [(5, 1025)]                                              # the element path's second sweep of a wave, one column in it
+
+
+@pytest.mark.parametrize("shape", LADDER, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_every_rung_of_the_ladder_with_a_seeded_row(shape):
+    """row 0 holds its largest magnitudes in column 0, in the last column and at the start of the last sweep: a slot past the row that is
+    counted, or a last group that is not, moves rstd far beyond its cap (tests/test_row_ladder_cases_cpu.py)"""
+    x, w, g = C.rms_inputs(shape[1], shape[0])
+    for dtype in DTYPES:
+        assert_contract(x.to(dtype).cuda(), w.to(dtype).cuda(), g.to(dtype).cuda(), f"ladder {shape} {dtype}")
+    if shape[1] == 1032:
+        for xdt, wdt in MIXED:
+            assert_contract(x.to(xdt).cuda(), w.to(wdt).cuda(), g.to(wdt).cuda(), f"ladder {shape} x {xdt} w {wdt}")
+
+
+@pytest.mark.parametrize("shape", LADDER_OFFSET, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_seeded_row_at_a_base_offset_of_one_element(shape):
+    x, w, g = C.rms_inputs(shape[1], shape[0])
+    for dtype in DTYPES:
+        assert_contract(offset_by_one(x.to(dtype).cuda()), w.to(dtype).cuda(), offset_by_one(g.to(dtype).cuda()), f"ladder offset {shape} {dtype}")
 
 
 # ---- the caps ------------------------------------------------------------------------------------------------------------------------------------
