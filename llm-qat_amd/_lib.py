@@ -49,6 +49,8 @@ ACT_EXPORTS = ("fqa_swiglu_fwd", "fqa_swiglu_bwd")
 ROPE_EXPORTS = ("fqr_rope_dense_strides", "fqr_rope_fwd", "fqr_rope_bwd")
 # every symbol include/llmqat_fakequant_attn.h declares (the fqs2_ family: the softmax chain between the two attention products)
 ATTN_EXPORTS = ("fqs2_attn_softmax_fwd", "fqs2_attn_softmax_bwd")
+# every symbol include/llmqat_fakequant_attn_decode.h declares (the fqd_ family: the fused attention of a few new tokens over a cache)
+DECODE_EXPORTS = ("fqd_attn_decode_workspace", "fqd_attn_decode_fwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -211,6 +213,10 @@ def _bind(L):
     L.fqs2_attn_softmax_fwd.restype = i32
     L.fqs2_attn_softmax_bwd.argtypes = [vp] * 5 + [i64] * 7 + [f32, i32, i32, vp]
     L.fqs2_attn_softmax_bwd.restype = i32
+    L.fqd_attn_decode_workspace.argtypes = [i64] * 6 + [i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.fqd_attn_decode_workspace.restype = i32
+    L.fqd_attn_decode_fwd.argtypes = [vp] * 6 + [sz] + [i64] * 17 + [f32, i32, i32, vp]
+    L.fqd_attn_decode_fwd.restype = i32
     return L
 
 

@@ -12,12 +12,15 @@ but the scores, the mask and two floats per row.
     from llm_qat_amd.attention import attn_softmax, convert, install
     previous = install(models.modeling_llama_quant)    # no edit: models built from now on use the fused forward
     convert(teacher)                                   # an existing model, in place
+
+decode_attention fuses the two products as well where a few new tokens (T <= 16) attend to a long cache and no gradient is asked for
+(DESIGN.md section 30): one stream over k and v.  install(..., decode=True) / convert(..., decode=True) route such calls to it.
 """
 import torch
 
 from . import compiled, cpu_tensors, ops
 
-__all__ = ["attn_softmax", "install", "convert"]
+__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention is public by name
 
 
 class _AttnSoftmax(torch.autograd.Function):
@@ -63,9 +66,47 @@ def attn_softmax(scores, attention_mask=None, head_dim=None, *, scale=None):
     return _AttnSoftmax.apply(scores, attention_mask, geom, need)
 
 
-def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False):
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def decode_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None):
+    """softmax(max(q k^T / sqrt(head_dim) + attention_mask, finfo.min), -1, float32) v for a few query rows over many keys, fused: the
+    scores never exist in memory, k and v are read once.  The chain's roundings stand in front of the softmax as in attn_softmax (the
+    first product rounded to the dtype, the product with the fp32 reciprocal of sqrt(head_dim), the sum with the mask in the promoted
+    dtype, the clamp under a mask only); the softmax is online in fp32 and the unnormalised exponentials are the second product's
+    operand, so the result is held to an error bound against float64 beside the composed path's own, not to its bits.
+
+    q: [B, H, T, D] with T <= 16 and D of 64 or 128; k, v: [B, H, S, D]; all three bfloat16 or all three float16, on a CUDA device, read
+    where they lie (the transposed views of a projection, a concatenation with a cache); attention_mask: None, or [B, 1, T, S] /
+    [1, 1, T, S] in their dtype or float32.  Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory, so that
+    .transpose(1, 2).reshape(B, T, H * D) is a view.  Forward only: a call in which a gradient is required raises.  CPU tensors are
+    refused unless llm_qat_amd.allow_cpu_tensors(True): then the chain runs in torch ops."""
+    B, H, T, S, D, inv = ops.check_attn_decode(q, k, v, attention_mask, head_dim, scale, "decode_attention")
+    if _needs_grad(q, k, v, attention_mask):
+        raise RuntimeError("decode_attention: forward only, but an input requires grad: call it under torch.no_grad(), detach the inputs, "
+                           "or use the products around attn_softmax, which have a backward")
+    if q.device.type == "cpu":
+        if not cpu_tensors.ENABLED:
+            cpu_tensors.refuse(q, "decode_attention")
+        return cpu_tensors.attn_decode(q, k, v, attention_mask, head_dim, scale)
+    if torch.compiler.is_compiling():
+        return compiled.attn_decode(q, k, v, attention_mask, inv).transpose(1, 2)
+    return ops.attn_decode_forward(q, k, v, attention_mask, scale=inv).transpose(1, 2)
+
+
+def _decode_serves(q, k, v, attention_mask, t, hd, output_attentions):
+    return (not output_attentions and t <= ops.DECODE_MAX_T and hd in ops.DECODE_HEAD_DIMS and q.dtype in (torch.bfloat16, torch.float16)
+            and k.dtype == q.dtype and v.dtype == q.dtype and q.device.type == "cuda" and k.device == q.device and v.device == q.device
+            and (attention_mask is None or (attention_mask.dtype in (q.dtype, torch.float32) and attention_mask.device == q.device))
+            and not _needs_grad(q, k, v, attention_mask))
+
+
+def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False,
+             decode=False):
     """LlamaAttention.forward through the parent's attribute names, with attn_softmax between the two products.  lookup(): the rotary
-    function, found at call time where the parent's forward finds it."""
+    function, found at call time where the parent's forward finds it.  decode: calls that decode_attention serves go to it, the others
+    are counted (ops.decode_counts["fallback"]) and take the three calls."""
     b, t, _ = hidden_states.size()
     nh, hd = self.num_heads, self.head_dim
     q = self.q_proj(hidden_states).view(b, t, nh, hd).transpose(1, 2)
@@ -83,6 +124,13 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
         k = torch.cat([past_key_value[0], k], dim=2)
         v = torch.cat([past_key_value[1], v], dim=2)
     past_key_value = (k, v) if use_cache else None
+    if decode:
+        if _decode_serves(q, k, v, attention_mask, t, hd, output_attentions):
+            if attention_mask is not None and attention_mask.size() != (b, 1, t, s):
+                raise ValueError(f"Attention mask should be of size {(b, 1, t, s)}, but is {attention_mask.size()}")
+            out = decode_attention(q, k, v, attention_mask, hd)
+            return self.o_proj(out.transpose(1, 2).reshape(b, t, nh * hd)), None, past_key_value
+        ops.decode_counts["fallback"] += 1
     scores = torch.matmul(q, k.transpose(2, 3))
     if scores.size() != (b, nh, t, s):
         raise ValueError(f"Attention weights should be of size {(b, nh, t, s)}, but is {scores.size()}")
@@ -96,55 +144,59 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
     return out, (y if output_attentions else None), past_key_value
 
 
-def _fused_class(parent, names):
+def _fused_class(parent, names, decode=False):
     """a subclass of `parent` whose forward is _forward; names: the mapping in which apply_rotary_pos_emb is looked up at call time"""
     class LlamaAttention(parent):
         fused_attn_softmax = True
+        fused_attn_decode = decode
 
         def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False):
             return _forward(self, lambda: names["apply_rotary_pos_emb"], hidden_states, attention_mask, position_ids, past_key_value,
-                            output_attentions, use_cache)
+                            output_attentions, use_cache, decode)
 
     LlamaAttention.__qualname__ = LlamaAttention.__name__ = getattr(parent, "__name__", "LlamaAttention")
     LlamaAttention.__module__ = getattr(parent, "__module__", LlamaAttention.__module__)
     return LlamaAttention
 
 
-def install(namespace):
+def install(namespace, decode=False):
     """Replace the attribute LlamaAttention of a module object (the reference's models.modeling_llama_quant, whose decoder layers look
     the class up when they are built) with a subclass of it: the constructor, the parameters and the state_dict are the parent's; the
     forward runs the projections, the K / V hooks and the rotary call through the parent's names (apply_rotary_pos_emb is looked up in
     `namespace` at call time, so rope.install composes in either order), then the product, attn_softmax, the product and o_proj.
     past_key_value, use_cache and output_attentions are honoured (output_attentions returns the probabilities in the scores' dtype).
+    decode=True: a call with at most 16 new tokens, a head_dim of 64 or 128, q, k, v sharing bfloat16 or float16 on the device, no
+    output_attentions and no gradient to ask for goes to decode_attention; any other is counted in ops.decode_counts["fallback"].
     -> the previous attribute: assign it back to undo.  Models built before the call keep their attention: convert() re-classes those."""
     import types
     if not isinstance(namespace, types.ModuleType):
         raise TypeError(f"install: expected a module object (e.g. models.modeling_llama_quant), got {type(namespace).__name__}")
     previous = namespace.LlamaAttention
-    namespace.LlamaAttention = _fused_class(previous, vars(namespace))
+    namespace.LlamaAttention = _fused_class(previous, vars(namespace), bool(decode))
     return previous
 
 
 _NEEDS = ("q_proj", "k_proj", "v_proj", "o_proj", "rotary_emb", "num_heads", "head_dim")
-_converted = {}      # parent class -> its fused subclass: one per class, so that type(m) is shared by a model's layers
+_converted = {}      # (parent class, decode) -> its fused subclass: one per class, so that type(m) is shared by a model's layers
 
 
 def _is_attention(m):
     return not getattr(m, "fused_attn_softmax", False) and all(hasattr(m, n) for n in _NEEDS) and "apply_rotary_pos_emb" in getattr(type(m).forward, "__globals__", {})
 
 
-def convert(model):
+def convert(model, decode=False):
     """Re-class, in place, every module of `model` (itself included) that has q_proj, k_proj, v_proj, o_proj, rotary_emb, num_heads and
     head_dim, whose forward finds apply_rotary_pos_emb in its module, and that is not converted already: its class becomes the fused
-    subclass of its class, the object, its parameters and its state_dict keys stay.  -> the number re-classed."""
+    subclass of its class, the object, its parameters and its state_dict keys stay.  decode: as install's.  -> the number re-classed."""
     if not isinstance(model, torch.nn.Module):
         raise TypeError(f"convert: expected a torch.nn.Module, got {type(model).__name__}")
     n = 0
     for m in model.modules():
         if _is_attention(m):
             parent = type(m)
-            if parent not in _converted:
-                _converted[parent] = _fused_class(parent, parent.forward.__globals__)
-            m.__class__ = _converted[parent]
+            key = (parent, bool(decode))
+            if key not in _converted:
+                _converted[key] = _fused_class(parent, parent.forward.__globals__, bool(decode))
+            m.__class__ = _converted[key]
             n += 1
     return n

@@ -541,3 +541,20 @@ def attn_softmax(scores, mask, inv):
     """attention.attn_softmax while compiling; as in eager mode no stats are written when no gradient can be asked for"""
     need = torch.is_grad_enabled() and scores.requires_grad
     return attn_softmax_fwd_op(scores, mask, inv, need)[0]
+
+
+# ---- the fused decode attention (ops.attn_decode_forward, DESIGN.md section 30): out [B, T, H, D], forward only ------------------------------
+@torch.library.custom_op("llmqat_amd::attn_decode", mutates_args=(), device_types="cuda")
+def attn_decode_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], inv: float) -> torch.Tensor:
+    return ops.attn_decode_forward(q, k, v, mask, scale=inv)
+
+
+@attn_decode_op.register_fake
+def _(q, k, v, mask, inv):
+    B, H, T, _, D, _ = ops.check_attn_decode(q, k, v, mask, scale=inv)
+    return q.new_empty((B, T, H, D))
+
+
+def attn_decode(q, k, v, mask, inv):
+    """attention.decode_attention while compiling -> out [B, T, H, D]"""
+    return attn_decode_op(q, k, v, mask, inv)

@@ -106,3 +106,16 @@ def attn_softmax(scores, mask, head_dim=None, scale=None):
         attn = attn + mask
         attn = torch.max(attn, torch.tensor(torch.finfo(attn.dtype).min))
     return torch.nn.functional.softmax(attn, dim=-1, dtype=torch.float32).to(scores.dtype)
+
+
+def attn_decode(q, k, v, mask, head_dim=None, scale=None):
+    """both attention products of LlamaAttention.forward with the chain between them (models/modeling_llama_quant.py:345-377), in torch
+    ops, under decode_attention's contract: the chain's roundings up to the clamp, then the fp32 softmax kept in fp32, the second product
+    in float64 and ONE rounding to the dtype -> [B, H, T, D] as a view of [B, T, H, D] memory, as the device route returns it"""
+    attn = torch.matmul(q, k.transpose(2, 3))
+    attn = attn / math.sqrt(head_dim) if scale is None else attn * scale
+    if mask is not None:
+        attn = attn + mask
+        attn = torch.max(attn, torch.tensor(torch.finfo(attn.dtype).min))
+    p = torch.nn.functional.softmax(attn, dim=-1, dtype=torch.float32)
+    return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)

@@ -69,4 +69,30 @@ constexpr int MXC_TILE_STRIPS = 64;
 constexpr int MXC_WAVE_STRIPS = 16;
 constexpr int MXC_ROW_GROUPS = 4;
 
+// Work split of the decode attention (fq_attn_decode.h): a wave walks the keys in tiles of DEC_TILE (two 16-key score tiles, the k of one
+// PV matrix instruction), a workgroup of DEC_WAVES waves owns one contiguous chunk of a (batch, head)'s tiles, and the S axis is cut into
+// dec_nsplit chunks so that about DEC_WG_PER_CU workgroups per compute unit exist however small B * H is.  A chunk holds at least
+// DEC_MIN_TILES tiles (one per wave) unless S itself is shorter, at most DEC_MAX_SPLIT chunks exist, and none is empty: the count is
+// re-derived from the chunk's length.  cus <= 0: the MI355X's 256.
+constexpr int DEC_TILE = 32;
+constexpr int DEC_WAVES = 4;
+constexpr int DEC_MIN_TILES = 4;
+constexpr int DEC_MAX_SPLIT = 64;
+constexpr int DEC_WG_PER_CU = 2;
+constexpr int DEC_MAX_T = 16;
+inline int64_t dec_tiles(int64_t S) { return (S + DEC_TILE - 1) / DEC_TILE; }
+// tiles of one chunk
+inline int64_t dec_chunk_tiles(int64_t bh, int64_t S, int64_t cus) {
+    const int64_t nt = dec_tiles(S), wgs = (cus > 0 ? cus : 256) * DEC_WG_PER_CU;
+    int64_t n = (wgs + bh - 1) / bh;                                        // chunks wanted
+    const int64_t most = nt / DEC_MIN_TILES > 1 ? nt / DEC_MIN_TILES : 1;   // chunks S can fill
+    n = n < most ? n : most;
+    n = n < DEC_MAX_SPLIT ? n : DEC_MAX_SPLIT;
+    return (nt + n - 1) / n;
+}
+inline int64_t dec_nsplit(int64_t bh, int64_t S, int64_t cus) {
+    const int64_t per = dec_chunk_tiles(bh, S, cus);
+    return (dec_tiles(S) + per - 1) / per;
+}
+
 }  // namespace fq

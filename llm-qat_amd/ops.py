@@ -2112,3 +2112,80 @@ def attn_softmax_backward(g, scores, attention_mask, stats, head_dim=None, scale
     _lib.check(rc, "attn_softmax_backward")
     attn_counts["bwd_launch"] += 1
     return dx
+
+
+# ---- the fused decode attention (the fqd_ header) ------------------------------------------------------------------------
+decode_counts = {"fwd_launch": 0, "copy_route": 0, "fallback": 0}
+DECODE_MAX_T = 16
+DECODE_HEAD_DIMS = (64, 128)
+_DECODE_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def check_attn_decode(q, k, v, attention_mask=None, head_dim=None, scale=None, what="attn_decode_forward"):
+    """The argument checks of the decode attention on types, shapes, dtypes and devices alone (the fake implementation of the compiled op
+    runs them too) -> (B, H, T, S, D, inv): TypeError for a non-tensor, q / k / v that do not share bfloat16 or float16, a mask whose dtype
+    is neither theirs nor float32, a head_dim / scale of the wrong type or both or neither; ValueError for a q that is not a non-empty
+    [B, H, T, D] with T <= 16 and D of 64 or 128, k / v that are not one non-empty [B, H, S, D], a mask that is not [B, 1, T, S] or
+    [1, 1, T, S], tensors on two devices."""
+    _row_tensors(what, q=q, k=k, v=v)
+    if attention_mask is not None:
+        _row_tensors(what, attention_mask=attention_mask)
+    if q.dtype not in _DECODE_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"{what}: q, k, v of {q.dtype}, {k.dtype}, {v.dtype} are not served: one of bfloat16, float16 for all three")
+    if attention_mask is not None and attention_mask.dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"{what}: a mask of dtype {attention_mask.dtype} beside q of {q.dtype} is not served: q's dtype or float32")
+    inv = attn_inv(head_dim, scale, what)
+    if q.dim() != 4 or q.numel() == 0 or q.shape[2] > DECODE_MAX_T or q.shape[3] not in DECODE_HEAD_DIMS:
+        raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with T <= {DECODE_MAX_T} and D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
+    B, H, T, D = q.shape
+    if k.dim() != 4 or k.shape[2] == 0 or tuple(k.shape) != (B, H, k.shape[2], D) or tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f"{what}: k and v are one non-empty [{B}, {H}, S, {D}], got {tuple(k.shape)} and {tuple(v.shape)}")
+    S = k.shape[2]
+    if attention_mask is not None and (attention_mask.dim() != 4 or tuple(attention_mask.shape[1:]) != (1, T, S) or attention_mask.shape[0] not in (1, B)):
+        raise ValueError(f"{what}: the mask is [{B}, 1, {T}, {S}] or [1, 1, {T}, {S}], got {tuple(attention_mask.shape)}")
+    for name, t in (("k", k), ("v", v), ("the mask", attention_mask)):
+        if t is not None and t.device != q.device:
+            raise ValueError(f"{what}: q is on {q.device}, {name} on {t.device}")
+    return B, H, T, S, D, inv
+
+
+def _decode_cus(t):
+    return torch.cuda.get_device_properties(t.device).multi_processor_count
+
+
+def attn_decode_workspace(B, H, T, D, S, cus, dtype=torch.bfloat16):
+    """-> (bytes, nsplit): the workspace fqd_attn_decode_fwd needs for this shape on a device of `cus` compute units, and the chunks it cuts S into"""
+    nbytes, nsplit = ctypes.c_size_t(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().fqd_attn_decode_workspace(B, H, T, D, S, cus, _OUT_DTYPES[dtype], ctypes.byref(nbytes), ctypes.byref(nsplit)), "attn_decode_workspace")
+    return nbytes.value, nsplit.value
+
+
+def attn_decode_forward(q, k, v, attention_mask=None, head_dim=None, scale=None):
+    """-> out [B, T, H, D] (contiguous; out.transpose(1, 2) is the [B, H, T, D] product): softmax(max(q k^T / sqrt(head_dim) + mask,
+    finfo.min), -1, float32) v for T <= 16 query rows as one stream over k and v, with the chain's roundings in front of the softmax and
+    an online fp32 softmax behind them.  q [B, H, T, D], k, v [B, H, S, D] in one of bfloat16, float16, D 64 or
+    128, read where they lie through their strides (a last stride that is not 1 is copied once: copy_route); the mask [B, 1, T, S] or
+    [1, 1, T, S] in their dtype or float32.  Forward only.  One launch, two where S is cut into chunks (fwd_launch counts calls)."""
+    B, H, T, S, D, inv = check_attn_decode(q, k, v, attention_mask, head_dim, scale)
+    _prep(q, "attn_decode_forward")
+    served = []
+    for t in (q.detach(), k.detach(), v.detach()):
+        if t.stride(-1) != 1:
+            decode_counts["copy_route"] += 1
+            t = t.contiguous()
+        served.append(t)
+    q, k, v = served
+    if attention_mask is not None and attention_mask.stride(-1) != 1 and S > 1:      # counted here: attn_counts is the softmax's
+        decode_counts["copy_route"] += 1
+        attention_mask = attention_mask.contiguous()
+    mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
+    cus = _decode_cus(q)
+    nbytes, _ = attn_decode_workspace(B, H, T, D, S, cus, q.dtype)
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if nbytes else None
+    rc = _launch(q, _lib.lib().fqd_attn_decode_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
+                 out.data_ptr(), ws.data_ptr() if nbytes else None, nbytes, *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], mbs, mrs,
+                 B, H, T, S, D, cus, inv, _OUT_DTYPES[q.dtype], mcode)
+    _lib.check(rc, "attn_decode_forward")
+    decode_counts["fwd_launch"] += 1
+    return out
