@@ -51,6 +51,8 @@ ROPE_EXPORTS = ("fqr_rope_dense_strides", "fqr_rope_fwd", "fqr_rope_bwd")
 ATTN_EXPORTS = ("fqs2_attn_softmax_fwd", "fqs2_attn_softmax_bwd")
 # every symbol include/llmqat_fakequant_attn_decode.h declares (the fqd_ family: the fused attention of a few new tokens over a cache)
 DECODE_EXPORTS = ("fqd_attn_decode_workspace", "fqd_attn_decode_fwd")
+# every symbol include/llmqat_fakequant_attn_prefill.h declares (the fqp_ family: the fused attention of a whole sequence)
+PREFILL_EXPORTS = ("fqp_attn_prefill_fwd",)
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -217,6 +219,8 @@ def _bind(L):
     L.fqd_attn_decode_workspace.restype = i32
     L.fqd_attn_decode_fwd.argtypes = [vp] * 6 + [sz] + [i64] * 17 + [f32, i32, i32, vp]
     L.fqd_attn_decode_fwd.restype = i32
+    L.fqp_attn_prefill_fwd.argtypes = [vp] * 5 + [i64] * 16 + [f32, i32, i32, i32, vp]
+    L.fqp_attn_prefill_fwd.restype = i32
     return L
 
 

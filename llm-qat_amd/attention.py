@@ -15,12 +15,14 @@ but the scores, the mask and two floats per row.
 
 decode_attention fuses the two products as well where a few new tokens (T <= 16) attend to a long cache and no gradient is asked for
 (DESIGN.md section 30): one stream over k and v.  install(..., decode=True) / convert(..., decode=True) route such calls to it.
+prefill_attention is the same operation for any T, a whole sequence or a long chunk over a cache: the teacher's
+forward, an evaluation run, the prompt pass of generation.  install(..., prefill=True) / convert(..., prefill=True) route to it.
 """
 import torch
 
 from . import compiled, cpu_tensors, ops
 
-__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention is public by name
+__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention and prefill_attention are public by name
 
 
 class _AttnSoftmax(torch.autograd.Function):
@@ -95,18 +97,44 @@ def decode_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None)
     return ops.attn_decode_forward(q, k, v, attention_mask, scale=inv).transpose(1, 2)
 
 
-def _decode_serves(q, k, v, attention_mask, t, hd, output_attentions):
-    return (not output_attentions and t <= ops.DECODE_MAX_T and hd in ops.DECODE_HEAD_DIMS and q.dtype in (torch.bfloat16, torch.float16)
+def prefill_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None, causal=False):
+    """decode_attention's operation, arithmetic and contract for any number T of query rows, fused: a workgroup owns 128 query rows and
+    walks all keys, each tile of k and v staged once for its four waves; the scores never exist in memory, where the three calls write and
+    re-read a [B, H, T, S] tensor twice.
+
+    q: [B, H, T, D] with D of 64 or 128; k, v: [B, H, S, D]; all three bfloat16 or all three float16, on a CUDA device, read where they
+    lie; attention_mask: None, or [B, 1, T, S] / [1, 1, T, S] in their dtype or float32.  causal=True (no mask, T <= S): query row t
+    attends to the keys s <= S - T + t and to no others, which for finite scores is the additive causal mask's result; no mask is read
+    and the keys past a workgroup's last row are skipped.  Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory.
+    Forward only: a call in which a gradient is required raises.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True):
+    then the chain runs in torch ops."""
+    B, H, T, S, D, inv = ops.check_attn_prefill(q, k, v, attention_mask, head_dim, scale, causal, "prefill_attention")
+    if _needs_grad(q, k, v, attention_mask):
+        raise RuntimeError("prefill_attention: forward only, but an input requires grad: call it under torch.no_grad(), detach the inputs, "
+                           "or use the products around attn_softmax, which have a backward")
+    if q.device.type == "cpu":
+        if not cpu_tensors.ENABLED:
+            cpu_tensors.refuse(q, "prefill_attention")
+        return cpu_tensors.attn_prefill(q, k, v, attention_mask, head_dim, scale, causal)
+    if torch.compiler.is_compiling():
+        return compiled.attn_prefill(q, k, v, attention_mask, inv, causal).transpose(1, 2)
+    return ops.attn_prefill_forward(q, k, v, attention_mask, scale=inv, causal=causal).transpose(1, 2)
+
+
+def _fused_serves(q, k, v, attention_mask, hd, output_attentions):
+    return (not output_attentions and hd in ops.DECODE_HEAD_DIMS and q.dtype in (torch.bfloat16, torch.float16)
             and k.dtype == q.dtype and v.dtype == q.dtype and q.device.type == "cuda" and k.device == q.device and v.device == q.device
             and (attention_mask is None or (attention_mask.dtype in (q.dtype, torch.float32) and attention_mask.device == q.device))
             and not _needs_grad(q, k, v, attention_mask))
 
 
 def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False,
-             decode=False):
+             decode=False, prefill=False):
     """LlamaAttention.forward through the parent's attribute names, with attn_softmax between the two products.  lookup(): the rotary
     function, found at call time where the parent's forward finds it.  decode: calls that decode_attention serves go to it, the others
-    are counted (ops.decode_counts["fallback"]) and take the three calls."""
+    are counted (ops.decode_counts["fallback"]) and take the three calls.  prefill: calls that the decode route has not taken and
+    prefill_attention serves go to it; the others are counted in ops.prefill_counts["fallback"], and a call the prefill route serves is
+    a fallback of neither dict."""
     b, t, _ = hidden_states.size()
     nh, hd = self.num_heads, self.head_dim
     q = self.q_proj(hidden_states).view(b, t, nh, hd).transpose(1, 2)
@@ -124,13 +152,16 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
         k = torch.cat([past_key_value[0], k], dim=2)
         v = torch.cat([past_key_value[1], v], dim=2)
     past_key_value = (k, v) if use_cache else None
-    if decode:
-        if _decode_serves(q, k, v, attention_mask, t, hd, output_attentions):
+    if decode or prefill:
+        serves = _fused_serves(q, k, v, attention_mask, hd, output_attentions)
+        fused = decode_attention if decode and serves and t <= ops.DECODE_MAX_T else prefill_attention if prefill and serves else None
+        if fused is not None:
             if attention_mask is not None and attention_mask.size() != (b, 1, t, s):
                 raise ValueError(f"Attention mask should be of size {(b, 1, t, s)}, but is {attention_mask.size()}")
-            out = decode_attention(q, k, v, attention_mask, hd)
+            out = fused(q, k, v, attention_mask, hd)
             return self.o_proj(out.transpose(1, 2).reshape(b, t, nh * hd)), None, past_key_value
-        ops.decode_counts["fallback"] += 1
+        ops.decode_counts["fallback"] += int(decode)
+        ops.prefill_counts["fallback"] += int(prefill)
     scores = torch.matmul(q, k.transpose(2, 3))
     if scores.size() != (b, nh, t, s):
         raise ValueError(f"Attention weights should be of size {(b, nh, t, s)}, but is {scores.size()}")
@@ -144,22 +175,23 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
     return out, (y if output_attentions else None), past_key_value
 
 
-def _fused_class(parent, names, decode=False):
+def _fused_class(parent, names, decode=False, prefill=False):
     """a subclass of `parent` whose forward is _forward; names: the mapping in which apply_rotary_pos_emb is looked up at call time"""
     class LlamaAttention(parent):
         fused_attn_softmax = True
         fused_attn_decode = decode
+        fused_attn_prefill = prefill
 
         def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False):
             return _forward(self, lambda: names["apply_rotary_pos_emb"], hidden_states, attention_mask, position_ids, past_key_value,
-                            output_attentions, use_cache, decode)
+                            output_attentions, use_cache, decode, prefill)
 
     LlamaAttention.__qualname__ = LlamaAttention.__name__ = getattr(parent, "__name__", "LlamaAttention")
     LlamaAttention.__module__ = getattr(parent, "__module__", LlamaAttention.__module__)
     return LlamaAttention
 
 
-def install(namespace, decode=False):
+def install(namespace, decode=False, prefill=False):
     """Replace the attribute LlamaAttention of a module object (the reference's models.modeling_llama_quant, whose decoder layers look
     the class up when they are built) with a subclass of it: the constructor, the parameters and the state_dict are the parent's; the
     forward runs the projections, the K / V hooks and the rotary call through the parent's names (apply_rotary_pos_emb is looked up in
@@ -167,36 +199,38 @@ def install(namespace, decode=False):
     past_key_value, use_cache and output_attentions are honoured (output_attentions returns the probabilities in the scores' dtype).
     decode=True: a call with at most 16 new tokens, a head_dim of 64 or 128, q, k, v sharing bfloat16 or float16 on the device, no
     output_attentions and no gradient to ask for goes to decode_attention; any other is counted in ops.decode_counts["fallback"].
+    prefill=True: a call that meets the same conditions but for the number of tokens, and that the decode route has not taken, goes to
+    prefill_attention with the module's mask (causality is never assumed); any other is counted in ops.prefill_counts["fallback"].
     -> the previous attribute: assign it back to undo.  Models built before the call keep their attention: convert() re-classes those."""
     import types
     if not isinstance(namespace, types.ModuleType):
         raise TypeError(f"install: expected a module object (e.g. models.modeling_llama_quant), got {type(namespace).__name__}")
     previous = namespace.LlamaAttention
-    namespace.LlamaAttention = _fused_class(previous, vars(namespace), bool(decode))
+    namespace.LlamaAttention = _fused_class(previous, vars(namespace), bool(decode), bool(prefill))
     return previous
 
 
 _NEEDS = ("q_proj", "k_proj", "v_proj", "o_proj", "rotary_emb", "num_heads", "head_dim")
-_converted = {}      # (parent class, decode) -> its fused subclass: one per class, so that type(m) is shared by a model's layers
+_converted = {}      # (parent class, decode, prefill) -> its fused subclass: one per class, so that type(m) is shared by a model's layers
 
 
 def _is_attention(m):
     return not getattr(m, "fused_attn_softmax", False) and all(hasattr(m, n) for n in _NEEDS) and "apply_rotary_pos_emb" in getattr(type(m).forward, "__globals__", {})
 
 
-def convert(model, decode=False):
+def convert(model, decode=False, prefill=False):
     """Re-class, in place, every module of `model` (itself included) that has q_proj, k_proj, v_proj, o_proj, rotary_emb, num_heads and
     head_dim, whose forward finds apply_rotary_pos_emb in its module, and that is not converted already: its class becomes the fused
-    subclass of its class, the object, its parameters and its state_dict keys stay.  decode: as install's.  -> the number re-classed."""
+    subclass of its class, the object, its parameters and its state_dict keys stay.  decode, prefill: as install's.  -> the number re-classed."""
     if not isinstance(model, torch.nn.Module):
         raise TypeError(f"convert: expected a torch.nn.Module, got {type(model).__name__}")
     n = 0
     for m in model.modules():
         if _is_attention(m):
             parent = type(m)
-            key = (parent, bool(decode))
+            key = (parent, bool(decode), bool(prefill))
             if key not in _converted:
-                _converted[key] = _fused_class(parent, parent.forward.__globals__, bool(decode))
+                _converted[key] = _fused_class(parent, parent.forward.__globals__, bool(decode), bool(prefill))
             m.__class__ = _converted[key]
             n += 1
     return n

@@ -558,3 +558,20 @@ def _(q, k, v, mask, inv):
 def attn_decode(q, k, v, mask, inv):
     """attention.decode_attention while compiling -> out [B, T, H, D]"""
     return attn_decode_op(q, k, v, mask, inv)
+
+
+# ---- the fused prefill attention (ops.attn_prefill_forward, DESIGN.md section 31): out [B, T, H, D], forward only -----------------------------
+@torch.library.custom_op("llmqat_amd::attn_prefill", mutates_args=(), device_types="cuda")
+def attn_prefill_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], inv: float, causal: bool) -> torch.Tensor:
+    return ops.attn_prefill_forward(q, k, v, mask, scale=inv, causal=causal)
+
+
+@attn_prefill_op.register_fake
+def _(q, k, v, mask, inv, causal):
+    B, H, T, _, D, _ = ops.check_attn_prefill(q, k, v, mask, scale=inv, causal=causal)
+    return q.new_empty((B, T, H, D))
+
+
+def attn_prefill(q, k, v, mask, inv, causal):
+    """attention.prefill_attention while compiling -> out [B, T, H, D]"""
+    return attn_prefill_op(q, k, v, mask, inv, causal)

@@ -119,3 +119,16 @@ def attn_decode(q, k, v, mask, head_dim=None, scale=None):
         attn = torch.max(attn, torch.tensor(torch.finfo(attn.dtype).min))
     p = torch.nn.functional.softmax(attn, dim=-1, dtype=torch.float32)
     return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)
+
+
+def attn_prefill(q, k, v, mask, head_dim=None, scale=None, causal=False):
+    """attn_decode for any T, under prefill_attention's contract; causal: the keys past S - T + t of row t get weight exactly 0 (-inf in
+    front of the softmax) and the others go through the chain without a mask"""
+    if not causal:
+        return attn_decode(q, k, v, mask, head_dim, scale)
+    T, S = q.shape[2], k.shape[2]
+    attn = torch.matmul(q, k.transpose(2, 3))
+    attn = attn / math.sqrt(head_dim) if scale is None else attn * scale
+    hidden = torch.arange(S)[None] > (S - T + torch.arange(T))[:, None]
+    p = torch.nn.functional.softmax(attn.float().masked_fill(hidden, float("-inf")), dim=-1)
+    return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)

@@ -95,4 +95,17 @@ inline int64_t dec_nsplit(int64_t bh, int64_t S, int64_t cus) {
     return (dec_tiles(S) + per - 1) / per;
 }
 
+// Work split of the prefill attention (fq_attn_prefill.h): grid (pre_query_tiles(T), B * H).  A workgroup of PRE_WAVES waves owns PRE_QT
+// query rows, PRE_RPW of them per wave (a multiple of 16: the B operands that share every K and V fragment), and walks all S keys in
+// tiles of PRE_KT; there is no split along S.  PRE_RPW is an A/B macro (DESIGN.md section 31 has 16 against 32).
+#ifndef PRE_RPW
+#define PRE_RPW 32
+#endif
+constexpr int PRE_WAVES = 4;
+constexpr int PRE_KT = 32;
+constexpr int PRE_QT = PRE_WAVES * PRE_RPW;
+constexpr int64_t PRE_MAX_GRID_Y = 65535;
+static_assert(PRE_RPW == 16 || PRE_RPW == 32, "one or two 16-row blocks a wave");
+inline int64_t pre_query_tiles(int64_t T) { return (T + PRE_QT - 1) / PRE_QT; }
+
 }  // namespace fq

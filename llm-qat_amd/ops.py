@@ -2121,12 +2121,12 @@ DECODE_HEAD_DIMS = (64, 128)
 _DECODE_DTYPES = (torch.bfloat16, torch.float16)
 
 
-def check_attn_decode(q, k, v, attention_mask=None, head_dim=None, scale=None, what="attn_decode_forward"):
+def check_attn_decode(q, k, v, attention_mask=None, head_dim=None, scale=None, what="attn_decode_forward", max_t=DECODE_MAX_T):
     """The argument checks of the decode attention on types, shapes, dtypes and devices alone (the fake implementation of the compiled op
     runs them too) -> (B, H, T, S, D, inv): TypeError for a non-tensor, q / k / v that do not share bfloat16 or float16, a mask whose dtype
     is neither theirs nor float32, a head_dim / scale of the wrong type or both or neither; ValueError for a q that is not a non-empty
     [B, H, T, D] with T <= 16 and D of 64 or 128, k / v that are not one non-empty [B, H, S, D], a mask that is not [B, 1, T, S] or
-    [1, 1, T, S], tensors on two devices."""
+    [1, 1, T, S], tensors on two devices.  max_t=None: any T (check_attn_prefill)."""
     _row_tensors(what, q=q, k=k, v=v)
     if attention_mask is not None:
         _row_tensors(what, attention_mask=attention_mask)
@@ -2135,8 +2135,8 @@ def check_attn_decode(q, k, v, attention_mask=None, head_dim=None, scale=None, w
     if attention_mask is not None and attention_mask.dtype not in (q.dtype, torch.float32):
         raise TypeError(f"{what}: a mask of dtype {attention_mask.dtype} beside q of {q.dtype} is not served: q's dtype or float32")
     inv = attn_inv(head_dim, scale, what)
-    if q.dim() != 4 or q.numel() == 0 or q.shape[2] > DECODE_MAX_T or q.shape[3] not in DECODE_HEAD_DIMS:
-        raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with T <= {DECODE_MAX_T} and D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
+    if q.dim() != 4 or q.numel() == 0 or (max_t is not None and q.shape[2] > max_t) or q.shape[3] not in DECODE_HEAD_DIMS:
+        raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with {'' if max_t is None else f'T <= {max_t} and '}D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
     B, H, T, D = q.shape
     if k.dim() != 4 or k.shape[2] == 0 or tuple(k.shape) != (B, H, k.shape[2], D) or tuple(v.shape) != tuple(k.shape):
         raise ValueError(f"{what}: k and v are one non-empty [{B}, {H}, S, {D}], got {tuple(k.shape)} and {tuple(v.shape)}")
@@ -2188,4 +2188,51 @@ def attn_decode_forward(q, k, v, attention_mask=None, head_dim=None, scale=None)
                  B, H, T, S, D, cus, inv, _OUT_DTYPES[q.dtype], mcode)
     _lib.check(rc, "attn_decode_forward")
     decode_counts["fwd_launch"] += 1
+    return out
+
+
+# ---- the fused prefill attention (the fqp_ header) -----------------------------------------------------------------------
+prefill_counts = {"fwd_launch": 0, "copy_route": 0, "fallback": 0}
+PREFILL_QT, PREFILL_KT = 128, 32      # csrc/fq_shapes.h PRE_QT, PRE_KT: query rows of a workgroup, keys of a tile (the tests' boundaries)
+
+
+def check_attn_prefill(q, k, v, attention_mask=None, head_dim=None, scale=None, causal=False, what="attn_prefill_forward"):
+    """check_attn_decode's checks without the limit on T -> (B, H, T, S, D, inv), and: TypeError for a causal that is not a bool;
+    ValueError for causal together with a mask or with T > S."""
+    geom = check_attn_decode(q, k, v, attention_mask, head_dim, scale, what, max_t=None)
+    if not isinstance(causal, bool):
+        raise TypeError(f"{what}: causal is a bool, got {type(causal).__name__}")
+    if causal and attention_mask is not None:
+        raise ValueError(f"{what}: causal=True reads no mask: give one of them")
+    if causal and geom[2] > geom[3]:
+        raise ValueError(f"{what}: causal=True takes the T = {geom[2]} query rows for the last of the S = {geom[3]} keys, so T <= S")
+    return geom
+
+
+def attn_prefill_forward(q, k, v, attention_mask=None, head_dim=None, scale=None, causal=False):
+    """-> out [B, T, H, D] (contiguous; out.transpose(1, 2) is the [B, H, T, D] product): attn_decode_forward's operation and arithmetic
+    for any T, as one kernel in which a workgroup owns 128 query rows and walks all keys: no [B, H, T, S] tensor
+    exists.  q [B, H, T, D], k, v [B, H, S, D] in one of bfloat16, float16, D 64 or 128, read where they lie through their strides (a
+    last stride that is not 1 is copied once: copy_route); the mask [B, 1, T, S] or [1, 1, T, S] in their dtype or float32.
+    causal=True (no mask, T <= S): row t attends to keys s <= S - T + t; nothing is read for it and key tiles past a workgroup's last
+    row are skipped.  Forward only.  One launch (fwd_launch)."""
+    B, H, T, S, D, inv = check_attn_prefill(q, k, v, attention_mask, head_dim, scale, causal)
+    _prep(q, "attn_prefill_forward")
+    served = []
+    for t in (q.detach(), k.detach(), v.detach()):
+        if t.stride(-1) != 1:
+            prefill_counts["copy_route"] += 1
+            t = t.contiguous()
+        served.append(t)
+    q, k, v = served
+    if attention_mask is not None and attention_mask.stride(-1) != 1 and S > 1:      # counted here: attn_counts is the softmax's
+        prefill_counts["copy_route"] += 1
+        attention_mask = attention_mask.contiguous()
+    mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    rc = _launch(q, _lib.lib().fqp_attn_prefill_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
+                 out.data_ptr(), *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], mbs, mrs, B, H, T, S, D, inv, _OUT_DTYPES[q.dtype], mcode,
+                 int(causal))
+    _lib.check(rc, "attn_prefill_forward")
+    prefill_counts["fwd_launch"] += 1
     return out
