@@ -53,6 +53,8 @@ ATTN_EXPORTS = ("fqs2_attn_softmax_fwd", "fqs2_attn_softmax_bwd")
 DECODE_EXPORTS = ("fqd_attn_decode_workspace", "fqd_attn_decode_fwd")
 # every symbol include/llmqat_fakequant_attn_prefill.h declares (the fqp_ family: the fused attention of a whole sequence)
 PREFILL_EXPORTS = ("fqp_attn_prefill_fwd",)
+# every symbol include/llmqat_fakequant_attn_train.h declares (the fqg_ family: the fused attention that has a gradient)
+ATTN_TRAIN_EXPORTS = ("fqg_attn_train_fwd", "fqg_attn_train_bwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -221,6 +223,10 @@ def _bind(L):
     L.fqd_attn_decode_fwd.restype = i32
     L.fqp_attn_prefill_fwd.argtypes = [vp] * 5 + [i64] * 16 + [f32, i32, i32, i32, vp]
     L.fqp_attn_prefill_fwd.restype = i32
+    L.fqg_attn_train_fwd.argtypes = [vp] * 6 + [i64] * 16 + [f32, i32, i32, i32, vp]
+    L.fqg_attn_train_fwd.restype = i32
+    L.fqg_attn_train_bwd.argtypes = [vp] * 11 + [i64] * 22 + [f32, i32, i32, i32, vp]
+    L.fqg_attn_train_bwd.restype = i32
     return L
 
 

@@ -17,12 +17,15 @@ decode_attention fuses the two products as well where a few new tokens (T <= 16)
 (DESIGN.md section 30): one stream over k and v.  install(..., decode=True) / convert(..., decode=True) route such calls to it.
 prefill_attention is the same operation for any T, a whole sequence or a long chunk over a cache: the teacher's
 forward, an evaluation run, the prompt pass of generation.  install(..., prefill=True) / convert(..., prefill=True) route to it.
+train_attention is prefill_attention with a gradient in q, k and v: the student's call.  Its backward recomputes the
+scores tile by tile from two floats per row, so no [B, H, T, S] tensor exists in either direction.  install(..., train=True) /
+convert(..., train=True) route the calls that need a gradient to it.
 """
 import torch
 
 from . import compiled, cpu_tensors, ops
 
-__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention and prefill_attention are public by name
+__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention, prefill_attention and train_attention are public by name
 
 
 class _AttnSoftmax(torch.autograd.Function):
@@ -121,20 +124,61 @@ def prefill_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None
     return ops.attn_prefill_forward(q, k, v, attention_mask, scale=inv, causal=causal).transpose(1, 2)
 
 
-def _fused_serves(q, k, v, attention_mask, hd, output_attentions):
+class _TrainAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, mask, inv, causal):
+        out, stats, (qs, ks, vs, mk) = ops.attn_train_forward(q, k, v, mask, scale=inv, causal=causal)
+        ctx.save_for_backward(qs, ks, vs, out, stats, *(() if mk is None else (mk,)))      # q, k, v, out, stats and the mask: nothing else
+        ctx.inv, ctx.causal = inv, causal
+        return out.transpose(1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, out, stats, *mask = ctx.saved_tensors
+        grads = ops.attn_train_backward(g, q, k, v, mask[0] if mask else None, out.transpose(1, 2), stats, scale=ctx.inv, causal=ctx.causal)
+        return (*(d.transpose(1, 2) if need else None for d, need in zip(grads, ctx.needs_input_grad)), None, None, None)
+
+
+def train_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None, causal=False):
+    """prefill_attention's operation, arithmetic and contract, differentiable in q, k and v.  The forward is
+    prefill_attention's kernel, to the bit, and also writes the maximum and the sum of every query row (an fp32 [B, H, T, 2]); the backward
+    is two kernels that recompute the scores and the probabilities tile by tile from those, q, k, v and the mask, so the only tensors saved
+    are q, k, v, the mask, out and that pair, and no [B, H, T, S] tensor exists.  The gradient is the chain's: straight through its
+    roundings, torch.max's rule at the clamp (a tie, which is every key of a fully masked row, gets half), held to an error bound against
+    float64 beside the composed path's own, not to its bits.  No atomics: two backward calls give the same bits.
+
+    q: [B, H, T, D] with D of 64 or 128; k, v: [B, H, S, D]; all three bfloat16 or all three float16, on a CUDA device, read where they
+    lie; attention_mask: None, or [B, 1, T, S] / [1, 1, T, S] in their dtype or float32, which must not require grad; causal=True (no
+    mask, T <= S) as prefill_attention's.  Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory; the gradients are
+    views of [B, T, H, D] / [B, S, H, D] memory likewise.  Under no_grad, or where nothing requires grad, nothing is saved and no row
+    statistics are written.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True): then the chain runs in torch ops."""
+    B, H, T, S, D, inv = ops.check_attn_train(q, k, v, attention_mask, head_dim, scale, causal, "train_attention")
+    if q.device.type == "cpu":
+        if not cpu_tensors.ENABLED:
+            cpu_tensors.refuse(q, "train_attention")
+        return cpu_tensors.attn_train(q, k, v, attention_mask, inv, causal)
+    if torch.compiler.is_compiling():
+        return compiled.attn_train(q, k, v, attention_mask, inv, causal).transpose(1, 2)
+    if not _needs_grad(q, k, v):
+        return ops.attn_train_forward(q, k, v, attention_mask, scale=inv, causal=causal, need_stats=False)[0].transpose(1, 2)
+    return _TrainAttention.apply(q, k, v, attention_mask, inv, causal)
+
+
+def _fused_serves(q, k, v, attention_mask, hd, output_attentions, grad=False):
     return (not output_attentions and hd in ops.DECODE_HEAD_DIMS and q.dtype in (torch.bfloat16, torch.float16)
             and k.dtype == q.dtype and v.dtype == q.dtype and q.device.type == "cuda" and k.device == q.device and v.device == q.device
             and (attention_mask is None or (attention_mask.dtype in (q.dtype, torch.float32) and attention_mask.device == q.device))
-            and not _needs_grad(q, k, v, attention_mask))
+            and _needs_grad(q, k, v, attention_mask) == grad and not (grad and attention_mask is not None and attention_mask.requires_grad))
 
 
 def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False,
-             decode=False, prefill=False):
+             decode=False, prefill=False, train=False):
     """LlamaAttention.forward through the parent's attribute names, with attn_softmax between the two products.  lookup(): the rotary
     function, found at call time where the parent's forward finds it.  decode: calls that decode_attention serves go to it, the others
     are counted (ops.decode_counts["fallback"]) and take the three calls.  prefill: calls that the decode route has not taken and
     prefill_attention serves go to it; the others are counted in ops.prefill_counts["fallback"], and a call the prefill route serves is
-    a fallback of neither dict."""
+    a fallback of neither dict.  train: a call that needs a gradient and that train_attention serves goes to it; any other call that needs
+    one is counted in ops.train_counts["fallback"]."""
     b, t, _ = hidden_states.size()
     nh, hd = self.num_heads, self.head_dim
     q = self.q_proj(hidden_states).view(b, t, nh, hd).transpose(1, 2)
@@ -162,6 +206,13 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
             return self.o_proj(out.transpose(1, 2).reshape(b, t, nh * hd)), None, past_key_value
         ops.decode_counts["fallback"] += int(decode)
         ops.prefill_counts["fallback"] += int(prefill)
+    if train and _needs_grad(q, k, v, attention_mask):
+        if _fused_serves(q, k, v, attention_mask, hd, output_attentions, grad=True):
+            if attention_mask is not None and attention_mask.size() != (b, 1, t, s):
+                raise ValueError(f"Attention mask should be of size {(b, 1, t, s)}, but is {attention_mask.size()}")
+            out = train_attention(q, k, v, attention_mask, hd)
+            return self.o_proj(out.transpose(1, 2).reshape(b, t, nh * hd)), None, past_key_value
+        ops.train_counts["fallback"] += 1
     scores = torch.matmul(q, k.transpose(2, 3))
     if scores.size() != (b, nh, t, s):
         raise ValueError(f"Attention weights should be of size {(b, nh, t, s)}, but is {scores.size()}")
@@ -175,23 +226,24 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
     return out, (y if output_attentions else None), past_key_value
 
 
-def _fused_class(parent, names, decode=False, prefill=False):
+def _fused_class(parent, names, decode=False, prefill=False, train=False):
     """a subclass of `parent` whose forward is _forward; names: the mapping in which apply_rotary_pos_emb is looked up at call time"""
     class LlamaAttention(parent):
         fused_attn_softmax = True
         fused_attn_decode = decode
         fused_attn_prefill = prefill
+        fused_attn_train = train
 
         def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False):
             return _forward(self, lambda: names["apply_rotary_pos_emb"], hidden_states, attention_mask, position_ids, past_key_value,
-                            output_attentions, use_cache, decode, prefill)
+                            output_attentions, use_cache, decode, prefill, train)
 
     LlamaAttention.__qualname__ = LlamaAttention.__name__ = getattr(parent, "__name__", "LlamaAttention")
     LlamaAttention.__module__ = getattr(parent, "__module__", LlamaAttention.__module__)
     return LlamaAttention
 
 
-def install(namespace, decode=False, prefill=False):
+def install(namespace, decode=False, prefill=False, train=False):
     """Replace the attribute LlamaAttention of a module object (the reference's models.modeling_llama_quant, whose decoder layers look
     the class up when they are built) with a subclass of it: the constructor, the parameters and the state_dict are the parent's; the
     forward runs the projections, the K / V hooks and the rotary call through the parent's names (apply_rotary_pos_emb is looked up in
@@ -201,36 +253,38 @@ def install(namespace, decode=False, prefill=False):
     output_attentions and no gradient to ask for goes to decode_attention; any other is counted in ops.decode_counts["fallback"].
     prefill=True: a call that meets the same conditions but for the number of tokens, and that the decode route has not taken, goes to
     prefill_attention with the module's mask (causality is never assumed); any other is counted in ops.prefill_counts["fallback"].
+    train=True: a call that needs a gradient and meets the other conditions goes to train_attention with the module's mask; any other call
+    that needs a gradient is counted in ops.train_counts["fallback"] and takes the three calls.
     -> the previous attribute: assign it back to undo.  Models built before the call keep their attention: convert() re-classes those."""
     import types
     if not isinstance(namespace, types.ModuleType):
         raise TypeError(f"install: expected a module object (e.g. models.modeling_llama_quant), got {type(namespace).__name__}")
     previous = namespace.LlamaAttention
-    namespace.LlamaAttention = _fused_class(previous, vars(namespace), bool(decode), bool(prefill))
+    namespace.LlamaAttention = _fused_class(previous, vars(namespace), bool(decode), bool(prefill), bool(train))
     return previous
 
 
 _NEEDS = ("q_proj", "k_proj", "v_proj", "o_proj", "rotary_emb", "num_heads", "head_dim")
-_converted = {}      # (parent class, decode, prefill) -> its fused subclass: one per class, so that type(m) is shared by a model's layers
+_converted = {}      # (parent class, decode, prefill, train) -> its fused subclass: one per class, so that type(m) is shared by a model's layers
 
 
 def _is_attention(m):
     return not getattr(m, "fused_attn_softmax", False) and all(hasattr(m, n) for n in _NEEDS) and "apply_rotary_pos_emb" in getattr(type(m).forward, "__globals__", {})
 
 
-def convert(model, decode=False, prefill=False):
+def convert(model, decode=False, prefill=False, train=False):
     """Re-class, in place, every module of `model` (itself included) that has q_proj, k_proj, v_proj, o_proj, rotary_emb, num_heads and
     head_dim, whose forward finds apply_rotary_pos_emb in its module, and that is not converted already: its class becomes the fused
-    subclass of its class, the object, its parameters and its state_dict keys stay.  decode, prefill: as install's.  -> the number re-classed."""
+    subclass of its class, the object, its parameters and its state_dict keys stay.  decode, prefill, train: as install's.  -> the number re-classed."""
     if not isinstance(model, torch.nn.Module):
         raise TypeError(f"convert: expected a torch.nn.Module, got {type(model).__name__}")
     n = 0
     for m in model.modules():
         if _is_attention(m):
             parent = type(m)
-            key = (parent, bool(decode), bool(prefill))
+            key = (parent, bool(decode), bool(prefill), bool(train))
             if key not in _converted:
-                _converted[key] = _fused_class(parent, parent.forward.__globals__, bool(decode), bool(prefill))
+                _converted[key] = _fused_class(parent, parent.forward.__globals__, bool(decode), bool(prefill), bool(train))
             m.__class__ = _converted[key]
             n += 1
     return n

@@ -575,3 +575,50 @@ def _(q, k, v, mask, inv, causal):
 def attn_prefill(q, k, v, mask, inv, causal):
     """attention.prefill_attention while compiling -> out [B, T, H, D]"""
     return attn_prefill_op(q, k, v, mask, inv, causal)
+
+
+# ---- the fused training attention (ops.attn_train_forward / ops.attn_train_backward, DESIGN.md section 32): (out [B, T, H, D], stats) and (dq, dk, dv)
+@torch.library.custom_op("llmqat_amd::attn_train_fwd", mutates_args=(), device_types="cuda")
+def attn_train_fwd_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], inv: float, causal: bool,
+                      need_stats: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    out, stats, _ = ops.attn_train_forward(q, k, v, mask, scale=inv, causal=causal, need_stats=need_stats)
+    return out, (stats if need_stats else q.new_empty((0, 2), dtype=torch.float32))      # an op returns tensors: an empty one for "not written"
+
+
+@attn_train_fwd_op.register_fake
+def _(q, k, v, mask, inv, causal, need_stats):
+    B, H, T, _, D, _ = ops.check_attn_train(q, k, v, mask, scale=inv, causal=causal)
+    return q.new_empty((B, T, H, D)), q.new_empty((B, H, T, 2) if need_stats else (0, 2), dtype=torch.float32)
+
+
+@torch.library.custom_op("llmqat_amd::attn_train_bwd", mutates_args=(), device_types="cuda")
+def attn_train_bwd_op(g: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor,
+                      stats: torch.Tensor, inv: float, causal: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.attn_train_backward(g.transpose(1, 2), q, k, v, mask, out.transpose(1, 2), stats, scale=inv, causal=causal)
+
+
+@attn_train_bwd_op.register_fake
+def _(g, q, k, v, mask, out, stats, inv, causal):
+    B, H, T, S, D, _ = ops.check_attn_train(q, k, v, mask, scale=inv, causal=causal)
+    return q.new_empty((B, T, H, D)), q.new_empty((B, S, H, D)), q.new_empty((B, S, H, D))
+
+
+def _attn_train_setup(ctx, inputs, output):
+    q, k, v, mask, inv, causal, _ = inputs
+    ctx.save_for_backward(q, k, v, output[0], output[1], *(() if mask is None else (mask,)))      # q, k, v, out, stats and the mask alone
+    ctx.inv, ctx.causal = inv, causal
+
+
+def _attn_train_backward(ctx, grad_out, grad_stats):
+    q, k, v, out, stats, *mask = ctx.saved_tensors
+    grads = attn_train_bwd_op(grad_out, q, k, v, mask[0] if mask else None, out, stats, ctx.inv, ctx.causal)      # all [B, T | S, H, D]
+    return (*(d.transpose(1, 2) if need else None for d, need in zip(grads, ctx.needs_input_grad)), None, None, None, None)
+
+
+attn_train_fwd_op.register_autograd(_attn_train_backward, setup_context=_attn_train_setup)
+
+
+def attn_train(q, k, v, mask, inv, causal):
+    """attention.train_attention while compiling -> out [B, T, H, D]; as in eager mode no stats are written when no gradient can be asked for"""
+    need = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
+    return attn_train_fwd_op(q, k, v, mask, inv, causal, need)[0]

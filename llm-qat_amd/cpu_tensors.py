@@ -132,3 +132,23 @@ def attn_prefill(q, k, v, mask, head_dim=None, scale=None, causal=False):
     hidden = torch.arange(S)[None] > (S - T + torch.arange(T))[:, None]
     p = torch.nn.functional.softmax(attn.float().masked_fill(hidden, float("-inf")), dim=-1)
     return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)
+
+
+def _ste(x, dtype):
+    """x rounded to `dtype`, in x's own (float64) dtype, with the gradient of the identity"""
+    return x + (x.to(dtype).to(x.dtype) - x).detach()
+
+
+def attn_train(q, k, v, mask, inv, causal=False):
+    """attn_prefill with a gradient, under train_attention's contract, differentiated by torch's autograd: the chain in float64 with
+    its roundings in front of the softmax applied straight through (the values are the rounded chain's, the derivative the unrounded
+    formula's), torch.max's own rule at the clamp, ONE rounding of the output and one of each gradient"""
+    T, S = q.shape[2], k.shape[2]
+    z = _ste(_ste(_ste(torch.matmul(q.double(), k.double().transpose(2, 3)), q.dtype) * inv, torch.float32), q.dtype)      # inv: the fp32 factor
+    if mask is not None:
+        P = torch.promote_types(q.dtype, mask.dtype)
+        z = torch.max(_ste(z + mask.double(), P), torch.tensor(torch.finfo(P).min, dtype=torch.float64))
+    if causal:
+        z = z.masked_fill(torch.arange(S)[None] > (S - T + torch.arange(T))[:, None], float("-inf"))
+    out = torch.matmul(torch.softmax(z, -1), v.double()).to(q.dtype)
+    return out.transpose(1, 2).contiguous().transpose(1, 2)

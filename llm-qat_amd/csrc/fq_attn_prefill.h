@@ -56,6 +56,7 @@ struct PreArgs {
     int64_t mbs, mrs;
     int64_t H, T, S;
     float inv;
+    float* stats;        // [B, H, T, 2]: (m, l) of each real row; read by the STATS instantiations alone (fq_attn_train.hip), nullptr: not written
 };
 
 // the mask of four consecutive keys from key0 (a multiple of 4) of the row at element `base`; keys past `last` repeat the last one's
@@ -86,8 +87,8 @@ template <int MDT, bool MVEC> __device__ __forceinline__ void pre_mask4(const vo
 template <int D> constexpr int pre_row_bytes() { return 2 * D + 16; }
 
 // MDT: the mask's dtype or ATTN_NOMASK; CAUSAL only beside ATTN_NOMASK.  RB: 16-row blocks of a wave.  VEC / MVEC: 16-byte loads of
-// q, k, v / vector loads of the mask
-template <int DT, int MDT, bool CAUSAL, int D, int RB, bool VEC, bool MVEC>
+// q, k, v / vector loads of the mask.  STATS: the row's maximum and the group-reduced sum go to a.stats behind the walk (the training forward)
+template <int DT, int MDT, bool CAUSAL, int D, int RB, bool VEC, bool MVEC, bool STATS = false>
 __global__ __launch_bounds__(PRE_WAVES * 64, 2) void pre_kernel(PreArgs a) {
     static_assert(D == 64 || D == 128, "head sizes served");
     static_assert(!CAUSAL || MDT == ATTN_NOMASK, "the causal mode reads no mask");
@@ -265,6 +266,12 @@ __global__ __launch_bounds__(PRE_WAVES * 64, 2) void pre_kernel(PreArgs a) {
             for (int db = 0; db < DB; ++db) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Ty<DT>::store1(a.out, o + 16 * db + r, acc[rb][db][r] / sum);
+            }
+            if constexpr (STATS) {
+                if (g == 0 && a.stats) {
+                    float* st = a.stats + 2 * ((b * a.H + h) * T + trow[rb]);
+                    st[0] = m[rb], st[1] = sum;
+                }
             }
         }
     }

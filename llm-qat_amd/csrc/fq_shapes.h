@@ -108,4 +108,23 @@ constexpr int64_t PRE_MAX_GRID_Y = 65535;
 static_assert(PRE_RPW == 16 || PRE_RPW == 32, "one or two 16-row blocks a wave");
 inline int64_t pre_query_tiles(int64_t T) { return (T + PRE_QT - 1) / PRE_QT; }
 
+// Work split of the training attention's backward (fq_attn_train.h): two launches.  The dq kernel has the forward's split: grid
+// (trn_query_tiles(T), B * H), a workgroup of TRN_WAVES waves owns TRN_DQ_QT query rows, TRN_RPW of them per wave, and walks the keys
+// in tiles of TRN_DQ_KT.  The dk/dv kernel is its mirror: grid (trn_key_tiles(S), B * H), a workgroup owns TRN_DKV_KT keys, TRN_KPW of
+// them per wave, and walks the query rows in tiles of TRN_DKV_QT.  TRN_RPW and TRN_KPW are A/B macros.
+#ifndef TRN_RPW
+#define TRN_RPW 32
+#endif
+#ifndef TRN_KPW
+#define TRN_KPW 16
+#endif
+constexpr int TRN_WAVES = 4;
+constexpr int TRN_DQ_QT = TRN_WAVES * TRN_RPW;
+constexpr int TRN_DQ_KT = 32;
+constexpr int TRN_DKV_KT = TRN_WAVES * TRN_KPW;
+constexpr int TRN_DKV_QT = 32;
+static_assert((TRN_RPW == 16 || TRN_RPW == 32) && (TRN_KPW == 16 || TRN_KPW == 32), "one or two 16-row / 16-key blocks a wave");
+inline int64_t trn_query_tiles(int64_t T) { return (T + TRN_DQ_QT - 1) / TRN_DQ_QT; }
+inline int64_t trn_key_tiles(int64_t S) { return (S + TRN_DKV_KT - 1) / TRN_DKV_KT; }
+
 }  // namespace fq

@@ -2236,3 +2236,79 @@ def attn_prefill_forward(q, k, v, attention_mask=None, head_dim=None, scale=None
     _lib.check(rc, "attn_prefill_forward")
     prefill_counts["fwd_launch"] += 1
     return out
+
+
+# ---- the fused training attention (the fqg_ header) ----------------------------------------------------------------------
+train_counts = {"fwd_launch": 0, "bwd_launch": 0, "copy_route": 0, "fallback": 0}
+# csrc/fq_shapes.h TRN_DQ_QT, TRN_DQ_KT, TRN_DKV_KT, TRN_DKV_QT: query rows of a workgroup and keys of a tile in the dq kernel, keys of a
+# workgroup and query rows of a tile in the dk/dv kernel (the tests' boundaries; the forward's are PREFILL_QT, PREFILL_KT)
+TRAIN_DQ_QT, TRAIN_DQ_KT, TRAIN_DKV_KT, TRAIN_DKV_QT = 128, 32, 64, 32
+
+
+def check_attn_train(q, k, v, attention_mask=None, head_dim=None, scale=None, causal=False, what="attn_train_forward"):
+    """check_attn_prefill's checks -> (B, H, T, S, D, inv), and: ValueError for a mask that requires grad (the kernels compute no gradient
+    for it)."""
+    geom = check_attn_prefill(q, k, v, attention_mask, head_dim, scale, causal, what)
+    if attention_mask is not None and attention_mask.requires_grad:
+        raise ValueError(f"{what}: a mask that requires grad is not served (the kernels compute no gradient for it)")
+    return geom
+
+
+def _train_served(tensors, mask, S):
+    """the tensors and the mask as the launches read them: a last stride that is not 1 is copied once and counted"""
+    served = []
+    for t in tensors:
+        t = t.detach()
+        if t.stride(-1) != 1:
+            train_counts["copy_route"] += 1
+            t = t.contiguous()
+        served.append(t)
+    if mask is not None and mask.stride(-1) != 1 and S > 1:
+        train_counts["copy_route"] += 1
+        mask = mask.contiguous()
+    return served, mask
+
+
+def attn_train_forward(q, k, v, attention_mask=None, head_dim=None, scale=None, causal=False, need_stats=True):
+    """-> (out, stats, saved): attn_prefill_forward's out [B, T, H, D], to the bit, and the fp32 [B, H, T, 2] row maxima and sums the
+    backward reads (None with need_stats=False: no buffer, nothing written); saved: (q, k, v, mask) as the launch read them, what a
+    backward needs beside out and stats.  One launch (fwd_launch)."""
+    B, H, T, S, D, inv = check_attn_train(q, k, v, attention_mask, head_dim, scale, causal)
+    _prep(q, "attn_train_forward")
+    (q, k, v), attention_mask = _train_served((q, k, v), attention_mask, S)
+    mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    stats = torch.empty((B, H, T, 2), dtype=torch.float32, device=q.device) if need_stats else None
+    rc = _launch(q, _lib.lib().fqg_attn_train_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
+                 out.data_ptr(), stats.data_ptr() if need_stats else None, *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], mbs, mrs,
+                 B, H, T, S, D, inv, _OUT_DTYPES[q.dtype], mcode, int(causal))
+    _lib.check(rc, "attn_train_forward")
+    train_counts["fwd_launch"] += 1
+    return out, stats, (q, k, v, mask)
+
+
+def attn_train_backward(dout, q, k, v, attention_mask, out, stats, head_dim=None, scale=None, causal=False):
+    """-> (dq [B, T, H, D], dk, dv [B, S, H, D]), contiguous (their transpose(1, 2) are the gradients of q, k, v): the gradient of
+    attn_train_forward's product from dout [B, H, T, D], the gradient of out.transpose(1, 2), with out [B, H, T, D] (that view) and
+    stats the forward's.  The scores and probabilities are recomputed tile by tile; the only workspace is an fp32 [B, H, T].  Two
+    launches, no atomics: two calls give the same bits (bwd_launch counts calls)."""
+    with torch.no_grad():
+        B, H, T, S, D, inv = check_attn_train(q, k, v, attention_mask, head_dim, scale, causal, "attn_train_backward")
+    _prep(q, "attn_train_backward")
+    _row_tensors("attn_train_backward", dout=dout, out=out)
+    for name, t in (("dout", dout), ("out", out)):
+        if t.dtype != q.dtype or tuple(t.shape) != (B, H, T, D) or t.device != q.device:
+            raise ValueError(f"attn_train_backward: {name} is [{B}, {H}, {T}, {D}] of {q.dtype} on {q.device}, got {tuple(t.shape)} of {t.dtype} on {t.device}")
+    _row_stats("attn_train_backward", stats, "stats is attn_train_forward's", (B, H, T, 2), q)
+    (q, k, v, out, dout), attention_mask = _train_served((q, k, v, out, dout), attention_mask, S)
+    mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
+    delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    dq = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    dk, dv = (torch.empty((B, S, H, D), dtype=q.dtype, device=q.device) for _ in range(2))
+    rc = _launch(q, _lib.lib().fqg_attn_train_bwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
+                 out.data_ptr(), dout.data_ptr(), stats.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                 *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3], *dout.stride()[:3], mbs, mrs, B, H, T, S, D, inv,
+                 _OUT_DTYPES[q.dtype], mcode, int(causal))
+    _lib.check(rc, "attn_train_backward")
+    train_counts["bwd_launch"] += 1
+    return dq, dk, dv
