@@ -55,6 +55,9 @@ DECODE_EXPORTS = ("fqd_attn_decode_workspace", "fqd_attn_decode_fwd")
 PREFILL_EXPORTS = ("fqp_attn_prefill_fwd",)
 # every symbol include/llmqat_fakequant_attn_train.h declares (the fqg_ family: the fused attention that has a gradient)
 ATTN_TRAIN_EXPORTS = ("fqg_attn_train_fwd", "fqg_attn_train_bwd")
+# every symbol include/llmqat_fakequant_attn_kvdecode.h declares (the fqk_ family: the decode attention over a cache of integer codes); named
+# apart from the recorded *_EXPORTS sets, which stay twelve beside the training attention's
+KVDECODE_SYMBOLS = ("fqk_attn_kvdecode_workspace", "fqk_attn_kvdecode_fwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -227,6 +230,10 @@ def _bind(L):
     L.fqg_attn_train_fwd.restype = i32
     L.fqg_attn_train_bwd.argtypes = [vp] * 11 + [i64] * 22 + [f32, i32, i32, i32, vp]
     L.fqg_attn_train_bwd.restype = i32
+    L.fqk_attn_kvdecode_workspace.argtypes = [i64] * 6 + [i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.fqk_attn_kvdecode_workspace.restype = i32
+    L.fqk_attn_kvdecode_fwd.argtypes = [vp] * 11 + [sz] + [i64] * 21 + [f32, i32, i32, i32, vp]
+    L.fqk_attn_kvdecode_fwd.restype = i32
     return L
 
 

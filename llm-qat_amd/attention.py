@@ -15,6 +15,8 @@ but the scores, the mask and two floats per row.
 
 decode_attention fuses the two products as well where a few new tokens (T <= 16) attend to a long cache and no gradient is asked for
 (DESIGN.md section 30): one stream over k and v.  install(..., decode=True) / convert(..., decode=True) route such calls to it.
+kv_decode_attention is decode_attention over a cache held as the exported integer codes of the fake-quantized k and v, dequantized and
+rotated in registers; install(..., decode=True, kv_codes=True) makes use_cache=True return such a cache.
 prefill_attention is the same operation for any T, a whole sequence or a long chunk over a cache: the teacher's
 forward, an evaluation run, the prompt pass of generation.  install(..., prefill=True) / convert(..., prefill=True) route to it.
 train_attention is prefill_attention with a gradient in q, k and v: the student's call.  Its backward recomputes the
@@ -25,7 +27,7 @@ import torch
 
 from . import compiled, cpu_tensors, ops
 
-__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention, prefill_attention and train_attention are public by name
+__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention, kv_decode_attention, prefill_attention and train_attention are public by name
 
 
 class _AttnSoftmax(torch.autograd.Function):
@@ -100,6 +102,34 @@ def decode_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None)
     return ops.attn_decode_forward(q, k, v, attention_mask, scale=inv).transpose(1, 2)
 
 
+def kv_decode_attention(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, head_dim=None, *, scale=None, num_bits=8, rotary=None, key_positions=None):
+    """decode_attention(q, k, v, ...) over a K/V cache held as the integer codes ops.sym_export writes for the per-token K / V hooks
+    (DESIGN.md section 33): k = rope(rb(k_codes / k_t2)) and v = rb(v_codes / v_t2) are made in registers and never exist in memory, so
+    the stream over the cache is a half (int8) or a quarter (int4) of the 16-bit one.  The dequantized values are QuantExport.dequantize()'s
+    bits, the rotated key has the bits rope.rotary would have written, and everything behind the operands is decode_attention's.
+
+    q: [B, H, T, D], bfloat16 or float16, T <= 16, D of 64 or 128; k_codes, v_codes: [B, H, S, D] int8, or for num_bits <= 4 uint8
+    [B, H, S, D / 2] with element 2 k in the low nibble of byte k, read where they lie (the .view(b, s, nh, hd).transpose(1, 2) of an
+    export's bins, a concatenation along the key axis); k_t2, v_t2: float32 [B, S], column 1 of QuantExport.scales; rotary: None (the codes
+    are the final key's) or (cos, sin) tables [P, D] / [1, 1, P, D] in q's dtype or float32; key_positions: int64 [B, S] or [1, S], None:
+    key s at position s (then S <= P).  v is never rotated.  -> [B, H, T, D] as a view of [B, T, H, D] memory.  Forward only: a call in
+    which a gradient is required raises.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True): then torch ops run."""
+    geom = ops.check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask, head_dim, scale, num_bits, rotary, key_positions, "kv_decode_attention")
+    if _needs_grad(q, k_t2, v_t2, attention_mask, *(rotary or ())):
+        raise RuntimeError("kv_decode_attention: forward only, but an input requires grad: call it under torch.no_grad(), detach the inputs, "
+                           "or use the products around attn_softmax, which have a backward")
+    inv = geom[5]
+    if q.device.type == "cpu":
+        if not cpu_tensors.ENABLED:
+            cpu_tensors.refuse(q, "kv_decode_attention")
+        return cpu_tensors.attn_kv_decode(q, k_codes, k_t2, v_codes, v_t2, attention_mask, inv, num_bits, rotary, key_positions)
+    if torch.compiler.is_compiling():
+        cos, sin = rotary if rotary is not None else (None, None)
+        return compiled.attn_kv_decode(q, k_codes, k_t2, v_codes, v_t2, attention_mask, inv, num_bits, cos, sin, key_positions).transpose(1, 2)
+    return ops.attn_kvdecode_forward(q, k_codes, k_t2, v_codes, v_t2, attention_mask, scale=inv, num_bits=num_bits, rotary=rotary,
+                                     key_positions=key_positions).transpose(1, 2)
+
+
 def prefill_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None, causal=False):
     """decode_attention's operation, arithmetic and contract for any number T of query rows, fused: a workgroup owns 128 query rows and
     walks all keys, each tile of k and v staged once for its four waves; the scores never exist in memory, where the three calls write and
@@ -172,13 +202,16 @@ def _fused_serves(q, k, v, attention_mask, hd, output_attentions, grad=False):
 
 
 def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False,
-             decode=False, prefill=False, train=False):
+             decode=False, prefill=False, train=False, kv_codes=False):
     """LlamaAttention.forward through the parent's attribute names, with attn_softmax between the two products.  lookup(): the rotary
     function, found at call time where the parent's forward finds it.  decode: calls that decode_attention serves go to it, the others
     are counted (ops.decode_counts["fallback"]) and take the three calls.  prefill: calls that the decode route has not taken and
     prefill_attention serves go to it; the others are counted in ops.prefill_counts["fallback"], and a call the prefill route serves is
     a fallback of neither dict.  train: a call that needs a gradient and that train_attention serves goes to it; any other call that needs
-    one is counted in ops.train_counts["fallback"]."""
+    one is counted in ops.train_counts["fallback"].  kv_codes (with kv_bits <= 8): the cache is (k_codes, v_codes, k_t2, v_t2,
+    key_positions), see _codes_forward."""
+    if kv_codes and getattr(self, "kv_bits", 32) <= ops.KV_CODE_MAX_BITS:
+        return _codes_forward(self, lookup, hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache, prefill, train)
     b, t, _ = hidden_states.size()
     nh, hd = self.num_heads, self.head_dim
     q = self.q_proj(hidden_states).view(b, t, nh, hd).transpose(1, 2)
@@ -196,6 +229,13 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
         k = torch.cat([past_key_value[0], k], dim=2)
         v = torch.cat([past_key_value[1], v], dim=2)
     past_key_value = (k, v) if use_cache else None
+    return _attend(self, q, k, v, attention_mask, past_key_value, output_attentions, decode, prefill, train)
+
+
+def _attend(self, q, k, v, attention_mask, past_key_value, output_attentions, decode, prefill, train):
+    """_forward behind the cache: the routes over q [B, H, T, D] and the full k, v -> (output, probabilities or None, past_key_value)"""
+    b, nh, t, hd = q.shape
+    s = k.shape[2]
     if decode or prefill:
         serves = _fused_serves(q, k, v, attention_mask, hd, output_attentions)
         fused = decode_attention if decode and serves and t <= ops.DECODE_MAX_T else prefill_attention if prefill and serves else None
@@ -226,24 +266,74 @@ def _forward(self, lookup, hidden_states, attention_mask=None, position_ids=None
     return out, (y if output_attentions else None), past_key_value
 
 
-def _fused_class(parent, names, decode=False, prefill=False, train=False):
+def _codes_forward(self, lookup, hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache, prefill, train):
+    """_forward with the cache held as codes: past_key_value = (k_codes, v_codes, k_t2, v_t2, key_positions), the
+    codes [B, H, S, D] (int4: D / 2) views of ops.sym_export's bins of the k / v projection outputs (k before the rotation), t2 fp32 [B, S],
+    the positions int64 [B, S]; each grows by torch.cat along its key axis.  A call with such a cache that kv_decode_attention serves goes
+    to it with the module's rotary tables; any other one with a cache materialises it in torch ops (ops.kvdecode_counts["fallback"]) and
+    takes the decode=True routes.  The prompt call runs on the fake-quantized tensors as ever and only emits the cache."""
+    b, t, _ = hidden_states.size()
+    nh, hd, bits = self.num_heads, self.head_dim, self.kv_bits
+    q = self.q_proj(hidden_states).view(b, t, nh, hd).transpose(1, 2)
+    kx, vx = self.k_proj(hidden_states), self.v_proj(hidden_states)
+    k = self.act_quantizer_k.apply(kx, self.act_clip_val_k, bits, False).view(b, t, nh, hd).transpose(1, 2)
+    v = self.act_quantizer_v.apply(vx, self.act_clip_val_v, bits, False).view(b, t, nh, hd).transpose(1, 2)
+    p = 0 if past_key_value is None else past_key_value[0].shape[-2]
+    s = t + p
+    cos, sin = self.rotary_emb(v, seq_len=s)
+    pos = (torch.arange(p, s, device=q.device) if position_ids is None else position_ids).reshape(-1, t).expand(b, t)
+    cache = None
+    if use_cache or past_key_value is not None:
+        container = ops.kv_container(bits)
+        new = []
+        for x in (kx, vx):
+            e = ops.sym_export(x.detach(), bits, container=container)
+            new += [e.bins.view(b, t, nh, -1).transpose(1, 2), e.scales[:, 1].reshape(b, t)]
+        new = (new[0], new[2], new[1], new[3], pos)
+        cache = new if past_key_value is None else tuple(torch.cat([old, x], dim=-2 if i < 2 else 1) for i, (old, x) in enumerate(zip(past_key_value, new)))
+    if past_key_value is None:
+        q, k = lookup()(q, k, cos, sin, position_ids)
+        return _attend(self, q, k, v, attention_mask, cache if use_cache else None, output_attentions, True, prefill, train)
+    serves = (_fused_serves(q, k, v, attention_mask, hd, output_attentions) and t <= ops.DECODE_MAX_T and cos.dtype == q.dtype
+              and cos.shape[-2] >= s and cos.device == q.device)
+    if serves:
+        if attention_mask is not None and attention_mask.size() != (b, 1, t, s):
+            raise ValueError(f"Attention mask should be of size {(b, 1, t, s)}, but is {attention_mask.size()}")
+        q = lookup()(q, k, cos, sin, position_ids)[0]
+        out = kv_decode_attention(q, cache[0], cache[2], cache[1], cache[3], attention_mask, hd, num_bits=bits, rotary=(cos, sin), key_positions=cache[4])
+        return self.o_proj(out.transpose(1, 2).reshape(b, t, nh * hd)), None, cache if use_cache else None
+    ops.kvdecode_counts["fallback"] += 1
+    q, k = lookup()(q, k, cos, sin, position_ids)
+    old = past_key_value
+    k = torch.cat([ops.kv_codes_materialize(old[0], old[2], q.dtype, bits, (cos, sin), old[4]), k], dim=2)
+    v = torch.cat([ops.kv_codes_materialize(old[1], old[3], q.dtype, bits), v], dim=2)
+    return _attend(self, q, k, v, attention_mask, cache if use_cache else None, output_attentions, True, prefill, train)
+
+
+def _fused_class(parent, names, decode=False, prefill=False, train=False, kv_codes=False):
     """a subclass of `parent` whose forward is _forward; names: the mapping in which apply_rotary_pos_emb is looked up at call time"""
     class LlamaAttention(parent):
         fused_attn_softmax = True
         fused_attn_decode = decode
         fused_attn_prefill = prefill
         fused_attn_train = train
+        fused_attn_kv_codes = kv_codes
 
         def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False):
             return _forward(self, lambda: names["apply_rotary_pos_emb"], hidden_states, attention_mask, position_ids, past_key_value,
-                            output_attentions, use_cache, decode, prefill, train)
+                            output_attentions, use_cache, decode, prefill, train, kv_codes)
 
     LlamaAttention.__qualname__ = LlamaAttention.__name__ = getattr(parent, "__name__", "LlamaAttention")
     LlamaAttention.__module__ = getattr(parent, "__module__", LlamaAttention.__module__)
     return LlamaAttention
 
 
-def install(namespace, decode=False, prefill=False, train=False):
+def _check_kv_codes(kv_codes, decode, what):
+    if kv_codes and not decode:
+        raise ValueError(f"{what}: kv_codes=True keeps the cache for kv_decode_attention, which is a decode route: give decode=True as well")
+
+
+def install(namespace, decode=False, prefill=False, train=False, kv_codes=False):
     """Replace the attribute LlamaAttention of a module object (the reference's models.modeling_llama_quant, whose decoder layers look
     the class up when they are built) with a subclass of it: the constructor, the parameters and the state_dict are the parent's; the
     forward runs the projections, the K / V hooks and the rotary call through the parent's names (apply_rotary_pos_emb is looked up in
@@ -255,36 +345,41 @@ def install(namespace, decode=False, prefill=False, train=False):
     prefill_attention with the module's mask (causality is never assumed); any other is counted in ops.prefill_counts["fallback"].
     train=True: a call that needs a gradient and meets the other conditions goes to train_attention with the module's mask; any other call
     that needs a gradient is counted in ops.train_counts["fallback"] and takes the three calls.
+    kv_codes=True (needs decode=True; a module whose kv_bits is above 8 ignores it): use_cache=True returns past_key_value = (k_codes,
+    v_codes, k_t2, v_t2, key_positions), the integer codes of the fake-quantized k and v (k before the rotation) with one divisor per
+    token, and a call over such a cache goes to kv_decode_attention; one it cannot serve is counted in ops.kvdecode_counts["fallback"].
     -> the previous attribute: assign it back to undo.  Models built before the call keep their attention: convert() re-classes those."""
     import types
     if not isinstance(namespace, types.ModuleType):
         raise TypeError(f"install: expected a module object (e.g. models.modeling_llama_quant), got {type(namespace).__name__}")
+    _check_kv_codes(kv_codes, decode, "install")
     previous = namespace.LlamaAttention
-    namespace.LlamaAttention = _fused_class(previous, vars(namespace), bool(decode), bool(prefill), bool(train))
+    namespace.LlamaAttention = _fused_class(previous, vars(namespace), bool(decode), bool(prefill), bool(train), bool(kv_codes))
     return previous
 
 
 _NEEDS = ("q_proj", "k_proj", "v_proj", "o_proj", "rotary_emb", "num_heads", "head_dim")
-_converted = {}      # (parent class, decode, prefill, train) -> its fused subclass: one per class, so that type(m) is shared by a model's layers
+_converted = {}      # (parent class, decode, prefill, train, kv_codes) -> its fused subclass: one per class, so that type(m) is shared by a model's layers
 
 
 def _is_attention(m):
     return not getattr(m, "fused_attn_softmax", False) and all(hasattr(m, n) for n in _NEEDS) and "apply_rotary_pos_emb" in getattr(type(m).forward, "__globals__", {})
 
 
-def convert(model, decode=False, prefill=False, train=False):
+def convert(model, decode=False, prefill=False, train=False, kv_codes=False):
     """Re-class, in place, every module of `model` (itself included) that has q_proj, k_proj, v_proj, o_proj, rotary_emb, num_heads and
     head_dim, whose forward finds apply_rotary_pos_emb in its module, and that is not converted already: its class becomes the fused
-    subclass of its class, the object, its parameters and its state_dict keys stay.  decode, prefill, train: as install's.  -> the number re-classed."""
+    subclass of its class, the object, its parameters and its state_dict keys stay.  decode, prefill, train, kv_codes: as install's.  -> the number re-classed."""
     if not isinstance(model, torch.nn.Module):
         raise TypeError(f"convert: expected a torch.nn.Module, got {type(model).__name__}")
+    _check_kv_codes(kv_codes, decode, "convert")
     n = 0
     for m in model.modules():
         if _is_attention(m):
             parent = type(m)
-            key = (parent, bool(decode), bool(prefill), bool(train))
+            key = (parent, bool(decode), bool(prefill), bool(train), bool(kv_codes))
             if key not in _converted:
-                _converted[key] = _fused_class(parent, parent.forward.__globals__, bool(decode), bool(prefill), bool(train))
+                _converted[key] = _fused_class(parent, parent.forward.__globals__, *key[1:])
             m.__class__ = _converted[key]
             n += 1
     return n

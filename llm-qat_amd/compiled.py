@@ -560,6 +560,26 @@ def attn_decode(q, k, v, mask, inv):
     return attn_decode_op(q, k, v, mask, inv)
 
 
+# ---- the decode attention over a codes cache (ops.attn_kvdecode_forward): out [B, T, H, D], forward only ---------------
+@torch.library.custom_op("llmqat_amd::attn_kv_decode", mutates_args=(), device_types="cuda")
+def attn_kv_decode_op(q: torch.Tensor, k_codes: torch.Tensor, k_t2: torch.Tensor, v_codes: torch.Tensor, v_t2: torch.Tensor, mask: Optional[torch.Tensor],
+                      inv: float, num_bits: int, cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], key_positions: Optional[torch.Tensor]) -> torch.Tensor:
+    return ops.attn_kvdecode_forward(q, k_codes, k_t2, v_codes, v_t2, mask, scale=inv, num_bits=num_bits, rotary=None if cos is None else (cos, sin),
+                                     key_positions=key_positions)
+
+
+@attn_kv_decode_op.register_fake
+def _(q, k_codes, k_t2, v_codes, v_t2, mask, inv, num_bits, cos, sin, key_positions):
+    B, H, T, _, D, *_ = ops.check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, mask, scale=inv, num_bits=num_bits, rotary=None if cos is None else (cos, sin),
+                                                key_positions=key_positions)
+    return q.new_empty((B, T, H, D))
+
+
+def attn_kv_decode(q, k_codes, k_t2, v_codes, v_t2, mask, inv, num_bits, cos, sin, key_positions):
+    """attention.kv_decode_attention while compiling -> out [B, T, H, D]"""
+    return attn_kv_decode_op(q, k_codes, k_t2, v_codes, v_t2, mask, inv, num_bits, cos, sin, key_positions)
+
+
 # ---- the fused prefill attention (ops.attn_prefill_forward, DESIGN.md section 31): out [B, T, H, D], forward only -----------------------------
 @torch.library.custom_op("llmqat_amd::attn_prefill", mutates_args=(), device_types="cuda")
 def attn_prefill_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], inv: float, causal: bool) -> torch.Tensor:

@@ -121,6 +121,15 @@ def attn_decode(q, k, v, mask, head_dim=None, scale=None):
     return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)
 
 
+def attn_kv_decode(q, k_codes, k_t2, v_codes, v_t2, mask, inv, num_bits, rotary=None, key_positions=None):
+    """kv_decode_attention in torch ops: the cache unpacked, divided by t2 in fp32, rounded to q's dtype and (k) rotated with the eager
+    chain's roundings, then attn_decode's chain"""
+    from . import ops
+    k = ops.kv_codes_materialize(k_codes, k_t2, q.dtype, num_bits, rotary, key_positions)
+    v = ops.kv_codes_materialize(v_codes, v_t2, q.dtype, num_bits)
+    return attn_decode(q, k, v, mask, scale=inv)
+
+
 def attn_prefill(q, k, v, mask, head_dim=None, scale=None, causal=False):
     """attn_decode for any T, under prefill_attention's contract; causal: the keys past S - T + t of row t get weight exactly 0 (-inf in
     front of the softmax) and the others go through the chain without a mask"""

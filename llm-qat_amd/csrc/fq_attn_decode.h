@@ -91,6 +91,119 @@ template <int N> __device__ __forceinline__ void dec_merge(float& m, float& l, f
 template <int D> constexpr int dec_row_bytes() { return 2 * D + 16; }
 template <int D> constexpr int dec_stage_bytes() { return DEC_TILE * dec_row_bytes<D>(); }
 
+// ---- the stages that dec_kernel and the codes-cache kernel (fq_attn_kvdecode.h) share -----------------------------------------------------
+// the online softmax's step over one tile: sc holds the scores of the lane's eight keys (4 g + r of both halves) of query row j, mk their
+// mask values.  (m, l) and the accumulator move to the new maximum; -> the rounded exponentials as the PV instruction's B operand
+template <int DT, int MDT, int DB>
+__device__ __forceinline__ u32x4_t dec_softmax_step(const f32x4_t (&sc)[2], const float (&mk)[8], int64_t tile, int g, int64_t S, float inv, float& m,
+                                                    float& l, f32x4_t (&acc)[DB]) {
+    float z[8];
+    float tmax = LOSS_NEG_INF;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int64_t key = tile * DEC_TILE + 16 * (c >> 2) + 4 * g + (c & 3);
+        const float x = Ty<DT>::rb(sc[c >> 2][c & 3]);      // the first product's own rounding
+        const float zz = attn_z<DT, MDT>(attn_a<DT, MDT>(x, mk[c], inv));
+        z[c] = key < S ? zz : LOSS_NEG_INF;                 // behind the clamp
+        tmax = __builtin_fmaxf(tmax, z[c]);
+    }
+    tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, 16));
+    tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, 32));
+    const float mn = __builtin_fmaxf(m, tmax), ref = loss_ref(mn);
+    const float alpha = attn_exp(m - ref);                  // m raw: -inf - ref is -inf, never inf - inf
+    m = mn;
+    l = l * alpha;
+    float p[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        p[c] = attn_exp(z[c] - ref);
+        l += p[c];
+    }
+    u32x4_t pf;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float e[2] = {p[2 * i], p[2 * i + 1]};
+        pf[i] = Ty<DT>::pack(e);
+    }
+#pragma unroll
+    for (int i = 0; i < DB; ++i) acc[i] = acc[i] * alpha;
+    return pf;
+}
+
+// the mask values of the lane's eight keys of a tile (0 without a mask); a key past S re-reads the last
+template <int MDT> __device__ __forceinline__ void dec_load_mask(const void* mask, int64_t mb, int64_t tile, int g, int64_t last, float (&mk)[8]) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        mk[c] = 0.0f;
+        if constexpr (MDT != ATTN_NOMASK) {
+            int64_t key = tile * DEC_TILE + 16 * (c >> 2) + 4 * g + (c & 3);
+            key = key < last ? key : last;
+            mk[c] = Ty<MDT>::load1(mask, mb + key);
+        }
+    }
+}
+
+// the column of `out` that register r of accumulator block db holds in lane group g.  The matrix instruction leaves row 4 g + r of block
+// db there; which d that row stands for is the A operand's choice: 16 db + row (dec_kernel), or, PERM, row * DB + db (the codes kernel,
+// whose lane reads the DB codes of one key with one LDS load)
+template <int DB, bool PERM> __device__ __forceinline__ int dec_col(int db, int g, int r) { return PERM ? (4 * g + r) * DB + db : 16 * db + 4 * g + r; }
+
+// the waves' partials into wave 0 through LDS, in wave order, then out (one chunk) or the workspace (more); all waves of the workgroup call
+template <int DT, int D, bool PERM>
+__device__ __forceinline__ void dec_finish(char* smem, float m, float l, f32x4_t (&acc)[D / 16], void* out, float* ws, int64_t H, int64_t T, int nsplit,
+                                           int64_t bh, int64_t b, int64_t h) {
+    constexpr int DB = D / 16, PART = 4 * DB + 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 15, g = lane >> 4;
+    // slot e of lane i at float e * 64 + i of the wave's part
+    __syncthreads();
+    float* part = (float*)smem;
+    if (wave > 0) {
+        float* mine = part + (wave - 1) * 64 * PART + lane;
+        mine[0] = m;
+        mine[64] = l;
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mine[(2 + 4 * db + r) * 64] = acc[db][r];
+        }
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll
+    for (int w = 1; w < DEC_WAVES; ++w) {
+        const float* theirs = part + (w - 1) * 64 * PART + lane;
+        f32x4_t acc1[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc1[db][r] = theirs[(2 + 4 * db + r) * 64];
+        }
+        dec_merge(m, l, acc, theirs[0], theirs[64], acc1);
+    }
+    l = dec_sum_groups(l);
+    if (j >= T) return;
+    if (nsplit == 1) {
+        const int64_t o = ((b * T + j) * H + h) * D;
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Ty<DT>::store1(out, o + dec_col<DB, PERM>(db, g, r), acc[db][r] / l);
+        }
+    } else {
+        float* w = ws + ((bh * nsplit + blockIdx.y) * T + j) * (D + 2);
+        if (g == 0) {
+            w[0] = m;
+            w[1] = l;
+        }
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) w[2 + dec_col<DB, PERM>(db, g, r)] = acc[db][r];
+        }
+    }
+}
+
 template <int DT, int MDT, int D, bool VEC>
 __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
     static_assert(D == 64 || D == 128, "head sizes served");
@@ -158,15 +271,7 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
                 vr[it] = dec_ld16<VEC>(vp + key * a.vs[2]);
             }
             float mk[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                mk[c] = 0.0f;
-                if constexpr (MDT != ATTN_NOMASK) {
-                    int64_t key = tile * DEC_TILE + 16 * (c >> 2) + 4 * g + (c & 3);
-                    key = key < last ? key : last;
-                    mk[c] = Ty<MDT>::load1(a.mask, mb + key);
-                }
-            }
+            dec_load_mask<MDT>(a.mask, mb, tile, g, last, mk);
             u32x4_t kn[2 * KS];
             load_k(tile + DEC_WAVES, kn);
 
@@ -177,36 +282,7 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) sc[hf] = dec_mfma<DT>(kr[hf * KS + ks], qf[ks], sc[hf]);
             }
-            float z[8];
-            float tmax = LOSS_NEG_INF;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const int64_t key = tile * DEC_TILE + 16 * (c >> 2) + 4 * g + (c & 3);
-                const float x = Ty<DT>::rb(sc[c >> 2][c & 3]);      // the first product's own rounding
-                const float zz = attn_z<DT, MDT>(attn_a<DT, MDT>(x, mk[c], a.inv));
-                z[c] = key < S ? zz : LOSS_NEG_INF;                 // behind the clamp
-                tmax = __builtin_fmaxf(tmax, z[c]);
-            }
-            tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, 16));
-            tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, 32));
-            const float mn = __builtin_fmaxf(m, tmax), ref = loss_ref(mn);
-            const float alpha = attn_exp(m - ref);                  // m raw: -inf - ref is -inf, never inf - inf
-            m = mn;
-            l = l * alpha;
-            float p[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                p[c] = attn_exp(z[c] - ref);
-                l += p[c];
-            }
-            u32x4_t pf;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float e[2] = {p[2 * i], p[2 * i + 1]};
-                pf[i] = Ty<DT>::pack(e);
-            }
-#pragma unroll
-            for (int i = 0; i < DB; ++i) acc[i] = acc[i] * alpha;
+            const u32x4_t pf = dec_softmax_step<DT, MDT>(sc, mk, tile, g, S, a.inv, m, l, acc);
 
             // V through the wave's stage
 #pragma unroll
@@ -231,53 +307,7 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
         }
     }
 
-    // the waves' partials into wave 0, in wave order; slot e of lane i at float e * 64 + i of the wave's part
-    __syncthreads();
-    float* part = (float*)smem;
-    if (wave > 0) {
-        float* mine = part + (wave - 1) * 64 * PART + lane;
-        mine[0] = m;
-        mine[64] = l;
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mine[(2 + 4 * db + r) * 64] = acc[db][r];
-        }
-    }
-    __syncthreads();
-    if (wave > 0) return;
-#pragma unroll
-    for (int w = 1; w < DEC_WAVES; ++w) {
-        const float* theirs = part + (w - 1) * 64 * PART + lane;
-        f32x4_t acc1[DB];
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc1[db][r] = theirs[(2 + 4 * db + r) * 64];
-        }
-        dec_merge(m, l, acc, theirs[0], theirs[64], acc1);
-    }
-    l = dec_sum_groups(l);
-    if (j >= a.T) return;
-    if (a.nsplit == 1) {
-        const int64_t o = ((b * a.T + j) * a.H + h) * D + 4 * g;
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Ty<DT>::store1(a.out, o + 16 * db + r, acc[db][r] / l);
-        }
-    } else {
-        float* w = a.ws + ((bh * a.nsplit + blockIdx.y) * a.T + j) * (D + 2);
-        if (g == 0) {
-            w[0] = m;
-            w[1] = l;
-        }
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) w[2 + 16 * db + 4 * g + r] = acc[db][r];
-        }
-    }
+    dec_finish<DT, D, false>(smem, m, l, acc, a.out, a.ws, a.H, a.T, a.nsplit, bh, b, h);
 }
 
 // the chunks of one (batch, head, query row) into out, in chunk order: grid (B * H, T), D threads, thread d owns out[.., d].  The chunks'

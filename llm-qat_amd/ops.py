@@ -2191,6 +2191,134 @@ def attn_decode_forward(q, k, v, attention_mask=None, head_dim=None, scale=None)
     return out
 
 
+# ---- the decode attention over a cache of integer codes (the fqk_ header) -----------------------------------------------
+kvdecode_counts = {"fwd_launch": 0, "copy_route": 0, "fallback": 0}
+KV_CODE_MAX_BITS = 8
+_KV_CONTAINERS = {"int4": (torch.uint8, 4, 2), "int8": (torch.int8, 8, 1)}      # container -> (dtype, bits of a code, codes per element)
+
+
+def kv_container(num_bits):
+    """the container of a codes cache: default_container's rule for Sym up to 8 bits, int8 at 8 for every dtype (the saturating format)"""
+    if isinstance(num_bits, bool) or not isinstance(num_bits, int):
+        raise TypeError(f"num_bits is an int, got {type(num_bits).__name__}")
+    if not 1 <= num_bits <= KV_CODE_MAX_BITS:
+        raise ValueError(f"num_bits={num_bits}: a codes cache holds 1 .. {KV_CODE_MAX_BITS} bits")
+    return "int4" if num_bits <= 4 else "int8"
+
+
+def check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, head_dim=None, scale=None, num_bits=8, rotary=None, key_positions=None,
+                        what="attn_kvdecode_forward"):
+    """The argument checks of the decode attention over a codes cache on types, shapes, dtypes and devices alone (the fake implementation
+    of the compiled op runs them too) -> (B, H, T, S, D, inv, container, P): TypeError for a non-tensor, a q that is not bfloat16 or
+    float16, codes whose dtype is not num_bits' container's, divisors that are not float32, a mask or tables of a dtype that is not served,
+    positions that are not int64, a rotary that is not a (cos, sin) pair; ValueError for a q that is not a non-empty [B, H, T, D] with
+    T <= 16 and D of 64 or 128, codes that are not one [B, H, S, D] (int4: D / 2), divisors that are not [B, S], a mask, tables or
+    positions of another shape, positions without tables, S > P where no positions are given, tensors on two devices.  P: 0 without tables."""
+    _row_tensors(what, q=q, k_codes=k_codes, k_t2=k_t2, v_codes=v_codes, v_t2=v_t2)
+    if attention_mask is not None:
+        _row_tensors(what, attention_mask=attention_mask)
+    container = kv_container(num_bits)
+    cdt, _, per = _KV_CONTAINERS[container]
+    if q.dtype not in _DECODE_DTYPES:
+        raise TypeError(f"{what}: q of {q.dtype} is not served: bfloat16 or float16")
+    if k_codes.dtype != cdt or v_codes.dtype != cdt:
+        raise TypeError(f"{what}: num_bits={num_bits} takes {container} codes ({cdt}), got {k_codes.dtype} and {v_codes.dtype}")
+    if k_t2.dtype != torch.float32 or v_t2.dtype != torch.float32:
+        raise TypeError(f"{what}: the divisors are float32 (column 1 of QuantExport.scales), got {k_t2.dtype} and {v_t2.dtype}")
+    if attention_mask is not None and attention_mask.dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"{what}: a mask of dtype {attention_mask.dtype} beside q of {q.dtype} is not served: q's dtype or float32")
+    if rotary is not None and not (isinstance(rotary, (tuple, list)) and len(rotary) == 2):
+        raise TypeError(f"{what}: rotary is None or the pair (cos, sin), got {type(rotary).__name__}")
+    inv = attn_inv(head_dim, scale, what)
+    if q.dim() != 4 or q.numel() == 0 or q.shape[2] > DECODE_MAX_T or q.shape[3] not in DECODE_HEAD_DIMS:
+        raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with T <= {DECODE_MAX_T} and D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
+    B, H, T, D = q.shape
+    if k_codes.dim() != 4 or k_codes.shape[2] == 0 or tuple(k_codes.shape) != (B, H, k_codes.shape[2], D // per) or tuple(v_codes.shape) != tuple(k_codes.shape):
+        raise ValueError(f"{what}: the {container} codes of k and v are one non-empty [{B}, {H}, S, {D // per}], got {tuple(k_codes.shape)} and {tuple(v_codes.shape)}")
+    S = k_codes.shape[2]
+    if tuple(k_t2.shape) != (B, S) or tuple(v_t2.shape) != (B, S):
+        raise ValueError(f"{what}: the divisors are [{B}, {S}], one per token, got {tuple(k_t2.shape)} and {tuple(v_t2.shape)}")
+    if attention_mask is not None and (attention_mask.dim() != 4 or tuple(attention_mask.shape[1:]) != (1, T, S) or attention_mask.shape[0] not in (1, B)):
+        raise ValueError(f"{what}: the mask is [{B}, 1, {T}, {S}] or [1, 1, {T}, {S}], got {tuple(attention_mask.shape)}")
+    P = 0
+    if rotary is not None:
+        check_rope_tables(rotary[0], rotary[1], key_positions, q, B, S, D, what, q.dtype)
+        P = rotary[0].shape[-2]
+        if key_positions is None and S > P:
+            raise ValueError(f"{what}: S = {S} keys at the positions 0 .. S - 1 need tables of S rows, got P = {P}")
+    elif key_positions is not None:
+        raise ValueError(f"{what}: key_positions without rotary=(cos, sin)")
+    for name, t in (("k_codes", k_codes), ("k_t2", k_t2), ("v_codes", v_codes), ("v_t2", v_t2), ("the mask", attention_mask)):
+        if t is not None and t.device != q.device:
+            raise ValueError(f"{what}: q is on {q.device}, {name} on {t.device}")
+    return B, H, T, S, D, inv, container, P
+
+
+def attn_kvdecode_workspace(B, H, T, D, S, cus, dtype=torch.bfloat16, num_bits=8):
+    """-> (bytes, nsplit): the workspace fqk_attn_kvdecode_fwd needs for this shape on a device of `cus` compute units, and the chunks it
+    cuts S into (attn_decode_workspace's split)"""
+    nbytes, nsplit = ctypes.c_size_t(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().fqk_attn_kvdecode_workspace(B, H, T, D, S, cus, _OUT_DTYPES[dtype], _KV_CONTAINERS[kv_container(num_bits)][1],
+                                                      ctypes.byref(nbytes), ctypes.byref(nsplit)), "attn_kvdecode_workspace")
+    return nbytes.value, nsplit.value
+
+
+def attn_kvdecode_forward(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, head_dim=None, scale=None, num_bits=8, rotary=None, key_positions=None):
+    """-> out [B, T, H, D] (contiguous): attn_decode_forward(q, rope(rb(k_codes / k_t2)), rb(v_codes / v_t2)) with k and v never
+    materialised.  The codes [B, H, S, D] (int8; num_bits <= 4: uint8 [B, H, S, D / 2], two nibbles a byte) are read
+    where they lie through their strides; k_t2, v_t2 fp32 [B, S]; rotary None or (cos, sin) tables [P, D] / [1, 1, P, D] in q's dtype or
+    float32 (rounded to q's dtype first); key_positions int64 [B, S] or [1, S], None: the key index.  A last stride that is not 1, tables
+    that are not in q's dtype or not dense and positions that are not dense take one counted copy (copy_route).  Forward only."""
+    B, H, T, S, D, inv, container, P = check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask, head_dim, scale, num_bits, rotary, key_positions)
+    _prep(q, "attn_kvdecode_forward")
+
+    def dense(t, ok):
+        if ok:
+            return t
+        kvdecode_counts["copy_route"] += 1
+        return t.contiguous()
+    q, k_codes, v_codes, k_t2, v_t2 = (dense(t.detach(), t.stride(-1) == 1 or t.shape[-1] == 1) for t in (q, k_codes, v_codes, k_t2, v_t2))
+    if attention_mask is not None:
+        attention_mask = dense(attention_mask, attention_mask.stride(-1) == 1 or S == 1)
+    mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
+    cos = sin = pos = None
+    pbs = 0
+    if rotary is not None:
+        cos, sin = (dense(t.detach().reshape(P, D), t.dtype == q.dtype and t.is_contiguous()).to(q.dtype) for t in rotary)
+        if key_positions is not None:
+            pos = dense(key_positions, key_positions.stride(-1) == 1 or S == 1)
+            pbs = pos.stride(0) if pos.shape[0] == B and B > 1 else 0
+    cus = _decode_cus(q)
+    nbytes, _ = attn_kvdecode_workspace(B, H, T, D, S, cus, q.dtype, num_bits)
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if nbytes else None
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    rc = _launch(q, _lib.lib().fqk_attn_kvdecode_fwd, q.data_ptr(), k_codes.data_ptr(), k_t2.data_ptr(), v_codes.data_ptr(), v_t2.data_ptr(), ptr(mask),
+                 ptr(cos), ptr(sin), ptr(pos), out.data_ptr(), ptr(ws), nbytes, *q.stride()[:3], *k_codes.stride()[:3], *v_codes.stride()[:3],
+                 k_t2.stride(0) if B > 1 else 0, v_t2.stride(0) if B > 1 else 0, mbs, mrs, pbs, P, B, H, T, S, D, cus, inv, _OUT_DTYPES[q.dtype], mcode,
+                 _KV_CONTAINERS[container][1])
+    _lib.check(rc, "attn_kvdecode_forward")
+    kvdecode_counts["fwd_launch"] += 1
+    return out
+
+
+def kv_codes_materialize(codes, t2, dtype, num_bits, rotary=None, key_positions=None):
+    """-> [B, H, S, D] of `dtype`: the tensor a codes cache stands for, in torch ops (the route of the calls the kernel does not serve and
+    of the CPU): unpack, divide by t2 in fp32, round to the dtype, rotate with the eager chain's roundings"""
+    if kv_container(num_bits) == "int4":
+        lo, hi = (codes & 0xF).to(torch.int16), (codes >> 4).to(torch.int16)
+        codes = torch.stack((lo, hi), -1).flatten(-2)
+        codes = torch.where(codes >= 8, codes - 16, codes)
+    x = (codes.to(torch.float32) / t2[:, None, :, None]).to(dtype)
+    if rotary is None:
+        return x
+    D, S = x.shape[-1], x.shape[2]
+    cos, sin = (t.reshape(-1, D).to(dtype) for t in rotary)
+    pos = torch.arange(S, device=x.device)[None] if key_positions is None else key_positions
+    cos, sin = cos[pos].unsqueeze(1), sin[pos].unsqueeze(1)
+    return x * cos + torch.cat((-x[..., D // 2:], x[..., :D // 2]), -1) * sin
+
+
 # ---- the fused prefill attention (the fqp_ header, DESIGN.md section 31) -----------------------------------------------------------------------
 prefill_counts = {"fwd_launch": 0, "copy_route": 0, "fallback": 0}
 PREFILL_QT, PREFILL_KT = 128, 32      # csrc/fq_shapes.h PRE_QT, PRE_KT: query rows of a workgroup, keys of a tile (the tests' boundaries)
