@@ -58,6 +58,8 @@ ATTN_TRAIN_EXPORTS = ("fqg_attn_train_fwd", "fqg_attn_train_bwd")
 # every symbol include/llmqat_fakequant_attn_kvdecode.h declares (the fqk_ family: the decode attention over a cache of integer codes); named
 # apart from the recorded *_EXPORTS sets, which stay twelve beside the training attention's
 KVDECODE_SYMBOLS = ("fqk_attn_kvdecode_workspace", "fqk_attn_kvdecode_fwd")
+# every symbol include/llmqat_fakequant_attn_gqa.h declares (the fqh_ family: the decode, codes-cache and prefill attention over fewer K/V heads)
+GQA_SYMBOLS = ("fqh_attn_decode_workspace", "fqh_attn_decode_fwd", "fqh_attn_kvdecode_workspace", "fqh_attn_kvdecode_fwd", "fqh_attn_prefill_fwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -234,6 +236,14 @@ def _bind(L):
     L.fqk_attn_kvdecode_workspace.restype = i32
     L.fqk_attn_kvdecode_fwd.argtypes = [vp] * 11 + [sz] + [i64] * 21 + [f32, i32, i32, i32, vp]
     L.fqk_attn_kvdecode_fwd.restype = i32
+    # the fqh_ family: the signatures above with Hkv behind H
+    L.fqh_attn_decode_workspace.argtypes = [i64] * 7 + [i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.fqh_attn_decode_fwd.argtypes = [vp] * 6 + [sz] + [i64] * 18 + [f32, i32, i32, vp]
+    L.fqh_attn_kvdecode_workspace.argtypes = [i64] * 7 + [i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.fqh_attn_kvdecode_fwd.argtypes = [vp] * 11 + [sz] + [i64] * 22 + [f32, i32, i32, i32, vp]
+    L.fqh_attn_prefill_fwd.argtypes = [vp] * 5 + [i64] * 17 + [f32, i32, i32, i32, vp]
+    for name in GQA_SYMBOLS:
+        getattr(L, name).restype = i32
     return L
 
 

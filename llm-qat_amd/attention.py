@@ -86,7 +86,9 @@ def decode_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None)
 
     q: [B, H, T, D] with T <= 16 and D of 64 or 128; k, v: [B, H, S, D]; all three bfloat16 or all three float16, on a CUDA device, read
     where they lie (the transposed views of a projection, a concatenation with a cache); attention_mask: None, or [B, 1, T, S] /
-    [1, 1, T, S] in their dtype or float32.  Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory, so that
+    [1, 1, T, S] in their dtype or float32.  Grouped-query attention: k, v may be [B, Hkv, S, D] with Hkv dividing H; query head h then
+    attends to K/V head h // (H // Hkv), the repeat_interleave(k, H // Hkv, dim=1) convention, and the query heads of a group share one
+    workgroup, so k and v are still read once.  Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory, so that
     .transpose(1, 2).reshape(B, T, H * D) is a view.  Forward only: a call in which a gradient is required raises.  CPU tensors are
     refused unless llm_qat_amd.allow_cpu_tensors(True): then the chain runs in torch ops."""
     B, H, T, S, D, inv = ops.check_attn_decode(q, k, v, attention_mask, head_dim, scale, "decode_attention")
@@ -112,7 +114,9 @@ def kv_decode_attention(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, he
     [B, H, S, D / 2] with element 2 k in the low nibble of byte k, read where they lie (the .view(b, s, nh, hd).transpose(1, 2) of an
     export's bins, a concatenation along the key axis); k_t2, v_t2: float32 [B, S], column 1 of QuantExport.scales; rotary: None (the codes
     are the final key's) or (cos, sin) tables [P, D] / [1, 1, P, D] in q's dtype or float32; key_positions: int64 [B, S] or [1, S], None:
-    key s at position s (then S <= P).  v is never rotated.  -> [B, H, T, D] as a view of [B, T, H, D] memory.  Forward only: a call in
+    key s at position s (then S <= P).  v is never rotated.  Grouped-query attention: the codes may have Hkv heads, Hkv dividing H, as
+    decode_attention's k, v; the heads of a group share one dequantisation and rotation of K (the divisors, tables and positions are per
+    token).  -> [B, H, T, D] as a view of [B, T, H, D] memory.  Forward only: a call in
     which a gradient is required raises.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True): then torch ops run."""
     geom = ops.check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask, head_dim, scale, num_bits, rotary, key_positions, "kv_decode_attention")
     if _needs_grad(q, k_t2, v_t2, attention_mask, *(rotary or ())):
@@ -138,8 +142,9 @@ def prefill_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None
     q: [B, H, T, D] with D of 64 or 128; k, v: [B, H, S, D]; all three bfloat16 or all three float16, on a CUDA device, read where they
     lie; attention_mask: None, or [B, 1, T, S] / [1, 1, T, S] in their dtype or float32.  causal=True (no mask, T <= S): query row t
     attends to the keys s <= S - T + t and to no others, which for finite scores is the additive causal mask's result; no mask is read
-    and the keys past a workgroup's last row are skipped.  Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory.
-    Forward only: a call in which a gradient is required raises.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True):
+    and the keys past a workgroup's last row are skipped.  Grouped-query attention: k, v may be [B, Hkv, S, D] with Hkv dividing H,
+    query head h over K/V head h // (H // Hkv); the result has the bits of the call on the repeated k, v.  Give head_dim, or scale=.
+    -> [B, H, T, D] as a view of [B, T, H, D] memory.  Forward only: a call in which a gradient is required raises.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True):
     then the chain runs in torch ops."""
     B, H, T, S, D, inv = ops.check_attn_prefill(q, k, v, attention_mask, head_dim, scale, causal, "prefill_attention")
     if _needs_grad(q, k, v, attention_mask):
@@ -181,7 +186,9 @@ def train_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None, 
     lie; attention_mask: None, or [B, 1, T, S] / [1, 1, T, S] in their dtype or float32, which must not require grad; causal=True (no
     mask, T <= S) as prefill_attention's.  Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory; the gradients are
     views of [B, T, H, D] / [B, S, H, D] memory likewise.  Under no_grad, or where nothing requires grad, nothing is saved and no row
-    statistics are written.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True): then the chain runs in torch ops."""
+    statistics are written.  k, v of fewer heads than q (grouped-query attention) are refused: the backward does not serve them; expand
+    k and v with repeat_interleave for a gradient.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True): then the chain
+    runs in torch ops."""
     B, H, T, S, D, inv = ops.check_attn_train(q, k, v, attention_mask, head_dim, scale, causal, "train_attention")
     if q.device.type == "cpu":
         if not cpu_tensors.ENABLED:

@@ -108,10 +108,17 @@ def attn_softmax(scores, mask, head_dim=None, scale=None):
     return torch.nn.functional.softmax(attn, dim=-1, dtype=torch.float32).to(scores.dtype)
 
 
+def _expand_kv(q, k, v):
+    """grouped-query attention: k, v of Hkv heads with every head repeated H / Hkv times (query head h reads K/V head h // (H // Hkv))"""
+    g = q.shape[1] // k.shape[1]
+    return (k, v) if g == 1 else (k.repeat_interleave(g, 1), v.repeat_interleave(g, 1))
+
+
 def attn_decode(q, k, v, mask, head_dim=None, scale=None):
     """both attention products of LlamaAttention.forward with the chain between them (models/modeling_llama_quant.py:345-377), in torch
     ops, under decode_attention's contract: the chain's roundings up to the clamp, then the fp32 softmax kept in fp32, the second product
     in float64 and ONE rounding to the dtype -> [B, H, T, D] as a view of [B, T, H, D] memory, as the device route returns it"""
+    k, v = _expand_kv(q, k, v)
     attn = torch.matmul(q, k.transpose(2, 3))
     attn = attn / math.sqrt(head_dim) if scale is None else attn * scale
     if mask is not None:
@@ -136,6 +143,7 @@ def attn_prefill(q, k, v, mask, head_dim=None, scale=None, causal=False):
     if not causal:
         return attn_decode(q, k, v, mask, head_dim, scale)
     T, S = q.shape[2], k.shape[2]
+    k, v = _expand_kv(q, k, v)
     attn = torch.matmul(q, k.transpose(2, 3))
     attn = attn / math.sqrt(head_dim) if scale is None else attn * scale
     hidden = torch.arange(S)[None] > (S - T + torch.arange(T))[:, None]

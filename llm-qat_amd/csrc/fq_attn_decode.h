@@ -51,7 +51,38 @@ struct DecArgs {
     int64_t per;         // tiles of a chunk
     int nsplit;
     float inv;
+    int64_t Hkv, G, HP, NP;      // the grouped launch (fq_attn_gqa.h) alone: K/V heads, query heads of one, heads of a pack, packs of a K/V head
 };
+
+// What column j of the two matrix instructions stands for in workgroup blockIdx.x.  One head a workgroup (!GQA): token j of head
+// blockIdx.x % H.  Grouped: the workgroup is (batch, K/V head, pack) and column j is token j % T of the pack's
+// query head j / T.  A dead column (a row >= T, a head past the group) has zero q, a live column's addresses and stores nothing.
+struct DecCol {
+    int64_t b, h, kvh;   // batch, query head, K/V head
+    int t;               // the token whose addresses the lane uses
+    bool live;
+    int64_t wrow;        // the column's row of the workspace [gridDim.x, nsplit, columns, D + 2]
+};
+template <bool GQA> __device__ __forceinline__ DecCol dec_column(const DecArgs& a, int j) {
+    DecCol c;
+    const int64_t x = blockIdx.x;
+    const int T = (int)a.T;
+    if constexpr (!GQA) {
+        c.b = x / a.H, c.h = x % a.H, c.kvh = c.h;
+        c.live = j < T;
+        c.t = c.live ? j : T - 1;
+        c.wrow = (x * a.nsplit + blockIdx.y) * T + j;
+    } else {
+        const int64_t per = a.Hkv * a.NP, r = x % per;
+        const int hl = (int)(r % a.NP) * (int)a.HP + j / T;      // the head within its group
+        c.b = x / per, c.kvh = r / a.NP;
+        c.live = j < (int)a.HP * T && hl < (int)a.G;
+        c.h = c.kvh * a.G + (c.live ? hl : 0);
+        c.t = j % T;
+        c.wrow = (x * a.nsplit + blockIdx.y) * (a.HP * T) + j;
+    }
+    return c;
+}
 
 template <bool VEC> __device__ __forceinline__ u32x4_t dec_ld16(const uint16_t* p) {
     if constexpr (VEC) {
@@ -148,10 +179,11 @@ template <int MDT> __device__ __forceinline__ void dec_load_mask(const void* mas
 // whose lane reads the DB codes of one key with one LDS load)
 template <int DB, bool PERM> __device__ __forceinline__ int dec_col(int db, int g, int r) { return PERM ? (4 * g + r) * DB + db : 16 * db + 4 * g + r; }
 
-// the waves' partials into wave 0 through LDS, in wave order, then out (one chunk) or the workspace (more); all waves of the workgroup call
+// the waves' partials into wave 0 through LDS, in wave order, then out (one chunk) or the workspace (more); all waves of the workgroup
+// call.  c: the lane's column
 template <int DT, int D, bool PERM>
 __device__ __forceinline__ void dec_finish(char* smem, float m, float l, f32x4_t (&acc)[D / 16], void* out, float* ws, int64_t H, int64_t T, int nsplit,
-                                           int64_t bh, int64_t b, int64_t h) {
+                                           const DecCol& c) {
     constexpr int DB = D / 16, PART = 4 * DB + 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, g = lane >> 4;
@@ -182,16 +214,16 @@ __device__ __forceinline__ void dec_finish(char* smem, float m, float l, f32x4_t
         dec_merge(m, l, acc, theirs[0], theirs[64], acc1);
     }
     l = dec_sum_groups(l);
-    if (j >= T) return;
+    if (!c.live) return;
     if (nsplit == 1) {
-        const int64_t o = ((b * T + j) * H + h) * D;
+        const int64_t o = ((c.b * T + c.t) * H + c.h) * D;
 #pragma unroll
         for (int db = 0; db < DB; ++db) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) Ty<DT>::store1(out, o + dec_col<DB, PERM>(db, g, r), acc[db][r] / l);
         }
     } else {
-        float* w = ws + ((bh * nsplit + blockIdx.y) * T + j) * (D + 2);
+        float* w = ws + c.wrow * (D + 2);
         if (g == 0) {
             w[0] = m;
             w[1] = l;
@@ -204,8 +236,9 @@ __device__ __forceinline__ void dec_finish(char* smem, float m, float l, f32x4_t
     }
 }
 
-template <int DT, int MDT, int D, bool VEC>
-__global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
+// the whole workgroup's work under either column map; dec_kernel and the grouped kernel (fq_attn_gqa.h) are this body
+template <int DT, int MDT, int D, bool VEC, bool GQA>
+__device__ __forceinline__ void dec_body(const DecArgs& a) {
     static_assert(D == 64 || D == 128, "head sizes served");
     constexpr int KS = D / 32;                  // k-steps of a score tile
     constexpr int DB = D / 16;                  // 16-column blocks of the output
@@ -220,17 +253,17 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, g = lane >> 4;
-    const int64_t bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
+    const DecCol col = dec_column<GQA>(a, j);       // the lane's query row (dead columns: zero q, never stored)
+    const int64_t b = col.b;
     const int64_t S = a.S, last = S - 1;
     const int64_t t0 = (int64_t)blockIdx.y * a.per;
     const int64_t nt = (S + DEC_TILE - 1) / DEC_TILE;
     const int64_t t1 = t0 + a.per < nt ? t0 + a.per : nt;
-    const int tq = j < a.T ? j : (int)a.T - 1;      // the query row whose addresses the lane uses (rows >= T: zero q, never stored)
 
-    const uint16_t* qp = (const uint16_t*)a.q + b * a.qs[0] + h * a.qs[1] + tq * a.qs[2] + 8 * g;
-    const uint16_t* kp = (const uint16_t*)a.k + b * a.ks[0] + h * a.ks[1] + 8 * g;
-    const uint16_t* vp = (const uint16_t*)a.v + b * a.vs[0] + h * a.vs[1] + 8 * (lane % LPR);
-    const int64_t mb = MDT == ATTN_NOMASK ? 0 : b * a.mbs + tq * a.mrs;
+    const uint16_t* qp = (const uint16_t*)a.q + b * a.qs[0] + col.h * a.qs[1] + col.t * a.qs[2] + 8 * g;
+    const uint16_t* kp = (const uint16_t*)a.k + b * a.ks[0] + col.kvh * a.ks[1] + 8 * g;
+    const uint16_t* vp = (const uint16_t*)a.v + b * a.vs[0] + col.kvh * a.vs[1] + 8 * (lane % LPR);
+    const int64_t mb = MDT == ATTN_NOMASK ? 0 : b * a.mbs + col.t * a.mrs;
     const int vrow = lane / LPR;
     char* stage = smem + wave * STAGE;
 
@@ -238,7 +271,7 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const u32x4_t x = dec_ld16<VEC>(qp + 32 * ks);
-        qf[ks] = j < a.T ? x : (u32x4_t){0u, 0u, 0u, 0u};
+        qf[ks] = col.live ? x : (u32x4_t){0u, 0u, 0u, 0u};
     }
 
     auto load_k = [&](int64_t tile, u32x4_t(&kr)[2 * KS]) {
@@ -307,19 +340,19 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) {
         }
     }
 
-    dec_finish<DT, D, false>(smem, m, l, acc, a.out, a.ws, a.H, a.T, a.nsplit, bh, b, h);
+    dec_finish<DT, D, false>(smem, m, l, acc, a.out, a.ws, a.H, a.T, a.nsplit, col);
 }
+
+template <int DT, int MDT, int D, bool VEC> __global__ __launch_bounds__(DEC_WAVES * 64) void dec_kernel(DecArgs a) { dec_body<DT, MDT, D, VEC, false>(a); }
 
 // the chunks of one (batch, head, query row) into out, in chunk order: grid (B * H, T), D threads, thread d owns out[.., d].  The chunks'
 // (m, l) come in with one load per thread through LDS and the accumulator loads run eight at a time: read one after the other, 2 x 16
 // dependent loads of another kernel's fresh output made this kernel as long as the stream it follows
-template <int DT> __global__ __launch_bounds__(128) void dec_combine_kernel(const float* ws, void* out, int64_t H, int64_t T, int D, int nsplit) {
+// w: the row's partial of chunk 0, chunk s `step` floats further; o: the row's element of out
+template <int DT> __device__ __forceinline__ void dec_combine(const float* w, int64_t step, void* out, int64_t o, int nsplit) {
     static_assert(DEC_MAX_SPLIT <= 64, "a thread per chunk in the smallest block (D = 64)");
     __shared__ float cm[DEC_MAX_SPLIT], cl[DEC_MAX_SPLIT];
-    const int64_t bh = blockIdx.x, b = bh / H, h = bh % H, t = blockIdx.y;
     const int d = threadIdx.x;                              // the block is D threads, nsplit <= DEC_MAX_SPLIT <= D
-    const int64_t row = D + 2, step = T * row;
-    const float* w = ws + (bh * nsplit * T + t) * row;      // chunk s: + s * step
     if (d < nsplit) {
         cm[d] = w[d * step];
         cl[d] = w[d * step + 1];
@@ -335,7 +368,12 @@ template <int DT> __global__ __launch_bounds__(128) void dec_combine_kernel(cons
         l += cl[s] * f;
         acc += w[s * step + 2 + d] * f;
     }
-    Ty<DT>::store1(out, ((b * T + t) * H + h) * D + d, acc / l);
+    Ty<DT>::store1(out, o + d, acc / l);
+}
+template <int DT> __global__ __launch_bounds__(128) void dec_combine_kernel(const float* ws, void* out, int64_t H, int64_t T, int D, int nsplit) {
+    const int64_t bh = blockIdx.x, b = bh / H, h = bh % H, t = blockIdx.y;
+    const int64_t row = D + 2, step = T * row;
+    dec_combine<DT>(ws + (bh * nsplit * T + t) * row, step, out, ((b * T + t) * H + h) * D, nsplit);
 }
 
 }  // namespace fq

@@ -85,8 +85,9 @@ template <int D, int CB> constexpr int kvd_smem_bytes() {
     return stage > merge ? stage : merge;
 }
 
-template <int DT, int MDT, int D, int CB, bool ROT, bool VEC>
-__global__ __launch_bounds__(DEC_WAVES * 64) void kvd_kernel(KvdArgs ka) {
+// the whole workgroup's work under either column map (dec_column); kvd_kernel and the grouped kernel (fq_attn_gqa.h) are this body
+template <int DT, int MDT, int D, int CB, bool ROT, bool VEC, bool GQA>
+__device__ __forceinline__ void kvd_body(const KvdArgs& ka) {
     static_assert((D == 64 || D == 128) && (CB == 8 || CB == 4), "head sizes and containers served");
     using T = Ty<DT>;
     constexpr int KS = D / 32;                  // k-steps of a score tile
@@ -107,20 +108,20 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void kvd_kernel(KvdArgs ka) {
     const DecArgs& a = ka.d;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, g = lane >> 4;
-    const int64_t bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
+    const DecCol col = dec_column<GQA>(a, j);
+    const int64_t b = col.b;
     const int64_t S = a.S, last = S - 1;
     const int64_t t0 = (int64_t)blockIdx.y * a.per;
     const int64_t nt = (S + DEC_TILE - 1) / DEC_TILE;
     const int64_t t1 = t0 + a.per < nt ? t0 + a.per : nt;
-    const int tq = j < a.T ? j : (int)a.T - 1;
 
-    const uint16_t* qp = (const uint16_t*)a.q + b * a.qs[0] + h * a.qs[1] + tq * a.qs[2] + HB * g;
-    const uint8_t* kp = (const uint8_t*)a.k + b * a.ks[0] + h * a.ks[1] + HB * g * CB / 8;
-    const uint8_t* vp = (const uint8_t*)a.v + b * a.vs[0] + h * a.vs[1] + 16 * (lane % LPR);
+    const uint16_t* qp = (const uint16_t*)a.q + b * a.qs[0] + col.h * a.qs[1] + col.t * a.qs[2] + HB * g;
+    const uint8_t* kp = (const uint8_t*)a.k + b * a.ks[0] + col.kvh * a.ks[1] + HB * g * CB / 8;
+    const uint8_t* vp = (const uint8_t*)a.v + b * a.vs[0] + col.kvh * a.vs[1] + 16 * (lane % LPR);
     const float* kt2 = ka.kt2 + b * ka.kt2_bs;
     const float* vt2 = ka.vt2 + b * ka.vt2_bs;
     const int64_t* pos = ka.pos ? ka.pos + b * ka.pos_bs : nullptr;
-    const int64_t mb = MDT == ATTN_NOMASK ? 0 : b * a.mbs + tq * a.mrs;
+    const int64_t mb = MDT == ATTN_NOMASK ? 0 : b * a.mbs + col.t * a.mrs;
     const int vrow = lane / LPR;
     char* stage = smem + wave * STAGE;
     float2* vscale = (float2*)(stage + DEC_TILE * RS);
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void kvd_kernel(KvdArgs ka) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const u32x4_t x = dec_ld16<VEC>(qp + (8 * ks / HB) * (D / 2) + 8 * ks % HB);
-        qf[ks] = j < a.T ? x : (u32x4_t){0u, 0u, 0u, 0u};
+        qf[ks] = col.live ? x : (u32x4_t){0u, 0u, 0u, 0u};
     }
 
     struct KRaw {                               // what the K operand of one tile is made of, per 16-key half: [hf]
@@ -299,7 +300,10 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void kvd_kernel(KvdArgs ka) {
             make_k(rn, kf);
         }
     }
-    dec_finish<DT, D, true>(smem, m, l, acc, a.out, a.ws, a.H, a.T, a.nsplit, bh, b, h);
+    dec_finish<DT, D, true>(smem, m, l, acc, a.out, a.ws, a.H, a.T, a.nsplit, col);
 }
+
+template <int DT, int MDT, int D, int CB, bool ROT, bool VEC>
+__global__ __launch_bounds__(DEC_WAVES * 64) void kvd_kernel(KvdArgs ka) { kvd_body<DT, MDT, D, CB, ROT, VEC, false>(ka); }
 
 }  // namespace fq

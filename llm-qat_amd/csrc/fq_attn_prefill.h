@@ -56,6 +56,7 @@ struct PreArgs {
     int64_t mbs, mrs;
     int64_t H, T, S;
     float inv;
+    int64_t G;           // query heads of a K/V head, read by the GQA instantiations alone (fq_attn_gqa.hip): k, v are [B, H / G, S, D]
     float* stats;        // [B, H, T, 2]: (m, l) of each real row; read by the STATS instantiations alone (fq_attn_train.hip), nullptr: not written
 };
 
@@ -88,7 +89,8 @@ template <int D> constexpr int pre_row_bytes() { return 2 * D + 16; }
 
 // MDT: the mask's dtype or ATTN_NOMASK; CAUSAL only beside ATTN_NOMASK.  RB: 16-row blocks of a wave.  VEC / MVEC: 16-byte loads of
 // q, k, v / vector loads of the mask.  STATS: the row's maximum and the group-reduced sum go to a.stats behind the walk (the training forward)
-template <int DT, int MDT, bool CAUSAL, int D, int RB, bool VEC, bool MVEC, bool STATS = false>
+// GQA: K and V come from head h / a.G; nothing else moves
+template <int DT, int MDT, bool CAUSAL, int D, int RB, bool VEC, bool MVEC, bool STATS = false, bool GQA = false>
 __global__ __launch_bounds__(PRE_WAVES * 64, 2) void pre_kernel(PreArgs a) {
     static_assert(D == 64 || D == 128, "head sizes served");
     static_assert(!CAUSAL || MDT == ATTN_NOMASK, "the causal mode reads no mask");
@@ -119,8 +121,9 @@ __global__ __launch_bounds__(PRE_WAVES * 64, 2) void pre_kernel(PreArgs a) {
         wnt = w0 < T ? (S - T + wl) / PRE_KT + 1 : 0;
     }
 
-    const uint16_t* kp = (const uint16_t*)a.k + b * a.ks[0] + h * a.ks[1] + 8 * (tid % LPR);
-    const uint16_t* vp = (const uint16_t*)a.v + b * a.vs[0] + h * a.vs[1] + 8 * (tid % LPR);
+    const int64_t kvh = GQA ? h / a.G : h;
+    const uint16_t* kp = (const uint16_t*)a.k + b * a.ks[0] + kvh * a.ks[1] + 8 * (tid % LPR);
+    const uint16_t* vp = (const uint16_t*)a.v + b * a.vs[0] + kvh * a.vs[1] + 8 * (tid % LPR);
     const int lrow = tid / LPR, lcol = 16 * (tid % LPR);
 
     u32x4_t qf[RB][KS];

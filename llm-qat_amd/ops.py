@@ -2125,8 +2125,9 @@ def check_attn_decode(q, k, v, attention_mask=None, head_dim=None, scale=None, w
     """The argument checks of the decode attention on types, shapes, dtypes and devices alone (the fake implementation of the compiled op
     runs them too) -> (B, H, T, S, D, inv): TypeError for a non-tensor, q / k / v that do not share bfloat16 or float16, a mask whose dtype
     is neither theirs nor float32, a head_dim / scale of the wrong type or both or neither; ValueError for a q that is not a non-empty
-    [B, H, T, D] with T <= 16 and D of 64 or 128, k / v that are not one non-empty [B, H, S, D], a mask that is not [B, 1, T, S] or
-    [1, 1, T, S], tensors on two devices.  max_t=None: any T (check_attn_prefill)."""
+    [B, H, T, D] with T <= 16 and D of 64 or 128, k / v that are not one non-empty [B, Hkv, S, D] with Hkv dividing H (grouped-query
+    attention: query head h reads K/V head h // (H // Hkv); Hkv is k.shape[1]), a mask that is not [B, 1, T, S] or [1, 1, T, S], tensors
+    on two devices.  max_t=None: any T (check_attn_prefill)."""
     _row_tensors(what, q=q, k=k, v=v)
     if attention_mask is not None:
         _row_tensors(what, attention_mask=attention_mask)
@@ -2138,8 +2139,9 @@ def check_attn_decode(q, k, v, attention_mask=None, head_dim=None, scale=None, w
     if q.dim() != 4 or q.numel() == 0 or (max_t is not None and q.shape[2] > max_t) or q.shape[3] not in DECODE_HEAD_DIMS:
         raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with {'' if max_t is None else f'T <= {max_t} and '}D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
     B, H, T, D = q.shape
-    if k.dim() != 4 or k.shape[2] == 0 or tuple(k.shape) != (B, H, k.shape[2], D) or tuple(v.shape) != tuple(k.shape):
-        raise ValueError(f"{what}: k and v are one non-empty [{B}, {H}, S, {D}], got {tuple(k.shape)} and {tuple(v.shape)}")
+    if (k.dim() != 4 or k.shape[2] == 0 or tuple(k.shape) != (B, k.shape[1], k.shape[2], D) or k.shape[1] == 0 or H % k.shape[1] != 0
+            or tuple(v.shape) != tuple(k.shape)):
+        raise ValueError(f"{what}: k and v are one non-empty [{B}, Hkv, S, {D}] with Hkv dividing H = {H}, got {tuple(k.shape)} and {tuple(v.shape)}")
     S = k.shape[2]
     if attention_mask is not None and (attention_mask.dim() != 4 or tuple(attention_mask.shape[1:]) != (1, T, S) or attention_mask.shape[0] not in (1, B)):
         raise ValueError(f"{what}: the mask is [{B}, 1, {T}, {S}] or [1, 1, {T}, {S}], got {tuple(attention_mask.shape)}")
@@ -2153,10 +2155,16 @@ def _decode_cus(t):
     return torch.cuda.get_device_properties(t.device).multi_processor_count
 
 
-def attn_decode_workspace(B, H, T, D, S, cus, dtype=torch.bfloat16):
-    """-> (bytes, nsplit): the workspace fqd_attn_decode_fwd needs for this shape on a device of `cus` compute units, and the chunks it cuts S into"""
+def attn_decode_workspace(B, H, T, D, S, cus, dtype=torch.bfloat16, kv_heads=None):
+    """-> (bytes, nsplit): the workspace fqd_attn_decode_fwd needs for this shape on a device of `cus` compute units, and the chunks it cuts
+    S into; kv_heads other than None or H: fqh_attn_decode_fwd's for k, v of that many heads"""
     nbytes, nsplit = ctypes.c_size_t(0), ctypes.c_int64(0)
-    _lib.check(_lib.lib().fqd_attn_decode_workspace(B, H, T, D, S, cus, _OUT_DTYPES[dtype], ctypes.byref(nbytes), ctypes.byref(nsplit)), "attn_decode_workspace")
+    out = (_OUT_DTYPES[dtype], ctypes.byref(nbytes), ctypes.byref(nsplit))
+    if kv_heads is None or kv_heads == H:
+        rc = _lib.lib().fqd_attn_decode_workspace(B, H, T, D, S, cus, *out)
+    else:
+        rc = _lib.lib().fqh_attn_decode_workspace(B, H, kv_heads, T, D, S, cus, *out)
+    _lib.check(rc, "attn_decode_workspace")
     return nbytes.value, nsplit.value
 
 
@@ -2165,8 +2173,11 @@ def attn_decode_forward(q, k, v, attention_mask=None, head_dim=None, scale=None)
     finfo.min), -1, float32) v for T <= 16 query rows as one stream over k and v, with the chain's roundings in front of the softmax and
     an online fp32 softmax behind them.  q [B, H, T, D], k, v [B, H, S, D] in one of bfloat16, float16, D 64 or
     128, read where they lie through their strides (a last stride that is not 1 is copied once: copy_route); the mask [B, 1, T, S] or
-    [1, 1, T, S] in their dtype or float32.  Forward only.  One launch, two where S is cut into chunks (fwd_launch counts calls)."""
+    [1, 1, T, S] in their dtype or float32.  Forward only.  One launch, two where S is cut into chunks (fwd_launch counts calls).
+    k, v of Hkv < H heads (H % Hkv == 0): grouped-query attention, query head h over K/V head h // (H // Hkv), by the kernel that packs
+    the heads of a group into one workgroup and reads k and v once for them."""
     B, H, T, S, D, inv = check_attn_decode(q, k, v, attention_mask, head_dim, scale)
+    Hkv = k.shape[1]
     _prep(q, "attn_decode_forward")
     served = []
     for t in (q.detach(), k.detach(), v.detach()):
@@ -2180,12 +2191,13 @@ def attn_decode_forward(q, k, v, attention_mask=None, head_dim=None, scale=None)
         attention_mask = attention_mask.contiguous()
     mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
     cus = _decode_cus(q)
-    nbytes, _ = attn_decode_workspace(B, H, T, D, S, cus, q.dtype)
+    nbytes, _ = attn_decode_workspace(B, H, T, D, S, cus, q.dtype, Hkv)
     out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if nbytes else None
-    rc = _launch(q, _lib.lib().fqd_attn_decode_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
+    fn, heads = (_lib.lib().fqd_attn_decode_fwd, (H,)) if Hkv == H else (_lib.lib().fqh_attn_decode_fwd, (H, Hkv))
+    rc = _launch(q, fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
                  out.data_ptr(), ws.data_ptr() if nbytes else None, nbytes, *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], mbs, mrs,
-                 B, H, T, S, D, cus, inv, _OUT_DTYPES[q.dtype], mcode)
+                 B, *heads, T, S, D, cus, inv, _OUT_DTYPES[q.dtype], mcode)
     _lib.check(rc, "attn_decode_forward")
     decode_counts["fwd_launch"] += 1
     return out
@@ -2212,7 +2224,7 @@ def check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, he
     of the compiled op runs them too) -> (B, H, T, S, D, inv, container, P): TypeError for a non-tensor, a q that is not bfloat16 or
     float16, codes whose dtype is not num_bits' container's, divisors that are not float32, a mask or tables of a dtype that is not served,
     positions that are not int64, a rotary that is not a (cos, sin) pair; ValueError for a q that is not a non-empty [B, H, T, D] with
-    T <= 16 and D of 64 or 128, codes that are not one [B, H, S, D] (int4: D / 2), divisors that are not [B, S], a mask, tables or
+    T <= 16 and D of 64 or 128, codes that are not one [B, Hkv, S, D] (int4: D / 2) with Hkv dividing H, divisors that are not [B, S], a mask, tables or
     positions of another shape, positions without tables, S > P where no positions are given, tensors on two devices.  P: 0 without tables."""
     _row_tensors(what, q=q, k_codes=k_codes, k_t2=k_t2, v_codes=v_codes, v_t2=v_t2)
     if attention_mask is not None:
@@ -2233,8 +2245,10 @@ def check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, he
     if q.dim() != 4 or q.numel() == 0 or q.shape[2] > DECODE_MAX_T or q.shape[3] not in DECODE_HEAD_DIMS:
         raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with T <= {DECODE_MAX_T} and D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
     B, H, T, D = q.shape
-    if k_codes.dim() != 4 or k_codes.shape[2] == 0 or tuple(k_codes.shape) != (B, H, k_codes.shape[2], D // per) or tuple(v_codes.shape) != tuple(k_codes.shape):
-        raise ValueError(f"{what}: the {container} codes of k and v are one non-empty [{B}, {H}, S, {D // per}], got {tuple(k_codes.shape)} and {tuple(v_codes.shape)}")
+    if (k_codes.dim() != 4 or k_codes.shape[2] == 0 or tuple(k_codes.shape) != (B, k_codes.shape[1], k_codes.shape[2], D // per) or k_codes.shape[1] == 0
+            or H % k_codes.shape[1] != 0 or tuple(v_codes.shape) != tuple(k_codes.shape)):
+        raise ValueError(f"{what}: the {container} codes of k and v are one non-empty [{B}, Hkv, S, {D // per}] with Hkv dividing H = {H}, got "
+                         f"{tuple(k_codes.shape)} and {tuple(v_codes.shape)}")
     S = k_codes.shape[2]
     if tuple(k_t2.shape) != (B, S) or tuple(v_t2.shape) != (B, S):
         raise ValueError(f"{what}: the divisors are [{B}, {S}], one per token, got {tuple(k_t2.shape)} and {tuple(v_t2.shape)}")
@@ -2254,12 +2268,16 @@ def check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, he
     return B, H, T, S, D, inv, container, P
 
 
-def attn_kvdecode_workspace(B, H, T, D, S, cus, dtype=torch.bfloat16, num_bits=8):
+def attn_kvdecode_workspace(B, H, T, D, S, cus, dtype=torch.bfloat16, num_bits=8, kv_heads=None):
     """-> (bytes, nsplit): the workspace fqk_attn_kvdecode_fwd needs for this shape on a device of `cus` compute units, and the chunks it
-    cuts S into (attn_decode_workspace's split)"""
+    cuts S into (attn_decode_workspace's split); kv_heads other than None or H: fqh_attn_kvdecode_fwd's for codes of that many heads"""
     nbytes, nsplit = ctypes.c_size_t(0), ctypes.c_int64(0)
-    _lib.check(_lib.lib().fqk_attn_kvdecode_workspace(B, H, T, D, S, cus, _OUT_DTYPES[dtype], _KV_CONTAINERS[kv_container(num_bits)][1],
-                                                      ctypes.byref(nbytes), ctypes.byref(nsplit)), "attn_kvdecode_workspace")
+    out = (_OUT_DTYPES[dtype], _KV_CONTAINERS[kv_container(num_bits)][1], ctypes.byref(nbytes), ctypes.byref(nsplit))
+    if kv_heads is None or kv_heads == H:
+        rc = _lib.lib().fqk_attn_kvdecode_workspace(B, H, T, D, S, cus, *out)
+    else:
+        rc = _lib.lib().fqh_attn_kvdecode_workspace(B, H, kv_heads, T, D, S, cus, *out)
+    _lib.check(rc, "attn_kvdecode_workspace")
     return nbytes.value, nsplit.value
 
 
@@ -2268,8 +2286,11 @@ def attn_kvdecode_forward(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, 
     materialised.  The codes [B, H, S, D] (int8; num_bits <= 4: uint8 [B, H, S, D / 2], two nibbles a byte) are read
     where they lie through their strides; k_t2, v_t2 fp32 [B, S]; rotary None or (cos, sin) tables [P, D] / [1, 1, P, D] in q's dtype or
     float32 (rounded to q's dtype first); key_positions int64 [B, S] or [1, S], None: the key index.  A last stride that is not 1, tables
-    that are not in q's dtype or not dense and positions that are not dense take one counted copy (copy_route).  Forward only."""
+    that are not in q's dtype or not dense and positions that are not dense take one counted copy (copy_route).  Forward only.
+    Codes of Hkv < H heads (H % Hkv == 0): grouped-query attention as in attn_decode_forward; the heads of a group share one
+    dequantisation and rotation of K."""
     B, H, T, S, D, inv, container, P = check_attn_kvdecode(q, k_codes, k_t2, v_codes, v_t2, attention_mask, head_dim, scale, num_bits, rotary, key_positions)
+    Hkv = k_codes.shape[1]
     _prep(q, "attn_kvdecode_forward")
 
     def dense(t, ok):
@@ -2289,13 +2310,14 @@ def attn_kvdecode_forward(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, 
             pos = dense(key_positions, key_positions.stride(-1) == 1 or S == 1)
             pbs = pos.stride(0) if pos.shape[0] == B and B > 1 else 0
     cus = _decode_cus(q)
-    nbytes, _ = attn_kvdecode_workspace(B, H, T, D, S, cus, q.dtype, num_bits)
+    nbytes, _ = attn_kvdecode_workspace(B, H, T, D, S, cus, q.dtype, num_bits, Hkv)
     out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if nbytes else None
     ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-    rc = _launch(q, _lib.lib().fqk_attn_kvdecode_fwd, q.data_ptr(), k_codes.data_ptr(), k_t2.data_ptr(), v_codes.data_ptr(), v_t2.data_ptr(), ptr(mask),
+    fn, heads = (_lib.lib().fqk_attn_kvdecode_fwd, (H,)) if Hkv == H else (_lib.lib().fqh_attn_kvdecode_fwd, (H, Hkv))
+    rc = _launch(q, fn, q.data_ptr(), k_codes.data_ptr(), k_t2.data_ptr(), v_codes.data_ptr(), v_t2.data_ptr(), ptr(mask),
                  ptr(cos), ptr(sin), ptr(pos), out.data_ptr(), ptr(ws), nbytes, *q.stride()[:3], *k_codes.stride()[:3], *v_codes.stride()[:3],
-                 k_t2.stride(0) if B > 1 else 0, v_t2.stride(0) if B > 1 else 0, mbs, mrs, pbs, P, B, H, T, S, D, cus, inv, _OUT_DTYPES[q.dtype], mcode,
+                 k_t2.stride(0) if B > 1 else 0, v_t2.stride(0) if B > 1 else 0, mbs, mrs, pbs, P, B, *heads, T, S, D, cus, inv, _OUT_DTYPES[q.dtype], mcode,
                  _KV_CONTAINERS[container][1])
     _lib.check(rc, "attn_kvdecode_forward")
     kvdecode_counts["fwd_launch"] += 1
@@ -2343,8 +2365,10 @@ def attn_prefill_forward(q, k, v, attention_mask=None, head_dim=None, scale=None
     exists.  q [B, H, T, D], k, v [B, H, S, D] in one of bfloat16, float16, D 64 or 128, read where they lie through their strides (a
     last stride that is not 1 is copied once: copy_route); the mask [B, 1, T, S] or [1, 1, T, S] in their dtype or float32.
     causal=True (no mask, T <= S): row t attends to keys s <= S - T + t; nothing is read for it and key tiles past a workgroup's last
-    row are skipped.  Forward only.  One launch (fwd_launch)."""
+    row are skipped.  Forward only.  One launch (fwd_launch).  k, v of Hkv < H heads (H % Hkv == 0): grouped-query attention by head
+    mapping, the bits of the call on the repeated k, v."""
     B, H, T, S, D, inv = check_attn_prefill(q, k, v, attention_mask, head_dim, scale, causal)
+    Hkv = k.shape[1]
     _prep(q, "attn_prefill_forward")
     served = []
     for t in (q.detach(), k.detach(), v.detach()):
@@ -2358,8 +2382,9 @@ def attn_prefill_forward(q, k, v, attention_mask=None, head_dim=None, scale=None
         attention_mask = attention_mask.contiguous()
     mask, mbs, mrs, mcode = _attn_mask(attention_mask, B, T)
     out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
-    rc = _launch(q, _lib.lib().fqp_attn_prefill_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
-                 out.data_ptr(), *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], mbs, mrs, B, H, T, S, D, inv, _OUT_DTYPES[q.dtype], mcode,
+    fn, heads = (_lib.lib().fqp_attn_prefill_fwd, (H,)) if Hkv == H else (_lib.lib().fqh_attn_prefill_fwd, (H, Hkv))
+    rc = _launch(q, fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr() if mask is not None else None,
+                 out.data_ptr(), *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], mbs, mrs, B, *heads, T, S, D, inv, _OUT_DTYPES[q.dtype], mcode,
                  int(causal))
     _lib.check(rc, "attn_prefill_forward")
     prefill_counts["fwd_launch"] += 1
@@ -2375,8 +2400,11 @@ TRAIN_DQ_QT, TRAIN_DQ_KT, TRAIN_DKV_KT, TRAIN_DKV_QT = 128, 32, 64, 32
 
 def check_attn_train(q, k, v, attention_mask=None, head_dim=None, scale=None, causal=False, what="attn_train_forward"):
     """check_attn_prefill's checks -> (B, H, T, S, D, inv), and: ValueError for a mask that requires grad (the kernels compute no gradient
-    for it)."""
+    for it) and for k, v of fewer heads than q (grouped-query attention has no fused backward)."""
     geom = check_attn_prefill(q, k, v, attention_mask, head_dim, scale, causal, what)
+    if k.shape[1] != geom[1]:
+        raise ValueError(f"{what}: k and v of {k.shape[1]} heads beside q of {geom[1]}: grouped-query attention is served forward only (decode, "
+                         f"codes cache, prefill); for a gradient expand k and v with repeat_interleave({geom[1] // k.shape[1]}, dim=1)")
     if attention_mask is not None and attention_mask.requires_grad:
         raise ValueError(f"{what}: a mask that requires grad is not served (the kernels compute no gradient for it)")
     return geom
