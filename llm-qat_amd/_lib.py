@@ -60,6 +60,8 @@ ATTN_TRAIN_EXPORTS = ("fqg_attn_train_fwd", "fqg_attn_train_bwd")
 KVDECODE_SYMBOLS = ("fqk_attn_kvdecode_workspace", "fqk_attn_kvdecode_fwd")
 # every symbol include/llmqat_fakequant_attn_gqa.h declares (the fqh_ family: the decode, codes-cache and prefill attention over fewer K/V heads)
 GQA_SYMBOLS = ("fqh_attn_decode_workspace", "fqh_attn_decode_fwd", "fqh_attn_kvdecode_workspace", "fqh_attn_kvdecode_fwd", "fqh_attn_prefill_fwd")
+# every symbol include/llmqat_fakequant_attn_cached.h declares (the fqu_ family: the decode attention over an in-place cache with device lengths)
+CACHED_SYMBOLS = ("fqu_attn_cached_workspace", "fqu_attn_cached_fwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -242,7 +244,9 @@ def _bind(L):
     L.fqh_attn_kvdecode_workspace.argtypes = [i64] * 7 + [i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
     L.fqh_attn_kvdecode_fwd.argtypes = [vp] * 11 + [sz] + [i64] * 22 + [f32, i32, i32, i32, vp]
     L.fqh_attn_prefill_fwd.argtypes = [vp] * 5 + [i64] * 17 + [f32, i32, i32, i32, vp]
-    for name in GQA_SYMBOLS:
+    L.fqu_attn_cached_workspace.argtypes = [i64] * 7 + [i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.fqu_attn_cached_fwd.argtypes = [vp] * 9 + [sz] + [i64] * 22 + [f32, i32, vp]
+    for name in GQA_SYMBOLS + CACHED_SYMBOLS:
         getattr(L, name).restype = i32
     return L
 

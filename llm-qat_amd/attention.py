@@ -15,6 +15,8 @@ but the scores, the mask and two floats per row.
 
 decode_attention fuses the two products as well where a few new tokens (T <= 16) attend to a long cache and no gradient is asked for
 (DESIGN.md section 30): one stream over k and v.  install(..., decode=True) / convert(..., decode=True) route such calls to it.
+cached_decode_attention is decode_attention over a preallocated cache that one launch appends to in place and attends over, with the
+sequence lengths on the device; static_kv_cache makes such a cache from a prompt call's (k, v).
 kv_decode_attention is decode_attention over a cache held as the exported integer codes of the fake-quantized k and v, dequantized and
 rotated in registers; install(..., decode=True, kv_codes=True) makes use_cache=True return such a cache.
 prefill_attention is the same operation for any T, a whole sequence or a long chunk over a cache: the teacher's
@@ -27,7 +29,7 @@ import torch
 
 from . import compiled, cpu_tensors, ops
 
-__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention, kv_decode_attention, prefill_attention and train_attention are public by name
+__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention, cached_decode_attention, static_kv_cache, kv_decode_attention, prefill_attention and train_attention are public by name
 
 
 class _AttnSoftmax(torch.autograd.Function):
@@ -102,6 +104,56 @@ def decode_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None)
     if torch.compiler.is_compiling():
         return compiled.attn_decode(q, k, v, attention_mask, inv).transpose(1, 2)
     return ops.attn_decode_forward(q, k, v, attention_mask, scale=inv).transpose(1, 2)
+
+
+def cached_decode_attention(q, k_new, v_new, k_cache, v_cache, cache_lens, head_dim=None, *, scale=None, cache_starts=None):
+    """decode_attention over a preallocated K/V cache that is appended to IN PLACE, with the sequence lengths on the device (DESIGN.md
+    section 35).  For batch row b with len = cache_lens[b], one launch (1) writes k_new[b], v_new[b] into rows len .. len + T - 1 of
+    k_cache[b], v_cache[b], bit for bit, and (2) lets query row t attend to the keys cache_starts[b] <= s <= len + t of the updated cache:
+    every earlier valid key, causal among the new tokens.  The result is what prefill_attention(q[b], cat(cache[b, :, :len], new[b]), ...,
+    causal=True) defines: the no-mask chain (both roundings in front of the softmax, no clamp), unseen keys -inf behind it, the online
+    fp32 softmax, the rounded exponentials as the second product's operand, one output rounding.  No torch.cat, no mask tensor, and the
+    lengths are never read on the host: the grid and the workspace depend on the shapes alone, so a decode loop launches the same thing
+    every step, and a batch may hold sequences of different lengths.
+
+    q: [B, H, T, D], T <= 16, D of 64 or 128; k_new, v_new: [B, Hkv, T, D], Hkv dividing H, k already rotated, read where they lie (the
+    transposed views of a projection); k_cache, v_cache: [B, Hkv, Smax, D] with a last stride of 1 and any other strides, never copied; all
+    five bfloat16 or all five float16 on one CUDA device, the new tensors not overlapping the caches; cache_lens: int32 [B] on that device;
+    cache_starts: None or int32 [B], keys below it are not seen (left padding).  The contract is 0 <= start <= len and len + T <= Smax; the
+    kernel cannot tell the host, so it clamps: a negative length counts as 0, one above Smax as Smax, and a new row that would land at or
+    past Smax is not stored but still attended to in this call.  cache_lens is NOT advanced: the caller adds T once, after its layers.
+    Give head_dim, or scale=.  -> [B, H, T, D] as a view of [B, T, H, D] memory.  Forward only: a call in which a gradient is required
+    raises.  CPU tensors are refused unless llm_qat_amd.allow_cpu_tensors(True): then torch ops run, without a host read either."""
+    geom = ops.check_attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, head_dim, scale, cache_starts, "cached_decode_attention")
+    if _needs_grad(q, k_new, v_new, k_cache, v_cache):
+        raise RuntimeError("cached_decode_attention: forward only, but an input requires grad: call it under torch.no_grad(), detach the inputs, "
+                           "or use the products around attn_softmax, which have a backward")
+    inv = geom[6]
+    if q.device.type == "cpu":
+        if not cpu_tensors.ENABLED:
+            cpu_tensors.refuse(q, "cached_decode_attention")
+        return cpu_tensors.attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, inv, cache_starts)
+    if torch.compiler.is_compiling():
+        return compiled.attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, cache_starts, inv).transpose(1, 2)
+    return ops.attn_cached_forward(q, k_new, v_new, k_cache, v_cache, cache_lens, scale=inv, cache_starts=cache_starts).transpose(1, 2)
+
+
+def static_kv_cache(k, v, max_len):
+    """(k, v) [B, Hkv, S, D] as a prompt call returned them -> (k_cache, v_cache, cache_lens) for cached_decode_attention: contiguous
+    [B, Hkv, max_len, D] caches holding the prompt's rows in front (the rest zero) and int32 lengths [B], all S, on k's device."""
+    if not isinstance(max_len, int) or isinstance(max_len, bool):
+        raise TypeError(f"static_kv_cache: max_len is an int, got {type(max_len).__name__}")
+    if k.dim() != 4 or k.shape != v.shape or k.dtype != v.dtype or k.device != v.device:
+        raise ValueError(f"static_kv_cache: k and v are one [B, Hkv, S, D] of one dtype on one device, got {tuple(k.shape)} and {tuple(v.shape)}")
+    B, Hkv, S, D = k.shape
+    if max_len < S:
+        raise ValueError(f"static_kv_cache: max_len={max_len} is below the prompt's S={S}")
+    caches = []
+    for t in (k, v):
+        cache = t.new_zeros((B, Hkv, max_len, D))
+        cache[:, :, :S] = t.detach()
+        caches.append(cache)
+    return caches[0], caches[1], torch.full((B,), S, dtype=torch.int32, device=k.device)
 
 
 def kv_decode_attention(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, head_dim=None, *, scale=None, num_bits=8, rotary=None, key_positions=None):

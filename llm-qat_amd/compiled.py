@@ -560,6 +560,24 @@ def attn_decode(q, k, v, mask, inv):
     return attn_decode_op(q, k, v, mask, inv)
 
 
+# ---- the decode attention over an in-place cache (ops.attn_cached_forward): out [B, T, H, D]; the caches are mutated ----
+@torch.library.custom_op("llmqat_amd::attn_cached", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def attn_cached_op(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lens: torch.Tensor,
+                   cache_starts: Optional[torch.Tensor], inv: float) -> torch.Tensor:
+    return ops.attn_cached_forward(q, k_new, v_new, k_cache, v_cache, cache_lens, scale=inv, cache_starts=cache_starts)
+
+
+@attn_cached_op.register_fake
+def _(q, k_new, v_new, k_cache, v_cache, cache_lens, cache_starts, inv):
+    B, H, _, T, _, D, _ = ops.check_attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, scale=inv, cache_starts=cache_starts)
+    return q.new_empty((B, T, H, D))
+
+
+def attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, cache_starts, inv):
+    """attention.cached_decode_attention while compiling -> out [B, T, H, D]"""
+    return attn_cached_op(q, k_new, v_new, k_cache, v_cache, cache_lens, cache_starts, inv)
+
+
 # ---- the decode attention over a codes cache (ops.attn_kvdecode_forward, DESIGN.md section 33): out [B, T, H, D], forward only ---------------
 @torch.library.custom_op("llmqat_amd::attn_kv_decode", mutates_args=(), device_types="cuda")
 def attn_kv_decode_op(q: torch.Tensor, k_codes: torch.Tensor, k_t2: torch.Tensor, v_codes: torch.Tensor, v_t2: torch.Tensor, mask: Optional[torch.Tensor],

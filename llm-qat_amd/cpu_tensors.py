@@ -151,6 +151,30 @@ def attn_prefill(q, k, v, mask, head_dim=None, scale=None, causal=False):
     return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)
 
 
+def attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, inv, cache_starts=None):
+    """cached_decode_attention in torch ops that never read a length on the host: an index_put of the new rows at lens + arange(T) (into
+    the caches extended by T rows, so that a row past Smax has somewhere to go: it takes part and is not kept), the seen / unseen mask
+    from arange against lens and starts, and attn_prefill's causal chain over all Smax + T rows"""
+    B, Hkv, T, D = k_new.shape
+    Smax = k_cache.shape[2]
+    lens = cache_lens.long().clamp(0, Smax)
+    starts = torch.zeros_like(lens) if cache_starts is None else torch.minimum(cache_starts.long().clamp(min=0), lens)
+    rows = lens[:, None] + torch.arange(T, device=q.device)      # [B, T]
+    batch = torch.arange(B, device=q.device)[:, None]
+    full = []
+    for cache, new in ((k_cache, k_new), (v_cache, v_new)):
+        ext = torch.cat([cache, cache.new_zeros((B, Hkv, T, D))], 2)
+        ext[batch, :, rows] = new.transpose(1, 2)
+        cache.copy_(ext[:, :, :Smax])
+        full.append(ext)
+    k, v = _expand_kv(q, *full)
+    attn = torch.matmul(q, k.transpose(2, 3)) * inv
+    col = torch.arange(Smax + T, device=q.device)
+    hidden = (col < starts[:, None, None]) | (col > rows[:, :, None])      # [B, T, Smax + T]
+    p = torch.nn.functional.softmax(attn.float().masked_fill(hidden[:, None], float("-inf")), dim=-1)
+    return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)
+
+
 def _ste(x, dtype):
     """x rounded to `dtype`, in x's own (float64) dtype, with the gradient of the identity"""
     return x + (x.to(dtype).to(x.dtype) - x).detach()

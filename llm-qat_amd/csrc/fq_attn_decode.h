@@ -124,10 +124,11 @@ template <int D> constexpr int dec_stage_bytes() { return DEC_TILE * dec_row_byt
 
 // ---- the stages that dec_kernel and the codes-cache kernel (fq_attn_kvdecode.h) share -----------------------------------------------------
 // the online softmax's step over one tile: sc holds the scores of the lane's eight keys (4 g + r of both halves) of query row j, mk their
-// mask values.  (m, l) and the accumulator move to the new maximum; -> the rounded exponentials as the PV instruction's B operand
-template <int DT, int MDT, int DB>
+// mask values.  (m, l) and the accumulator move to the new maximum; -> the rounded exponentials as the PV instruction's B operand.
+// S may differ between query rows (lanes of another j); LOW (the in-place cache kernel, fq_attn_cached.h): keys below lo are unseen too
+template <int DT, int MDT, int DB, bool LOW = false>
 __device__ __forceinline__ u32x4_t dec_softmax_step(const f32x4_t (&sc)[2], const float (&mk)[8], int64_t tile, int g, int64_t S, float inv, float& m,
-                                                    float& l, f32x4_t (&acc)[DB]) {
+                                                    float& l, f32x4_t (&acc)[DB], int64_t lo = 0) {
     float z[8];
     float tmax = LOSS_NEG_INF;
 #pragma unroll
@@ -135,7 +136,7 @@ __device__ __forceinline__ u32x4_t dec_softmax_step(const f32x4_t (&sc)[2], cons
         const int64_t key = tile * DEC_TILE + 16 * (c >> 2) + 4 * g + (c & 3);
         const float x = Ty<DT>::rb(sc[c >> 2][c & 3]);      // the first product's own rounding
         const float zz = attn_z<DT, MDT>(attn_a<DT, MDT>(x, mk[c], inv));
-        z[c] = key < S ? zz : LOSS_NEG_INF;                 // behind the clamp
+        z[c] = key < S && (!LOW || key >= lo) ? zz : LOSS_NEG_INF;      // behind the clamp
         tmax = __builtin_fmaxf(tmax, z[c]);
     }
     tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, 16));

@@ -2203,6 +2203,94 @@ def attn_decode_forward(q, k, v, attention_mask=None, head_dim=None, scale=None)
     return out
 
 
+# ---- the decode attention over an in-place cache with device lengths (the fqu_ header) ----------------------------------
+cached_counts = {"fwd_launch": 0, "copy_route": 0}
+
+
+def check_attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, head_dim=None, scale=None, cache_starts=None, what="attn_cached_forward"):
+    """The argument checks of the cached decode attention on types, shapes, dtypes and devices alone (the fake implementation of the
+    compiled op runs them too) -> (B, H, Hkv, T, Smax, D, inv): TypeError for a non-tensor, tensors that do not share bfloat16 or float16,
+    lengths / starts that are not int32, a head_dim / scale of the wrong type or both or neither; ValueError for a q that is not a
+    non-empty [B, H, T, D] with T <= 16 and D of 64 or 128, k_new / v_new that are not one [B, Hkv, T, D] with Hkv dividing H, caches
+    that are not one non-empty [B, Hkv, Smax, D] with a last stride of 1 (a copy would defeat the in-place write), lengths / starts that
+    are not [B], tensors on two devices."""
+    named = dict(q=q, k_new=k_new, v_new=v_new, k_cache=k_cache, v_cache=v_cache, cache_lens=cache_lens)
+    if cache_starts is not None:
+        named["cache_starts"] = cache_starts
+    _row_tensors(what, **named)
+    if q.dtype not in _DECODE_DTYPES or any(t.dtype != q.dtype for t in (k_new, v_new, k_cache, v_cache)):
+        raise TypeError(f"{what}: q, k_new, v_new, k_cache, v_cache of {q.dtype}, {k_new.dtype}, {v_new.dtype}, {k_cache.dtype}, {v_cache.dtype} "
+                        "are not served: one of bfloat16, float16 for all five")
+    for name in ("cache_lens", "cache_starts"):
+        if name in named and named[name].dtype != torch.int32:
+            raise TypeError(f"{what}: {name} is an int32 tensor, got {named[name].dtype}")
+    inv = attn_inv(head_dim, scale, what)
+    if q.dim() != 4 or q.numel() == 0 or q.shape[2] > DECODE_MAX_T or q.shape[3] not in DECODE_HEAD_DIMS:
+        raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with T <= {DECODE_MAX_T} and D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
+    B, H, T, D = q.shape
+    Hkv = k_new.shape[1] if k_new.dim() == 4 else 0
+    if Hkv == 0 or H % Hkv != 0 or tuple(k_new.shape) != (B, Hkv, T, D) or tuple(v_new.shape) != (B, Hkv, T, D):
+        raise ValueError(f"{what}: k_new and v_new are one [{B}, Hkv, {T}, {D}] with Hkv dividing H = {H}, got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
+    if k_cache.dim() != 4 or k_cache.shape[2] == 0 or tuple(k_cache.shape) != (B, Hkv, k_cache.shape[2], D) or tuple(v_cache.shape) != tuple(k_cache.shape):
+        raise ValueError(f"{what}: k_cache and v_cache are one non-empty [{B}, {Hkv}, Smax, {D}], got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(-1) != 1:
+            raise ValueError(f"{what}: {name} has a last stride of {t.stride(-1)}: the cache is written in place, so it is not copied; give one with a last stride of 1")
+    for name in ("cache_lens", "cache_starts"):
+        if name in named and tuple(named[name].shape) != (B,):
+            raise ValueError(f"{what}: {name} is [{B}], got {tuple(named[name].shape)}")
+    for name, t in named.items():
+        if t.device != q.device:
+            raise ValueError(f"{what}: q is on {q.device}, {name} on {t.device}")
+    return B, H, Hkv, T, k_cache.shape[2], D, inv
+
+
+def attn_cached_workspace(B, H, T, D, Smax, cus, dtype=torch.bfloat16, kv_heads=None):
+    """-> (bytes, nsplit): the workspace fqu_attn_cached_fwd needs on a device of `cus` compute units and the chunks it cuts every batch
+    row's keys into at most: functions of the shapes alone, never of the lengths"""
+    nbytes, nsplit = ctypes.c_size_t(0), ctypes.c_int64(0)
+    rc = _lib.lib().fqu_attn_cached_workspace(B, H, H if kv_heads is None else kv_heads, T, D, Smax, cus, _OUT_DTYPES[dtype], ctypes.byref(nbytes),
+                                              ctypes.byref(nsplit))
+    _lib.check(rc, "attn_cached_workspace")
+    return nbytes.value, nsplit.value
+
+
+def attn_cached_forward(q, k_new, v_new, k_cache, v_cache, cache_lens, head_dim=None, scale=None, cache_starts=None):
+    """-> out [B, T, H, D] (contiguous): one launch that writes k_new, v_new [B, Hkv, T, D] into rows cache_lens[b] .. + T - 1 of the
+    preallocated k_cache, v_cache [B, Hkv, Smax, D] IN PLACE and attends q [B, H, T, D] to the keys cache_starts[b] <= s <= cache_lens[b] + t
+    of the updated cache, with decode_attention's no-mask arithmetic.  The int32 lengths (and starts) stay on the
+    device: nothing here reads them, and the grid and the workspace depend on the shapes alone.  q, k_new, v_new are read where they lie (a
+    last stride that is not 1, or int32s that are not contiguous, are copied once: copy_route); the caches are never copied.  Forward only."""
+    B, H, Hkv, T, Smax, D, inv = check_attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, head_dim, scale, cache_starts)
+    _prep(q, "attn_cached_forward")
+    served = []
+    for t in (q.detach(), k_new.detach(), v_new.detach()):
+        if t.stride(-1) != 1:
+            cached_counts["copy_route"] += 1
+            t = t.contiguous()
+        served.append(t)
+    q, k_new, v_new = served
+    ints = []
+    for t in (cache_lens, cache_starts):
+        if t is not None and not t.is_contiguous():
+            cached_counts["copy_route"] += 1
+            t = t.contiguous()
+        ints.append(t)
+    lens, starts = ints
+    k_cache, v_cache = k_cache.detach(), v_cache.detach()
+    cus = _decode_cus(q)
+    nbytes, _ = attn_cached_workspace(B, H, T, D, Smax, cus, q.dtype, Hkv)
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if nbytes else None
+    rc = _launch(q, _lib.lib().fqu_attn_cached_fwd, q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                 lens.data_ptr(), starts.data_ptr() if starts is not None else None, out.data_ptr(), ws.data_ptr() if nbytes else None, nbytes,
+                 *q.stride()[:3], *k_new.stride()[:3], *v_new.stride()[:3], *k_cache.stride()[:3], *v_cache.stride()[:3], B, H, Hkv, T, Smax, D,
+                 cus, inv, _OUT_DTYPES[q.dtype])
+    _lib.check(rc, "attn_cached_forward")
+    cached_counts["fwd_launch"] += 1
+    return out
+
+
 # ---- the decode attention over a cache of integer codes (the fqk_ header, DESIGN.md section 33) -----------------------------------------------
 kvdecode_counts = {"fwd_launch": 0, "copy_route": 0, "fallback": 0}
 KV_CODE_MAX_BITS = 8
