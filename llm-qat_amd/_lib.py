@@ -62,6 +62,8 @@ KVDECODE_SYMBOLS = ("fqk_attn_kvdecode_workspace", "fqk_attn_kvdecode_fwd")
 GQA_SYMBOLS = ("fqh_attn_decode_workspace", "fqh_attn_decode_fwd", "fqh_attn_kvdecode_workspace", "fqh_attn_kvdecode_fwd", "fqh_attn_prefill_fwd")
 # every symbol include/llmqat_fakequant_attn_cached.h declares (the fqu_ family: the decode attention over an in-place cache with device lengths)
 CACHED_SYMBOLS = ("fqu_attn_cached_workspace", "fqu_attn_cached_fwd")
+# every symbol include/llmqat_fakequant_attn_cached_codes.h declares (the fqw_ family: the decode attention over an in-place cache of integer codes)
+CACHED_CODES_SYMBOLS = ("fqw_attn_cached_codes_workspace", "fqw_attn_cached_codes_fwd")
 MAX_TENSORS = 4  # tensors per multi-tensor launch
 
 
@@ -246,7 +248,9 @@ def _bind(L):
     L.fqh_attn_prefill_fwd.argtypes = [vp] * 5 + [i64] * 17 + [f32, i32, i32, i32, vp]
     L.fqu_attn_cached_workspace.argtypes = [i64] * 7 + [i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
     L.fqu_attn_cached_fwd.argtypes = [vp] * 9 + [sz] + [i64] * 22 + [f32, i32, vp]
-    for name in GQA_SYMBOLS + CACHED_SYMBOLS:
+    L.fqw_attn_cached_codes_workspace.argtypes = [i64] * 7 + [i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.fqw_attn_cached_codes_fwd.argtypes = [vp] * 15 + [sz] + [i64] * 27 + [f32, i32, i32, vp]
+    for name in GQA_SYMBOLS + CACHED_SYMBOLS + CACHED_CODES_SYMBOLS:
         getattr(L, name).restype = i32
     return L
 

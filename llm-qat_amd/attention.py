@@ -19,6 +19,8 @@ cached_decode_attention is decode_attention over a preallocated cache that one l
 sequence lengths on the device; static_kv_cache makes such a cache from a prompt call's (k, v).
 kv_decode_attention is decode_attention over a cache held as the exported integer codes of the fake-quantized k and v, dequantized and
 rotated in registers; install(..., decode=True, kv_codes=True) makes use_cache=True return such a cache.
+cached_kv_decode_attention is both at once: a preallocated cache of codes and divisors, appended to in place by the launch that attends
+over it; static_kv_codes_cache makes such a cache from a prompt call's codes.
 prefill_attention is the same operation for any T, a whole sequence or a long chunk over a cache: the teacher's
 forward, an evaluation run, the prompt pass of generation.  install(..., prefill=True) / convert(..., prefill=True) route to it.
 train_attention is prefill_attention with a gradient in q, k and v: the student's call.  Its backward recomputes the
@@ -29,7 +31,7 @@ import torch
 
 from . import compiled, cpu_tensors, ops
 
-__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention, cached_decode_attention, static_kv_cache, kv_decode_attention, prefill_attention and train_attention are public by name
+__all__ = ["attn_softmax", "install", "convert"]      # the recorded star-import set; decode_attention, cached_decode_attention, static_kv_cache, kv_decode_attention, cached_kv_decode_attention, static_kv_codes_cache, prefill_attention and train_attention are public by name
 
 
 class _AttnSoftmax(torch.autograd.Function):
@@ -184,6 +186,70 @@ def kv_decode_attention(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, he
         return compiled.attn_kv_decode(q, k_codes, k_t2, v_codes, v_t2, attention_mask, inv, num_bits, cos, sin, key_positions).transpose(1, 2)
     return ops.attn_kvdecode_forward(q, k_codes, k_t2, v_codes, v_t2, attention_mask, scale=inv, num_bits=num_bits, rotary=rotary,
                                      key_positions=key_positions).transpose(1, 2)
+
+
+def cached_kv_decode_attention(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens,
+                               head_dim=None, *, scale=None, num_bits=8, rotary=None, cache_starts=None):
+    """cached_decode_attention over a cache held as kv_decode_attention's integer codes: the preallocated caches are
+    the codes and one float32 divisor per token, appended to IN PLACE, with the sequence lengths on the device.  For batch row b with
+    len = cache_lens[b], one launch (1) writes the new code rows and the new divisors, bit for bit, into rows len .. len + T - 1 of the
+    four caches and (2) lets query row t attend to the keys cache_starts[b] <= s <= len + t of the updated cache.  The operands are
+    kv_decode_attention's, k = rope(rb(code / t2)) and v = rb(code / t2), made in registers; everything behind them is
+    cached_decode_attention's: no mask, no clamp, unseen keys -inf behind the score, the online fp32 softmax.  No torch.cat, no mask tensor,
+    no host read: a decode loop launches the same thing every step.
+
+    q: [B, H, T, D], bfloat16 or float16, T <= 16, D of 64 or 128, read where it lies; k_codes_new, v_codes_new: [B, Hkv, T, D] int8, or for
+    num_bits <= 4 uint8 [B, Hkv, T, D / 2] in ops.sym_export's nibble order, Hkv dividing H, read where they lie (the
+    .view(b, t, nh, -1).transpose(1, 2) of an export's bins); k_t2_new, v_t2_new: float32 [B, T]; k_code_cache, v_code_cache:
+    [B, Hkv, Smax, D or D / 2] with a last stride of 1 and any other strides, never copied; k_t2_cache, v_t2_cache: float32 [B, Smax] with
+    a last stride of 1; cache_lens, cache_starts: int32 [B] on the device, as in cached_decode_attention; rotary: None (the codes are the
+    final key's) or (cos, sin) tables [P, D] / [1, 1, P, D] in q's dtype or float32 with P >= Smax.  Key s of batch row b sits at position
+    s - cache_starts[b], which is what cumulative-sum position ids give under left padding.  There is no positions tensor: a cache of
+    arbitrary positions is out of scope (kv_decode_attention's key_positions serves it, over a torch.cat cache).  The contract is
+    0 <= start <= len and len + T <= Smax; the kernel clamps lengths and starts and never trusts them, and a new row that would land at or
+    past Smax is not stored but still attended to in this call.  cache_lens is NOT advanced.  Give head_dim, or scale=.
+    -> [B, H, T, D] as a view of [B, T, H, D] memory.  Forward only: a call in which a gradient is required raises.  CPU tensors are
+    refused unless llm_qat_amd.allow_cpu_tensors(True): then torch ops run, without a host read either."""
+    geom = ops.check_attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens,
+                                       head_dim, scale, num_bits, rotary, cache_starts, "cached_kv_decode_attention")
+    if _needs_grad(q, k_t2_new, v_t2_new, k_t2_cache, v_t2_cache, *(rotary or ())):
+        raise RuntimeError("cached_kv_decode_attention: forward only, but an input requires grad: call it under torch.no_grad(), detach the inputs, "
+                           "or use the products around attn_softmax, which have a backward")
+    inv = geom[6]
+    if q.device.type == "cpu":
+        if not cpu_tensors.ENABLED:
+            cpu_tensors.refuse(q, "cached_kv_decode_attention")
+        return cpu_tensors.attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens,
+                                             inv, num_bits, rotary, cache_starts)
+    if torch.compiler.is_compiling():
+        cos, sin = rotary if rotary is not None else (None, None)
+        return compiled.attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens,
+                                          cache_starts, inv, num_bits, cos, sin).transpose(1, 2)
+    return ops.attn_cached_codes_forward(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens,
+                                         scale=inv, num_bits=num_bits, rotary=rotary, cache_starts=cache_starts).transpose(1, 2)
+
+
+def static_kv_codes_cache(k_codes, k_t2, v_codes, v_t2, max_len):
+    """The codes cache a prompt call with kv_codes=True returned, k_codes, v_codes [B, Hkv, S, D or D / 2] and k_t2, v_t2 [B, S] ->
+    (k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens) for cached_kv_decode_attention: contiguous [B, Hkv, max_len, ..] code
+    caches and [B, max_len] divisor caches holding the prompt's rows in front (the other codes 0, the other divisors 1) and int32
+    lengths [B], all S, on the codes' device."""
+    if not isinstance(max_len, int) or isinstance(max_len, bool):
+        raise TypeError(f"static_kv_codes_cache: max_len is an int, got {type(max_len).__name__}")
+    if k_codes.dim() != 4 or k_codes.shape != v_codes.shape or k_codes.dtype != v_codes.dtype or k_codes.device != v_codes.device:
+        raise ValueError(f"static_kv_codes_cache: k_codes and v_codes are one [B, Hkv, S, D or D / 2] of one dtype on one device, got {tuple(k_codes.shape)} "
+                         f"and {tuple(v_codes.shape)}")
+    B, Hkv, S, W = k_codes.shape
+    if tuple(k_t2.shape) != (B, S) or tuple(v_t2.shape) != (B, S):
+        raise ValueError(f"static_kv_codes_cache: the divisors are [{B}, {S}], got {tuple(k_t2.shape)} and {tuple(v_t2.shape)}")
+    if max_len < S:
+        raise ValueError(f"static_kv_codes_cache: max_len={max_len} is below the prompt's S={S}")
+    caches = []
+    for codes, t2 in ((k_codes, k_t2), (v_codes, v_t2)):
+        code_cache, t2_cache = codes.new_zeros((B, Hkv, max_len, W)), t2.new_ones((B, max_len))
+        code_cache[:, :, :S], t2_cache[:, :S] = codes.detach(), t2.detach()
+        caches += [code_cache, t2_cache]
+    return (*caches, torch.full((B,), S, dtype=torch.int32, device=k_codes.device))
 
 
 def prefill_attention(q, k, v, attention_mask=None, head_dim=None, *, scale=None, causal=False):

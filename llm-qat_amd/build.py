@@ -13,9 +13,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libllmqat_fakequant.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("fq_api.hip", "fq_bf16.hip", "fq_f32.hip", "fq_f16.hip", "fq_export.hip", "fq_f64.hip", "fq_group.hip", "fq_mx.hip", "fq_mx_gemm.hip", "fq_mx_cols.hip", "fq_mx_sr.hip", "fq_mx_dequant.hip", "fq_kd_loss.hip", "fq_ce_loss.hip", "fq_rms_norm.hip", "fq_swiglu.hip", "fq_rope.hip", "fq_attn_softmax.hip", "fq_attn_decode.hip", "fq_attn_prefill.hip", "fq_attn_train.hip", "fq_attn_kvdecode.hip", "fq_attn_gqa.hip", "fq_attn_cached.hip")]
-DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("fq_kernels.h", "fq_device.h", "fq_launch.h", "fq_shapes.h", "fq_dtype_impl.h", "fq_export.h", "fq_group.h", "fq_mx.h", "fq_mx_gemm.h", "fq_mx_cols.h", "fq_mx_sr.h", "fq_mx_dequant.h", "fq_rows.h", "fq_loss_rows.h", "fq_kd_loss.h", "fq_ce_loss.h", "fq_rms_norm.h", "fq_swiglu.h", "fq_rope.h", "fq_attn_softmax.h", "fq_attn_decode.h", "fq_attn_prefill.h", "fq_attn_train.h", "fq_attn_kvdecode.h", "fq_attn_gqa.h", "fq_attn_cached.h")] + [
-    os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_train.h", "llmqat_fakequant_sr.h", "llmqat_fakequant_infer.h", "llmqat_fakequant_loss.h", "llmqat_fakequant_ce.h", "llmqat_fakequant_norm.h", "llmqat_fakequant_act.h", "llmqat_fakequant_rope.h", "llmqat_fakequant_attn.h", "llmqat_fakequant_attn_decode.h", "llmqat_fakequant_attn_prefill.h", "llmqat_fakequant_attn_train.h", "llmqat_fakequant_attn_kvdecode.h", "llmqat_fakequant_attn_gqa.h", "llmqat_fakequant_attn_cached.h")]
+SOURCES = [os.path.join(CSRC, f) for f in ("fq_api.hip", "fq_bf16.hip", "fq_f32.hip", "fq_f16.hip", "fq_export.hip", "fq_f64.hip", "fq_group.hip", "fq_mx.hip", "fq_mx_gemm.hip", "fq_mx_cols.hip", "fq_mx_sr.hip", "fq_mx_dequant.hip", "fq_kd_loss.hip", "fq_ce_loss.hip", "fq_rms_norm.hip", "fq_swiglu.hip", "fq_rope.hip", "fq_attn_softmax.hip", "fq_attn_decode.hip", "fq_attn_prefill.hip", "fq_attn_train.hip", "fq_attn_kvdecode.hip", "fq_attn_gqa.hip", "fq_attn_cached.hip", "fq_attn_cached_codes.hip")]
+DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("fq_kernels.h", "fq_device.h", "fq_launch.h", "fq_shapes.h", "fq_dtype_impl.h", "fq_export.h", "fq_group.h", "fq_mx.h", "fq_mx_gemm.h", "fq_mx_cols.h", "fq_mx_sr.h", "fq_mx_dequant.h", "fq_rows.h", "fq_loss_rows.h", "fq_kd_loss.h", "fq_ce_loss.h", "fq_rms_norm.h", "fq_swiglu.h", "fq_rope.h", "fq_attn_softmax.h", "fq_attn_decode.h", "fq_attn_prefill.h", "fq_attn_train.h", "fq_attn_kvdecode.h", "fq_attn_gqa.h", "fq_attn_cached.h", "fq_attn_cached_codes.h")] + [
+    os.path.join(os.path.dirname(HERE), "include", h) for h in ("llmqat_fakequant.h", "llmqat_fakequant_train.h", "llmqat_fakequant_sr.h", "llmqat_fakequant_infer.h", "llmqat_fakequant_loss.h", "llmqat_fakequant_ce.h", "llmqat_fakequant_norm.h", "llmqat_fakequant_act.h", "llmqat_fakequant_rope.h", "llmqat_fakequant_attn.h", "llmqat_fakequant_attn_decode.h", "llmqat_fakequant_attn_prefill.h", "llmqat_fakequant_attn_train.h", "llmqat_fakequant_attn_kvdecode.h", "llmqat_fakequant_attn_gqa.h", "llmqat_fakequant_attn_cached.h", "llmqat_fakequant_attn_cached_codes.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",
          "-fPIC", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 # flags of single translation units: the decode attention is compiled without packed fp32 arithmetic.  With it the unit holds 2899
@@ -27,9 +27,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
 # The decode attention over a codes cache shares the decode kernel's softmax step, merge and combine: the decode unit's flag (section 33)
 # The grouped-query unit instantiates the decode, codes and prefill kernel bodies again: their flag (section 34)
 # The in-place cache unit is built on the decode kernel's stages (softmax step, finish, combine): the decode unit's flag (section 35)
+# The in-place codes-cache unit is the same stages again, on the codes kernel's operands: the decode unit's flag (section 36)
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"fq_attn_decode.hip": _NO_PACKED_FP32, "fq_attn_prefill.hip": _NO_PACKED_FP32, "fq_attn_train.hip": _NO_PACKED_FP32,
-              "fq_attn_kvdecode.hip": _NO_PACKED_FP32, "fq_attn_gqa.hip": _NO_PACKED_FP32, "fq_attn_cached.hip": _NO_PACKED_FP32}
+              "fq_attn_kvdecode.hip": _NO_PACKED_FP32, "fq_attn_gqa.hip": _NO_PACKED_FP32, "fq_attn_cached.hip": _NO_PACKED_FP32,
+              "fq_attn_cached_codes.hip": _NO_PACKED_FP32}
 
 
 def up_to_date():

@@ -598,6 +598,30 @@ def attn_kv_decode(q, k_codes, k_t2, v_codes, v_t2, mask, inv, num_bits, cos, si
     return attn_kv_decode_op(q, k_codes, k_t2, v_codes, v_t2, mask, inv, num_bits, cos, sin, key_positions)
 
 
+# ---- the decode attention over an in-place codes cache (ops.attn_cached_codes_forward): the four caches are mutated -----
+@torch.library.custom_op("llmqat_amd::attn_cached_codes", mutates_args=("k_code_cache", "k_t2_cache", "v_code_cache", "v_t2_cache"), device_types="cuda")
+def attn_cached_codes_op(q: torch.Tensor, k_codes_new: torch.Tensor, k_t2_new: torch.Tensor, v_codes_new: torch.Tensor, v_t2_new: torch.Tensor,
+                         k_code_cache: torch.Tensor, k_t2_cache: torch.Tensor, v_code_cache: torch.Tensor, v_t2_cache: torch.Tensor, cache_lens: torch.Tensor,
+                         cache_starts: Optional[torch.Tensor], inv: float, num_bits: int, cos: Optional[torch.Tensor], sin: Optional[torch.Tensor]) -> torch.Tensor:
+    return ops.attn_cached_codes_forward(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens,
+                                         scale=inv, num_bits=num_bits, rotary=None if cos is None else (cos, sin), cache_starts=cache_starts)
+
+
+@attn_cached_codes_op.register_fake
+def _(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens, cache_starts, inv, num_bits, cos, sin):
+    B, H, _, T, _, D, *_ = ops.check_attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache,
+                                                       cache_lens, scale=inv, num_bits=num_bits, rotary=None if cos is None else (cos, sin),
+                                                       cache_starts=cache_starts)
+    return q.new_empty((B, T, H, D))
+
+
+def attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens, cache_starts, inv,
+                      num_bits, cos, sin):
+    """attention.cached_kv_decode_attention while compiling -> out [B, T, H, D]"""
+    return attn_cached_codes_op(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens, cache_starts,
+                                inv, num_bits, cos, sin)
+
+
 # ---- the fused prefill attention (ops.attn_prefill_forward, DESIGN.md section 31): out [B, T, H, D], forward only -----------------------------
 @torch.library.custom_op("llmqat_amd::attn_prefill", mutates_args=(), device_types="cuda")
 def attn_prefill_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], inv: float, causal: bool) -> torch.Tensor:

@@ -175,6 +175,39 @@ def attn_cached(q, k_new, v_new, k_cache, v_cache, cache_lens, inv, cache_starts
     return torch.matmul(p.double(), v.double()).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)
 
 
+def attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens, inv, num_bits,
+                      rotary=None, cache_starts=None):
+    """cached_kv_decode_attention in torch ops that never read a length on the host: attn_cached's index_put of the new code rows and
+    divisors (into caches extended by T rows), the extended caches materialised as attn_kv_decode does with key s at position
+    s - start, and attn_cached's seen / unseen mask and chain over all Smax + T rows"""
+    from . import ops
+    B, Hkv, T, _ = k_codes_new.shape
+    Smax = k_code_cache.shape[2]
+    lens = cache_lens.long().clamp(0, Smax)
+    starts = torch.zeros_like(lens) if cache_starts is None else torch.minimum(cache_starts.long().clamp(min=0), lens)
+    rows = lens[:, None] + torch.arange(T, device=q.device)      # [B, T]
+    batch = torch.arange(B, device=q.device)[:, None]
+    col = torch.arange(Smax + T, device=q.device)
+    full = []
+    for codes, t2, codes_new, t2_new in ((k_code_cache, k_t2_cache, k_codes_new, k_t2_new), (v_code_cache, v_t2_cache, v_codes_new, v_t2_new)):
+        ext = torch.cat([codes, codes.new_zeros((B, Hkv, T, codes.shape[3]))], 2)
+        ext[batch, :, rows] = codes_new.transpose(1, 2)
+        codes.copy_(ext[:, :, :Smax])
+        ext_t2 = torch.cat([t2, t2.new_ones((B, T))], 1)
+        ext_t2[batch, rows] = t2_new
+        t2.copy_(ext_t2[:, :Smax])
+        if rotary is not None and codes is k_code_cache:
+            pos = (col[None] - starts[:, None]).clamp(0, rotary[0].shape[-2] - 1)
+            full.append(ops.kv_codes_materialize(ext, ext_t2, q.dtype, num_bits, rotary, pos))
+        else:
+            full.append(ops.kv_codes_materialize(ext, ext_t2, q.dtype, num_bits))
+    k, v = _expand_kv(q, *full)
+    attn = torch.matmul(q, k.transpose(2, 3)) * inv
+    hidden = (col < starts[:, None, None]) | (col > rows[:, :, None])      # [B, T, Smax + T]
+    p = torch.nn.functional.softmax(attn.float().masked_fill(hidden[:, None], float("-inf")), dim=-1)
+    return torch.matmul(p.double(), v.double().masked_fill(hidden.all(1)[:, None, :, None], 0.0)).to(q.dtype).transpose(1, 2).contiguous().transpose(1, 2)
+
+
 def _ste(x, dtype):
     """x rounded to `dtype`, in x's own (float64) dtype, with the gradient of the identity"""
     return x + (x.to(dtype).to(x.dtype) - x).detach()

@@ -2412,6 +2412,122 @@ def attn_kvdecode_forward(q, k_codes, k_t2, v_codes, v_t2, attention_mask=None, 
     return out
 
 
+# ---- the decode attention over an in-place cache of integer codes with device lengths (the fqw_ header) -----------------
+cached_codes_counts = {"fwd_launch": 0, "copy_route": 0}
+
+
+def check_attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens, head_dim=None,
+                            scale=None, num_bits=8, rotary=None, cache_starts=None, what="attn_cached_codes_forward"):
+    """The argument checks of the cached decode attention over codes on types, shapes, dtypes and devices alone (the fake implementation of
+    the compiled op runs them too) -> (B, H, Hkv, T, Smax, D, inv, container, P), in this order: TypeError for a non-tensor, a q that is not
+    bfloat16 or float16, codes (new or cached) whose dtype is not num_bits' container's, divisors that are not float32, lengths / starts
+    that are not int32, a rotary that is not a (cos, sin) pair, a head_dim / scale of the wrong type or both or neither; ValueError for a q
+    that is not a non-empty [B, H, T, D] with T <= 16 and D of 64 or 128, new codes that are not one [B, Hkv, T, D] (int4: D / 2) with Hkv
+    dividing H, new divisors that are not [B, T], code caches that are not one non-empty [B, Hkv, Smax, D or D / 2], divisor caches that
+    are not [B, Smax], a cache whose last stride is not 1 (it is written in place, so it is not copied), lengths / starts that are not
+    [B], tables of another dtype or shape or with fewer than Smax rows, tensors on two devices.  P: 0 without tables."""
+    named = dict(q=q, k_codes_new=k_codes_new, k_t2_new=k_t2_new, v_codes_new=v_codes_new, v_t2_new=v_t2_new, k_code_cache=k_code_cache, k_t2_cache=k_t2_cache,
+                 v_code_cache=v_code_cache, v_t2_cache=v_t2_cache, cache_lens=cache_lens)
+    if cache_starts is not None:
+        named["cache_starts"] = cache_starts
+    _row_tensors(what, **named)
+    container = kv_container(num_bits)
+    cdt, _, per = _KV_CONTAINERS[container]
+    if q.dtype not in _DECODE_DTYPES:
+        raise TypeError(f"{what}: q of {q.dtype} is not served: bfloat16 or float16")
+    codes = (k_codes_new, v_codes_new, k_code_cache, v_code_cache)
+    if any(t.dtype != cdt for t in codes):
+        raise TypeError(f"{what}: num_bits={num_bits} takes {container} codes ({cdt}), got {', '.join(str(t.dtype) for t in codes)}")
+    t2s = (k_t2_new, v_t2_new, k_t2_cache, v_t2_cache)
+    if any(t.dtype != torch.float32 for t in t2s):
+        raise TypeError(f"{what}: the divisors are float32 (column 1 of QuantExport.scales), got {', '.join(str(t.dtype) for t in t2s)}")
+    for name in ("cache_lens", "cache_starts"):
+        if name in named and named[name].dtype != torch.int32:
+            raise TypeError(f"{what}: {name} is an int32 tensor, got {named[name].dtype}")
+    if rotary is not None and not (isinstance(rotary, (tuple, list)) and len(rotary) == 2):
+        raise TypeError(f"{what}: rotary is None or the pair (cos, sin), got {type(rotary).__name__}")
+    inv = attn_inv(head_dim, scale, what)
+    if q.dim() != 4 or q.numel() == 0 or q.shape[2] > DECODE_MAX_T or q.shape[3] not in DECODE_HEAD_DIMS:
+        raise ValueError(f"{what}: q is a non-empty [B, H, T, D] with T <= {DECODE_MAX_T} and D in {DECODE_HEAD_DIMS}, got {tuple(q.shape)}")
+    B, H, T, D = q.shape
+    Hkv = k_codes_new.shape[1] if k_codes_new.dim() == 4 else 0
+    if Hkv == 0 or H % Hkv != 0 or tuple(k_codes_new.shape) != (B, Hkv, T, D // per) or tuple(v_codes_new.shape) != (B, Hkv, T, D // per):
+        raise ValueError(f"{what}: the new {container} codes of k and v are one [{B}, Hkv, {T}, {D // per}] with Hkv dividing H = {H}, got "
+                         f"{tuple(k_codes_new.shape)} and {tuple(v_codes_new.shape)}")
+    if tuple(k_t2_new.shape) != (B, T) or tuple(v_t2_new.shape) != (B, T):
+        raise ValueError(f"{what}: the new divisors are [{B}, {T}], one per token, got {tuple(k_t2_new.shape)} and {tuple(v_t2_new.shape)}")
+    if (k_code_cache.dim() != 4 or k_code_cache.shape[2] == 0 or tuple(k_code_cache.shape) != (B, Hkv, k_code_cache.shape[2], D // per)
+            or tuple(v_code_cache.shape) != tuple(k_code_cache.shape)):
+        raise ValueError(f"{what}: the code caches are one non-empty [{B}, {Hkv}, Smax, {D // per}], got {tuple(k_code_cache.shape)} and {tuple(v_code_cache.shape)}")
+    Smax = k_code_cache.shape[2]
+    if tuple(k_t2_cache.shape) != (B, Smax) or tuple(v_t2_cache.shape) != (B, Smax):
+        raise ValueError(f"{what}: the divisor caches are [{B}, {Smax}], got {tuple(k_t2_cache.shape)} and {tuple(v_t2_cache.shape)}")
+    for name in ("k_code_cache", "k_t2_cache", "v_code_cache", "v_t2_cache"):
+        if named[name].stride(-1) != 1:
+            raise ValueError(f"{what}: {name} has a last stride of {named[name].stride(-1)}: the cache is written in place, so it is not copied; give one with "
+                             "a last stride of 1")
+    for name in ("cache_lens", "cache_starts"):
+        if name in named and tuple(named[name].shape) != (B,):
+            raise ValueError(f"{what}: {name} is [{B}], got {tuple(named[name].shape)}")
+    P = 0
+    if rotary is not None:
+        check_rope_tables(rotary[0], rotary[1], None, q, B, T, D, what, q.dtype)
+        P = rotary[0].shape[-2]
+        if P < Smax:
+            raise ValueError(f"{what}: keys at the positions 0 .. Smax - 1 need tables of Smax = {Smax} rows, got P = {P}")
+    for name, t in named.items():
+        if t.device != q.device:
+            raise ValueError(f"{what}: q is on {q.device}, {name} on {t.device}")
+    return B, H, Hkv, T, Smax, D, inv, container, P
+
+
+def attn_cached_codes_workspace(B, H, T, D, Smax, cus, dtype=torch.bfloat16, num_bits=8, kv_heads=None):
+    """-> (bytes, nsplit): the workspace fqw_attn_cached_codes_fwd needs on a device of `cus` compute units and the chunks it cuts every
+    batch row's keys into at most: attn_cached_workspace's, functions of the shapes alone"""
+    nbytes, nsplit = ctypes.c_size_t(0), ctypes.c_int64(0)
+    rc = _lib.lib().fqw_attn_cached_codes_workspace(B, H, H if kv_heads is None else kv_heads, T, D, Smax, cus, _OUT_DTYPES[dtype],
+                                                    _KV_CONTAINERS[kv_container(num_bits)][1], ctypes.byref(nbytes), ctypes.byref(nsplit))
+    _lib.check(rc, "attn_cached_codes_workspace")
+    return nbytes.value, nsplit.value
+
+
+def attn_cached_codes_forward(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache, v_t2_cache, cache_lens, head_dim=None,
+                              scale=None, num_bits=8, rotary=None, cache_starts=None):
+    """-> out [B, T, H, D] (contiguous): one launch that writes the new codes [B, Hkv, T, D or D / 2] and divisors [B, T] into rows
+    cache_lens[b] .. + T - 1 of the preallocated code caches [B, Hkv, Smax, D or D / 2] and divisor caches [B, Smax] IN PLACE and attends
+    q [B, H, T, D] to the keys cache_starts[b] <= s <= cache_lens[b] + t of the updated cache, k = rope(rb(code / t2)) at position
+    s - cache_starts[b] and v = rb(code / t2) made in registers.  The int32 lengths and starts stay on the device.
+    q and the new tensors are read where they lie (a last stride that is not 1, tables that are not in q's dtype or not dense and int32s
+    that are not contiguous are copied once: copy_route); the caches are never copied.  Forward only."""
+    B, H, Hkv, T, Smax, D, inv, container, P = check_attn_cached_codes(q, k_codes_new, k_t2_new, v_codes_new, v_t2_new, k_code_cache, k_t2_cache, v_code_cache,
+                                                                       v_t2_cache, cache_lens, head_dim, scale, num_bits, rotary, cache_starts)
+    _prep(q, "attn_cached_codes_forward")
+
+    def dense(t, ok):
+        if ok:
+            return t
+        cached_codes_counts["copy_route"] += 1
+        return t.contiguous()
+    q, kn, vn, ktn, vtn = (dense(t.detach(), t.stride(-1) == 1 or t.shape[-1] == 1) for t in (q, k_codes_new, v_codes_new, k_t2_new, v_t2_new))
+    lens, starts = (t if t is None else dense(t, t.is_contiguous()) for t in (cache_lens, cache_starts))
+    kc, vc, ktc, vtc = (t.detach() for t in (k_code_cache, v_code_cache, k_t2_cache, v_t2_cache))
+    cos = sin = None
+    if rotary is not None:
+        cos, sin = (dense(t.detach().reshape(P, D), t.dtype == q.dtype and t.is_contiguous()).to(q.dtype) for t in rotary)
+    cus = _decode_cus(q)
+    nbytes, _ = attn_cached_codes_workspace(B, H, T, D, Smax, cus, q.dtype, num_bits, Hkv)
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if nbytes else None
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    rc = _launch(q, _lib.lib().fqw_attn_cached_codes_fwd, q.data_ptr(), kn.data_ptr(), ktn.data_ptr(), vn.data_ptr(), vtn.data_ptr(), kc.data_ptr(),
+                 ktc.data_ptr(), vc.data_ptr(), vtc.data_ptr(), lens.data_ptr(), ptr(starts), ptr(cos), ptr(sin), out.data_ptr(), ptr(ws), nbytes,
+                 *q.stride()[:3], *kn.stride()[:3], *vn.stride()[:3], *kc.stride()[:3], *vc.stride()[:3], ktn.stride(0), vtn.stride(0), ktc.stride(0),
+                 vtc.stride(0), P, B, H, Hkv, T, Smax, D, cus, inv, _OUT_DTYPES[q.dtype], _KV_CONTAINERS[container][1])
+    _lib.check(rc, "attn_cached_codes_forward")
+    cached_codes_counts["fwd_launch"] += 1
+    return out
+
+
 def kv_codes_materialize(codes, t2, dtype, num_bits, rotary=None, key_positions=None):
     """-> [B, H, S, D] of `dtype`: the tensor a codes cache stands for, in torch ops (the route of the calls the kernel does not serve and
     of the CPU): unpack, divide by t2 in fp32, round to the dtype, rotate with the eager chain's roundings"""
